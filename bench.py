@@ -58,6 +58,11 @@ def main():
     ap.add_argument("--proposal", default="uniform", choices=["uniform", "heatbath"], help="auxiliary: heatbath = proposal_method fast_heatbath (off_diagonal_move_chem_efficient_heatbath, "
                     "two walker slots per child) on the shipped C2 integrals with 10 electrons -- the synthetic system the reference's own check accepts; one GPU, no CPU baseline leg")
     ap.add_argument("--heg-cutoff", type=float, default=2.3, help="plane-wave cutoff radius (2.3 -> 57 orbitals; the GPU path holds at most 64)")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline: HIP events on the timed region's kernels, the roofline "
+                    "(per-kernel times, an untimed stage breakdown, the PMC traffic of profiles/) and, on the default config, the CPU baselines "
+                    "and the energy check against the CPU restatement (--no-cpu-baseline drops those two)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (its 16 step sums and the "
+                    "walker list it left) to DIR/<name>.npy, float64 / float32")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -176,11 +181,13 @@ def main():
     sharded = isinstance(walk, H.ShardedWalk)
     slowest = None
     shard_split = None
+    # --full: HIP events around the annihilation kernel's launch only (every 8th step), accumulated from the timed region on
+    events = 1 if args.full and not os.environ.get('SQMC_BENCH_NO_EVENTS') else 0
 
     if sharded and not walk.in_library:
         for _ in range(args.equil + args.warmup):
             walk.step()
-        walk.g.set_timing(1)
+        walk.g.set_timing(events)
         fence()
         t0 = time.perf_counter()
         rows = [walk.step() for _ in range(args.steps)]
@@ -190,16 +197,18 @@ def main():
         # out[5] (nwalk) is already the all-reduced global count; spawns (out[15]) are rank-local
         nwalk_sum, spawn_sum = float(stats[:, 5].sum()) / world, float(stats[:, 15].sum())
         e_num, e_den = float((stats[:, 3] * np.sign(stats[:, 2])).sum()), float(np.abs(stats[:, 2]).sum())
-        timers_timed = walk.g.timing()
-        spawn_ms = dict(timers_timed).get("spawn", float("nan"))
-        walk.g.set_timing(2)
-        for _ in range(10):
-            walk.step()
-        stage_ms = dict(walk.g.timing())
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, stats[-1], walk.g, rank, world)
+        if args.full:
+            timers_timed = walk.g.timing()
+            walk.g.set_timing(2)
+            for _ in range(10):
+                walk.step()
+            stage_ms = dict(walk.g.timing())
     else:
         # equilibration + warmup (untimed), then EXACTLY --steps timed steps inside sqmc_gpu_run
         walk.run(args.equil, keep_stats=False)
-        walk.g.set_timing(0 if os.environ.get('SQMC_BENCH_NO_EVENTS') else 1)           # HIP events around the annihilation kernel's launch only (every 8th step), accumulated from here on
+        walk.g.set_timing(events)
         # A host that walks in blocks calls sqmc_gpu_run once per block; with chained runs the last step of a call enqueues the head
         # of the first step of the next one, as every step does for its successor.  Warm-up and timed region are two such calls: the K
         # timed steps then are K tails and K heads (the last one enqueues -- and the closing fence waits for -- the head of a step
@@ -219,13 +228,18 @@ def main():
         e_num, e_den = float((stats[:, 3] * np.sign(stats[:, 2])).sum()), float(np.abs(stats[:, 2]).sum())
         slowest = walk.g.slowest_steps()                   # wall clock of the slowest timed steps: host jitter, reruns
         if chain: walk.g.set_chained_runs(False)          # forgets the head the last timed step enqueued
-        timers_timed = walk.g.timing()                     # mean ms per k_spawn / k_anneal launch (warm-up and timed steps)
+        if args.full:
+            timers_timed = walk.g.timing()                 # mean ms per k_spawn / k_anneal launch (warm-up and timed steps)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, stats[-1], walk.g, rank, world)
+        if args.full:
+            walk.g.set_timing(2)                            # informational stage breakdown from an untimed tail
+            walk.run(20, keep_stats=False)
+            stage_ms = dict(walk.g.timing())
+    if args.full:
         spawn_ms = dict(timers_timed).get("spawn", float('nan'))
-        walk.g.set_timing(2)                                # informational stage breakdown from an untimed tail
-        walk.run(20, keep_stats=False)
-        stage_ms = dict(walk.g.timing())
-    if spawn_ms != spawn_ms:                                # a semistochastic walk times only its annihilation kernel inside the timed region
-        spawn_ms = stage_ms.get("spawn", spawn_ms)
+        if spawn_ms != spawn_ms:                            # a semistochastic walk times only its annihilation kernel inside the timed region
+            spawn_ms = stage_ms.get("spawn", spawn_ms)
     tot = torch.tensor([nwalk_sum, spawn_sum, dt], dtype=torch.float64, device=comm_dev)
     if multi:
         mx = tot.clone(); dist.all_reduce(mx, op=dist.ReduceOp.MAX)
@@ -235,38 +249,8 @@ def main():
 
     if rank == 0:
         value = nwalk_all / dt
-        # Dominant kernel = the longest one on the step's critical path: k_anneal (annihilation + rounding + compaction
-        # + estimator sums, one launch per step).  Its timer is the pair of HIP events hipExtLaunchKernelGGL attaches
-        # to that launch on the library's stream: the kernel's own start/stop timestamps, what rocprofv3
-        # --kernel-trace reports.  Algorithmic bytes per launch: 68 B per occupied determinant
-        # (walker read + write) + 58 B per child proposal (26 B read-back + 32 B annihilation slot; the other 26 B
-        # of a spawn's 84 B are its write in k_spawn, reported beside it).
         n_avg, s_avg = nwalk_sum / args.steps, spawn_sum / args.steps
-        timers = {k: v for k, v in dict(timers_timed).items() if v == v}
-        if "anneal" not in timers and "anneal" in stage_ms:      # fewer timed steps than the event stride: take the untimed tail's launches
-            timers["anneal"], spawn_ms = stage_ms["anneal"], stage_ms.get("spawn", spawn_ms)
-        if "anneal" in timers:
-            dom, dom_ms, dom_bytes = "k_anneal", timers["anneal"], 68.0 * n_avg + 58.0 * s_avg
-        else:                                  # semistochastic = f keeps the unfused tail: k_spawn is then the longest single kernel
-            dom, dom_ms, dom_bytes = "k_spawn", spawn_ms, 26.0 * s_avg + 34.0 * n_avg
-        ach = dom_bytes / (dom_ms * 1e-3) / 1e9
-        step_bytes = 68.0 * n_avg + 84.0 * s_avg
-        default_cfg = (args.system == "c2" and args.target == 1e5 and world == 1 and not args.hf_to_psit and args.proposal == "uniform")
-        tr = load_traffic() if default_cfg else None
-
-        def traffic_of(kern):
-            """PMC traffic per launch: FETCH_SIZE weighted by the calibration of tools/calib_fetch.hip for this kernel's mix of
-            streamed and gathered reads, + WRITE_SIZE; beside it the raw (x1) and guide-default (x2) readings of FETCH_SIZE"""
-            if not tr or kern not in tr.get("kernels", {}):
-                return None, None
-            k = tr["kernels"][kern]
-            return k["hbm_bytes_calibrated"], {"fetch_x1": k["hbm_bytes_x1"], "fetch_x2": k["hbm_bytes_x2"], "calibrated": k["hbm_bytes_calibrated"],
-                                               "profiled_kernel": k.get("kernel", "")[:60],
-                                               "source": os.path.relpath(TRAFFIC_JSON, ROOT), "commit": tr.get("commit")}
-
         tail = walk.g.tail_stats()
-        # which annihilation kernel the timed launches were: the short-list tail's (one block per key range) or the radix tail's
-        dom_name = "k_anneal_bucket" if (dom == "k_anneal" and tail[0] - tail[1] > (args.steps + args.warmup) // 2) else dom
         line = {
             "metric": "walker-steps/sec", "value": value, "unit": "walker-steps/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": args.scaling if sharded else "weak",
@@ -281,16 +265,10 @@ def main():
                        "short_list_tail": dict(zip(("bucket_steps", "rerun_through_radix_tail"), tail)),
                        "slowest_steps_us": slowest, "chained_runs": bool(not sharded and not os.environ.get('SQMC_BENCH_NO_CHAIN')),
                        "sharded_step_host_split_us_rank0": shard_split},
-            "roofline": {"bound": "hbm", "kernel": dom_name, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
-                         "traffic": traffic_of(dom)[0], "traffic_detail": traffic_of(dom)[1], "ms_per_launch": dom_ms,
-                         "algorithmic_bytes_per_launch": dom_bytes,
-                         "other_kernels": {"k_spawn": {"ms_per_launch": spawn_ms, "algorithmic_bytes_per_launch": 26.0 * s_avg + 34.0 * n_avg,
-                                                       "achieved": (26.0 * s_avg + 34.0 * n_avg) / (spawn_ms * 1e-3) / 1e9, "traffic": traffic_of("k_spawn")[0]}},
-                         "whole_step": {"algorithmic_bytes": step_bytes, "achieved": step_bytes / (dt / args.steps) / 1e9,
-                                        "frac": step_bytes / (dt / args.steps) / 1e9 / HBM_PEAK_GBS},
-                         "stage_ms_per_step": stage_ms},
         }
-        if not args.no_cpu_baseline and world == 1 and args.system == "c2" and not args.hf_to_psit and args.proposal == "uniform":
+        if args.full:
+            line["roofline"] = roofline(args, world, timers_timed, stage_ms, spawn_ms, n_avg, s_avg, dt, tail)
+        if args.full and not args.no_cpu_baseline and world == 1 and args.system == "c2" and not args.hf_to_psit and args.proposal == "uniform":
             cpu = cpu_leg(walk, hst, n_avg)
             line["cpu_baseline"] = cpu["one_core"]
             line["cpu_baseline_all_cores"] = cpu["all_cores"]
@@ -303,6 +281,72 @@ def main():
     if multi:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def roofline(args, world, timers_timed, stage_ms, spawn_ms, n_avg, s_avg, dt, tail):
+    """--full: the dominant kernel's achieved HBM bandwidth against the chip's, with the PMC traffic of profiles/ where it was taken
+    for this config."""
+    # Dominant kernel = the longest one on the step's critical path: k_anneal (annihilation + rounding + compaction
+    # + estimator sums, one launch per step).  Its timer is the pair of HIP events hipExtLaunchKernelGGL attaches
+    # to that launch on the library's stream: the kernel's own start/stop timestamps, what rocprofv3
+    # --kernel-trace reports.  Algorithmic bytes per launch (SURVEY.md section 8d): 68 B per occupied determinant
+    # (walker read + write) + 58 B per child proposal (26 B read-back + 32 B annihilation slot; the other 26 B
+    # of a spawn's 84 B are its write in k_spawn, reported beside it).
+    timers = {k: v for k, v in dict(timers_timed).items() if v == v}
+    if "anneal" not in timers and "anneal" in stage_ms:      # fewer timed steps than the event stride: take the untimed tail's launches
+        timers["anneal"], spawn_ms = stage_ms["anneal"], stage_ms.get("spawn", spawn_ms)
+    if "anneal" in timers:
+        dom, dom_ms, dom_bytes = "k_anneal", timers["anneal"], 68.0 * n_avg + 58.0 * s_avg
+    else:                                  # semistochastic = f keeps the unfused tail: k_spawn is then the longest single kernel
+        dom, dom_ms, dom_bytes = "k_spawn", spawn_ms, 26.0 * s_avg + 34.0 * n_avg
+    ach = dom_bytes / (dom_ms * 1e-3) / 1e9
+    step_bytes = 68.0 * n_avg + 84.0 * s_avg
+    default_cfg = (args.system == "c2" and args.target == 1e5 and world == 1 and not args.hf_to_psit and args.proposal == "uniform")
+    tr = load_traffic() if default_cfg else None
+
+    def traffic_of(kern):
+        """PMC traffic per launch: FETCH_SIZE weighted by the calibration of tools/calib_fetch.hip for this kernel's mix of
+        streamed and gathered reads, + WRITE_SIZE; beside it the raw (x1) and guide-default (x2) readings of FETCH_SIZE"""
+        if not tr or kern not in tr.get("kernels", {}):
+            return None, None
+        k = tr["kernels"][kern]
+        return k["hbm_bytes_calibrated"], {"fetch_x1": k["hbm_bytes_x1"], "fetch_x2": k["hbm_bytes_x2"], "calibrated": k["hbm_bytes_calibrated"],
+                                           "profiled_kernel": k.get("kernel", "")[:60],
+                                           "source": os.path.relpath(TRAFFIC_JSON, ROOT), "commit": tr.get("commit")}
+
+    # which annihilation kernel the timed launches were: the short-list tail's (one block per key range) or the radix tail's
+    dom_name = "k_anneal_bucket" if (dom == "k_anneal" and tail[0] - tail[1] > (args.steps + args.warmup) // 2) else dom
+    return {"bound": "hbm", "kernel": dom_name, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
+            "traffic": traffic_of(dom)[0], "traffic_detail": traffic_of(dom)[1], "ms_per_launch": dom_ms,
+            "algorithmic_bytes_per_launch": dom_bytes,
+            "other_kernels": {"k_spawn": {"ms_per_launch": spawn_ms, "algorithmic_bytes_per_launch": 26.0 * s_avg + 34.0 * n_avg,
+                                          "achieved": (26.0 * s_avg + 34.0 * n_avg) / (spawn_ms * 1e-3) / 1e9, "traffic": traffic_of("k_spawn")[0]}},
+            "whole_step": {"algorithmic_bytes": step_bytes, "achieved": step_bytes / (dt / args.steps) / 1e9,
+                           "frac": step_bytes / (dt / args.steps) / 1e9 / HBM_PEAK_GBS},
+            "stage_ms_per_step": stage_ms}
+
+
+def dump_outputs(out_dir, sums, g, rank, world, budget=64 << 20):
+    """--dump-outputs: what a caller of the timed path holds after its last step, the step's 16 sums (its row of sqmc_gpu_run's
+    stats) and the walker list it left on the device (sqmc_gpu_download_walkers).  Determinants are written as their high and low
+    32-bit halves in float64, exact for any bit string; the int8 flags as float32.  A list larger than the budget (64 MB over all
+    files and ranks) is cut to a fixed, seeded sample of its rows, in list order.  N > 1: each rank writes its shard, as <name>_rank<r>."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    w = g.download_walkers()
+    n = len(w["up"])
+    row_bytes = 2 * 16 + 4 * 8 + 2 * 4
+    keep = min(n, max(0, (budget // world - 64 * 1024) // row_bytes))        # 64 KiB: the step sums and the .npy headers
+    rows = np.sort(np.random.default_rng(20261016).choice(n, keep, replace=False)) if keep < n else slice(None)
+    halves = lambda d: np.stack([(d >> np.uint64(32)).astype(np.float64), (d & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=1)
+    out = {"step_sums": np.asarray(sums, np.float64), "walkers_up": halves(w["up"][rows]), "walkers_dn": halves(w["dn"][rows])}
+    for k in ("wt", "matrix_elements", "e_num", "e_den"):
+        out["walkers_" + k] = w[k][rows].astype(np.float64)
+    for k in ("imp_distance", "initiator"):
+        out["walkers_" + k] = w[k][rows].astype(np.float32)
+    suffix = "_rank%d" % rank if world > 1 else ""
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
 
 
 def launch_ranks(n):

@@ -1,6 +1,10 @@
 #!/usr/bin/env python3
 """Regenerates the small fixtures in this directory.
 
+  ref_build.npz          what the REAL reference object code (oracle/_ref) returns on the inputs of the tests in
+                         tests/test_oracle.py that pin the oracle against it (rannyu, random_int, permutation_factor(2),
+                         merge_sort2_up_dn, the HEG k-vector sort), with the inputs that are drawn at random; those tests
+                         read it, so that they run where the reference is absent -- needs /root/reference, like rannyu.json.
   rannyu.json            first 1000 rannyu() reals for both seeds of the reference's input
                          line 1, produced by the REAL reference object code (oracle/_ref,
                          built from /root/reference/src/rannyu.f90 unmodified) -- needs
@@ -46,6 +50,27 @@ def rannyu_fixture():
         R.ref_rannyu_fill(C.c_int(1000), out.ctypes.data_as(C.c_void_p))
         recs.append({"seed": seed, "hex": [float(x).hex() for x in out]})
     json.dump(recs, open(os.path.join(HERE, "rannyu.json"), "w"))
+
+
+def ref_build_fixture():
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_oracle as T
+    R = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "libsqmc_ref.so"), mode=os.RTLD_LAZY)
+    rec = {}
+    for k, seed in enumerate(T.SEEDS):
+        rec["rannyu_%d" % k] = T.ref_rannyu(R, seed, 10000)
+    for nmax in T.RANDOM_INT_NMAX:
+        rec["random_int_%d" % nmax] = T.ref_random_int(R, T.SEEDS[0], nmax, 2000)
+    rng = np.random.default_rng(5)
+    rec["perm1_a"], rec["perm1_b"] = T._rand_pairs(rng, 3000, 1)
+    rec["perm2_a"], rec["perm2_b"] = T._rand_pairs(rng, 3000, 2)
+    rec["perm1"] = T.ref_permutation_factor(R, rec["perm1_a"], rec["perm1_b"])
+    rec["perm2"] = T.ref_permutation_factor2(R, rec["perm2_a"], rec["perm2_b"])
+    rng = np.random.default_rng(9)
+    rec["sort_up"], rec["sort_dn"] = rng.integers(0, 40, 5000).astype(np.int64), rng.integers(0, 40, 5000).astype(np.int64)
+    rec["sort_order"] = T.ref_merge_sort2_up_dn(R, rec["sort_up"], rec["sort_dn"])
+    rec["heg14_k_sorted"] = T.ref_sort_real_rank2(R, T.heg14_k_grid(O.HegSystem(3, 0.5, 14, 7, 1.49)))
+    np.savez_compressed(os.path.join(HERE, "ref_build.npz"), **rec)
 
 
 def walk_fixture():
@@ -105,4 +130,5 @@ if __name__ == "__main__":
     psit_fixture()
     if os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libsqmc_ref.so")):
         rannyu_fixture()
+        ref_build_fixture()
     walk_fixture()

@@ -6,13 +6,13 @@ set -e
 name=$1; shift
 out=gpurun_out/prof_$name
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline "$@" > $out.trace.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --full --steps 200 --warmup 20 --no-cpu-baseline "$@" > $out.trace.log 2>&1
 echo "trace done" > gpurun_out/progress_$name.txt
-timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/fetch -- python3 bench.py --steps 30 --warmup 5 --equil 300 --no-cpu-baseline "$@" > $out.fetch.log 2>&1
+timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/fetch -- python3 bench.py --full --steps 30 --warmup 5 --equil 300 --no-cpu-baseline "$@" > $out.fetch.log 2>&1
 echo "fetch done" >> gpurun_out/progress_$name.txt
-timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/write -- python3 bench.py --steps 30 --warmup 5 --equil 300 --no-cpu-baseline "$@" > $out.write.log 2>&1
+timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/write -- python3 bench.py --full --steps 30 --warmup 5 --equil 300 --no-cpu-baseline "$@" > $out.write.log 2>&1
 echo "write done" >> gpurun_out/progress_$name.txt
-timeout -k 10 300 rocprofv3 --pmc OccupancyPercent MeanOccupancyPerCU --output-format csv -d $out/occ -- python3 bench.py --steps 30 --warmup 5 --equil 300 --no-cpu-baseline "$@" > $out.occ.log 2>&1
+timeout -k 10 300 rocprofv3 --pmc OccupancyPercent MeanOccupancyPerCU --output-format csv -d $out/occ -- python3 bench.py --full --steps 30 --warmup 5 --equil 300 --no-cpu-baseline "$@" > $out.occ.log 2>&1
 echo "occ done" >> gpurun_out/progress_$name.txt
 # FETCH_SIZE calibration on known byte counts (8-byte streams, 32-byte gathers), same session
 mkdir -p $out && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 tools/calib_fetch.hip -o $out/calib_fetch

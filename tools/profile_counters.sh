@@ -21,7 +21,7 @@ for group in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_AN
   i=$((i+1))
   cs=$(pick $group)
   [ -z "$cs" ] && continue
-  timeout -k 10 300 rocprofv3 --pmc $cs --output-format csv -d $out/pmc$i -- python3 bench.py --steps 30 --warmup 5 --equil 300 --no-cpu-baseline "$@" > $out.pmc$i.log 2>&1
+  timeout -k 10 300 rocprofv3 --pmc $cs --output-format csv -d $out/pmc$i -- python3 bench.py --full --steps 30 --warmup 5 --equil 300 --no-cpu-baseline "$@" > $out.pmc$i.log 2>&1
   echo "pass $i ($cs) done rc=$?" >> gpurun_out/progress_$name.txt
 done
 python3 tools/summarize_counters.py $out gpurun_out/${name}_counters.txt > /dev/null

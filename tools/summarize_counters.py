@@ -10,7 +10,7 @@ def main(base, out):
     for f in sorted(glob.glob(base + "/pmc*/*/*counter_collection.csv")):
         for r in csv.DictReader(open(f)):
             acc[r["Kernel_Name"].split("(")[0][:60]][r["Counter_Name"]].append(float(r["Counter_Value"]))
-    lines = ["# rocprofv3 --pmc <group> -- python3 bench.py --steps 30 --warmup 5 --equil 300 --no-cpu-baseline [args]; one pass per group;",
+    lines = ["# rocprofv3 --pmc <group> -- python3 bench.py --full --steps 30 --warmup 5 --equil 300 --no-cpu-baseline [args]; one pass per group;",
              "# averages over the last 30 launches of each kernel (SQ_* cycle counters are quad-cycles summed over all waves / SIMDs)"]
     want = [k for k in acc if any(s in k for s in ("k_anneal", "k_spawn", "k_diag", "k_psit", "rs_", "merge_path", "scan_lookback", "k_gate"))]
     for k in sorted(want, key=lambda k: -sum(acc[k].get("SQ_WAVE_CYCLES", [0])[-30:])):

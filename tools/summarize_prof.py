@@ -9,7 +9,7 @@ def main(base, out):
     lines = []
     ks = glob.glob(base + '/trace/*/*kernel_stats.csv')
     if ks:
-        lines.append("# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline")
+        lines.append("# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 200 --warmup 20 --no-cpu-baseline")
         lines.append("%-64s %8s %12s %10s" % ("kernel", "calls", "avg_us", "percent"))
         for r in list(csv.DictReader(open(ks[0])))[:30]:
             lines.append("%-64s %8s %12.2f %10s" % (r['Name'][:64], r['Calls'], float(r['AverageNs']) / 1e3, r['Percentage']))
@@ -24,7 +24,7 @@ def main(base, out):
     w = pmc(base + '/write/*/*counter_collection.csv', 'WRITE_SIZE')
     if f:
         lines.append("")
-        lines.append("# separate passes: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE -- python3 bench.py --steps 30 --warmup 5 --equil 300 --no-cpu-baseline")
+        lines.append("# separate passes: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE -- python3 bench.py --full --steps 30 --warmup 5 --equil 300 --no-cpu-baseline")
         lines.append("# averages over the last 30 launches of each kernel; HBM bytes/launch = (2*FETCH_SIZE + WRITE_SIZE) * 1024")
         lines.append("%-50s %14s %14s %16s" % ("kernel", "FETCH_SIZE_KiB", "WRITE_SIZE_KiB", "hbm_bytes/launch"))
         for k in sorted(f, key=lambda k: -sum(f[k]))[:16]:
