@@ -178,7 +178,8 @@ int sqmc_gpu_set_ct_table(sqmc_gpu_ctx *ctx, int64_t n, const uint64_t *up, cons
  *     download returns it so.  The deterministic space must lie inside C(T) and only the first state may be a permanent initiator,
  *     as in the reference's own set-up.
  * sum_order: 1 = the step's three long sums (first row over C(T), first row over Psi_T, T^-1) through a fixed 64-ary tree;
- * 0 = left to right as the reference's loops run (one lane: slow).  One rank, COUNTER or REPLAY discipline, uniform proposal.
+ * 0 = left to right as the reference's loops run (one lane: slow).  One rank, COUNTER or REPLAY discipline, uniform proposal
+ * (over ranks: sqmc_gpu_set_hf_to_psit_shard below).
  * tests/golden/README_hf_to_psit.md records what parity is defined against (the reference's merge for this variant cannot run as written). */
 int sqmc_gpu_set_hf_to_psit(sqmc_gpu_ctx *ctx, int64_t n_psit, const int64_t *psit_ct_index, const double *cdet_psi_t,
                             const double *diag_elems, int32_t sum_order);
@@ -279,6 +280,30 @@ int sqmc_gpu_shard_finish(sqmc_gpu_ctx *ctx, const sqmc_step_params *p, const ui
  * communicator is attached, sqmc_gpu_shard_finish also all-reduces; use either the three-phase
  * calls without a communicator or shard_step with one. */
 #define SQMC_COMM_ID_BYTES 128
+
+/* hf_to_psit over ranks (do_walk.f90:1808-1886, 2272-2288, 2304-2320, 2394-2462, 2701-2722): the step variant of
+ * sqmc_gpu_set_hf_to_psit on a sharded walk, chem and HEG, uniform proposal, COUNTER discipline.  Call after sqmc_gpu_shard_config
+ * (with the global projector of sqmc_gpu_set_hf_to_psit and the global C(T) table set on every rank), before sqmc_gpu_upload_walkers:
+ *   - ct_index[n_ct_local] (1-based, increasing): the C(T) determinants this rank owns, as positions in the C(T) list
+ *     (my_ndet_psi_t_connected); they sit at the head of its walker list in C(T) order; diag_elems[n_ct_local] as for one rank;
+ *   - psit_slot[n_psit_local] (1-based in that share, increasing): my_locations_of_psit; psit_mask[k]: the index of the entry in
+ *     Psi_T in label order (ndet_psit_mask); cdet_psi_t[n_psit]: all of Psi_T's coefficients;
+ *   - the first state (C(T)'s and Psi_T's first determinant) is at slot 1 of its owner (iown_first = iown_psit1); a share may be empty.
+ * Exchanges, beside the existing three: x_global is n_imp + 2*nranks doubles -- slots n_imp + r and n_imp + nranks + r carry rank r's
+ * partials of the first row over C(T) and over Psi_T, zero from every other rank, so its all-reduce is exact -- and, after the
+ * merge, one all-reduce (SUM) of nranks + 1 doubles: rank r's partial of T^-1's sum in entry r, the owner's weight of the first
+ * state in entry nranks.  With a communicator the library issues it; without one, finish each step with
+ * sqmc_gpu_shard_finish_psit, which writes the vector to reduce_buf_dev (device, nranks + 1 doubles), synchronises, calls
+ * allreduce(reduce_buf_dev, nranks + 1, user) -- which must return 0 once the buffer holds the sum over ranks -- and goes on.
+ * Sum order: inside a rank, the local terms through the fixed 64-ary tree (sum_order 1) or left to right (0), as for one rank;
+ * across ranks, the partials added in rank order.  One rank is therefore the one-rank step bit for bit, and every rank sees the
+ * same bits.  sqmc_gpu_shard_run runs this variant unpipelined.  Refused: fast_heatbath tables, the Hubbard model. */
+typedef int (*sqmc_allreduce_fn)(double *buf_dev, int64_t n, void *user);
+int sqmc_gpu_set_hf_to_psit_shard(sqmc_gpu_ctx *ctx, int64_t n_ct_local, const int64_t *ct_index, const double *diag_elems,
+                                  int64_t n_psit_local, const int64_t *psit_slot, const int64_t *psit_mask, int64_t n_psit,
+                                  const double *cdet_psi_t, int32_t sum_order);
+int sqmc_gpu_shard_finish_psit(sqmc_gpu_ctx *ctx, const sqmc_step_params *p, const uint64_t *recv_dev, int64_t n_recv,
+                               double *reduce_buf_dev, sqmc_allreduce_fn allreduce, void *user, double out_stats[16]);
 int sqmc_gpu_comm_unique_id(uint8_t id[SQMC_COMM_ID_BYTES]);
 int sqmc_gpu_comm_init(sqmc_gpu_ctx *ctx, const uint8_t id[SQMC_COMM_ID_BYTES]);
 /* number of ranks RCCL itself reports for the communicator (ncclCommCount; the reference's ncores, mpi_routines.f90:310) */

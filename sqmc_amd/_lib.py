@@ -23,13 +23,16 @@ _LIB = None
 
 EXPORTS = [
     "sqmc_gpu_set_device", "sqmc_gpu_init_chem", "sqmc_gpu_init_heg", "sqmc_gpu_init_hubbard", "sqmc_gpu_finalize", "sqmc_gpu_last_error", "sqmc_gpu_set_hb_tables", "sqmc_gpu_set_heatbath_tables", "sqmc_gpu_setup_efficient_heatbath", "sqmc_gpu_get_heatbath_tables", "sqmc_gpu_propose_heatbath_batch", "sqmc_gpu_set_projector",
-    "sqmc_gpu_scale_projector", "sqmc_gpu_set_ct_table", "sqmc_gpu_set_hf_to_psit", "sqmc_gpu_upload_walkers", "sqmc_gpu_num_walkers",
+    "sqmc_gpu_scale_projector", "sqmc_gpu_set_ct_table", "sqmc_gpu_set_hf_to_psit", "sqmc_gpu_set_hf_to_psit_shard", "sqmc_gpu_upload_walkers", "sqmc_gpu_num_walkers",
     "sqmc_gpu_download_walkers", "sqmc_gpu_step", "sqmc_gpu_run", "sqmc_gpu_annihilate", "sqmc_gpu_det_owner", "sqmc_gpu_set_owner_hash", "sqmc_gpu_shard_config",
-    "sqmc_gpu_shard_begin", "sqmc_gpu_shard_pack", "sqmc_gpu_shard_finish", "sqmc_gpu_comm_unique_id", "sqmc_gpu_comm_init", "sqmc_gpu_comm_size",
+    "sqmc_gpu_shard_begin", "sqmc_gpu_shard_pack", "sqmc_gpu_shard_finish", "sqmc_gpu_shard_finish_psit", "sqmc_gpu_comm_unique_id", "sqmc_gpu_comm_init", "sqmc_gpu_comm_size",
     "sqmc_gpu_shard_step", "sqmc_gpu_shard_run", "sqmc_gpu_shard_time_split", "sqmc_gpu_get_rng", "sqmc_gpu_set_rng", "sqmc_gpu_tail_stats", "sqmc_gpu_slowest_steps", "sqmc_gpu_set_chained_runs", "sqmc_gpu_spmv_prepare", "sqmc_gpu_davidson",
     "sqmc_gpu_spmv_apply", "sqmc_gpu_spmv_free", "sqmc_gpu_build_spmv_plan", "sqmc_gpu_spmv_sym_upper", "sqmc_gpu_hamiltonian_batch",
     "sqmc_gpu_propose_batch", "sqmc_gpu_hamiltonian_chem_batch", "sqmc_gpu_build_sparse_ham", "sqmc_gpu_hci_connections", "sqmc_gpu_hci_connections_slice", "sqmc_gpu_hci_pt2", "sqmc_gpu_hci_set_active_space", "sqmc_gpu_free", "sqmc_gpu_set_timing", "sqmc_gpu_get_timing",
 ]
+
+
+_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p)      # sqmc_allreduce_fn
 
 
 class SqmcGpuError(RuntimeError):
@@ -304,6 +307,38 @@ class GpuChem:
     def shard_finish(self, params, recv_ptr, n_recv):
         p = StepParams(**params); out = np.zeros(16)
         _chk(self.L.sqmc_gpu_shard_finish(self.h, C.byref(p), C.c_void_p(recv_ptr), int(n_recv), _p(out)))
+        return out
+
+    def set_hf_to_psit_shard(self, ct_index, diag_elems, psit_slot, psit_mask, cdet_psi_t, sum_order=1):
+        """hf_to_psit on a sharded walk: after shard_config, set_projector and set_ct_table (both global), before upload_walkers.
+        ct_index: 1-based positions of this rank's C(T) share in the C(T) list; psit_slot: 1-based slots of its Psi_T entries in that
+        share; psit_mask: their 1-based indices in Psi_T (label order); cdet_psi_t: all of Psi_T (psit_shard_tables in host.py)."""
+        ix, de = np.ascontiguousarray(ct_index, np.int64), _f64(diag_elems)
+        sl, mk, cd = np.ascontiguousarray(psit_slot, np.int64), np.ascontiguousarray(psit_mask, np.int64), _f64(cdet_psi_t)
+        self.L.sqmc_gpu_set_hf_to_psit_shard.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                         C.c_int64, C.c_void_p, C.c_int32]
+        _chk(self.L.sqmc_gpu_set_hf_to_psit_shard(self.h, len(ix), _p(ix) if len(ix) else None, _p(de) if len(de) else None, len(sl),
+                                                  _p(sl) if len(sl) else None, _p(mk) if len(mk) else None, len(cd), _p(cd), int(sum_order)))
+
+    def shard_finish_psit(self, params, recv_ptr, n_recv, buf_ptr, allreduce):
+        """shard_finish of a sharded hf_to_psit step without a communicator: allreduce() is called once, mid-way, after the library has
+        written the T^-1 partials (nranks + 1 doubles) to the device buffer at buf_ptr; it must leave their sum over ranks there."""
+        p = StepParams(**params); out = np.zeros(16)
+        err = []
+
+        def cb(buf, n, user):
+            try:
+                allreduce()
+                return 0
+            except Exception as e:          # reported after the library has returned
+                err.append(e)
+                return 1
+        fn = _ALLREDUCE_FN(cb)
+        self.L.sqmc_gpu_shard_finish_psit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, _ALLREDUCE_FN, C.c_void_p, C.c_void_p]
+        code = self.L.sqmc_gpu_shard_finish_psit(self.h, C.byref(p), C.c_void_p(recv_ptr), int(n_recv), C.c_void_p(buf_ptr), fn, None, _p(out))
+        if err:
+            raise err[0]
+        _chk(code)
         return out
 
     # ---- the same with the exchanges inside the library (RCCL)

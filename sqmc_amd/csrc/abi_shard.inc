@@ -3,6 +3,8 @@
 // image, the walker SoA types and the launch helpers defined there); not a standalone header.
 
 // ------------------------------------------------------------------ multi-rank sharding
+static int psit_shard_exchange(sqmc_gpu_ctx *c);                                                          // hf_to_psit over ranks (end of file)
+static int psit_shard_project(sqmc_gpu_ctx *c, const sqmc_step_params *sp, const double *x_global_dev);
 // owner of a determinant (the role of get_det_owner, mpi_routines.f90:419-445; any hash will
 // do for ownership, SURVEY.md section 5)
 __global__ void __launch_bounds__(TPB) k_owner_batch(ChemDev dev, const u64 *up, const u64 *dn, int *owner, long long n, int nranks, int mode) {
@@ -59,11 +61,13 @@ __global__ void __launch_bounds__(TPB) k_prj_finish_rows(const double *__restric
   y = y + e_trial * tau * xg[row]; wt[loc[i]] = wt[loc[i]] + y;
 }
 // destination rank of every child (nranks = "no walker": weight 0), as an 8-bit sort key
+// (koff: hf_to_psit's offset of the sort keys outside C(T), taken off again -- the owner is the determinant's)
 __global__ void __launch_bounds__(TPB) k_child_owner(WalkArr w, const u64 *__restrict__ keys, u64 *__restrict__ okey, u32 *__restrict__ oval,
-                                                     long long n0, long long nch, u64 invalid_key, int nranks, int pack, int mode) {
+                                                     long long n0, long long nch, u64 invalid_key, int nranks, int pack, int mode, u64 koff) {
   long long c = (long long)blockIdx.x * TPB + threadIdx.x;
   if (c >= nch) return;
-  const u64 k = get_key(keys, n0 + c, pack);
+  u64 k = get_key(keys, n0 + c, pack);
+  if (koff && k != invalid_key && k >= koff) k -= koff;
   u64 o = (u64)nranks;
   if (k != invalid_key) { if (mode == SQMC_OWNER_DJB) { const SpawnRec r = w.sp[c]; o = (u64)det_owner_djb(r.up, r.dn, nranks); } else o = (u64)det_owner(k, nranks); }
   okey[c] = o; oval[c] = (u32)c;
@@ -93,7 +97,9 @@ __global__ void __launch_bounds__(TPB) k_unpack_recv(ChemDev dev, WalkArr w, con
   const u64 u = src[0], d = src[1];
   SpawnRec r; r.up = u; r.dn = d; r.wt = __longlong_as_double((long long)src[2]); r.flg = src[3] & 0xFFFFFFFFull;
   w.sp[q] = r;
-  put_key(keys, vals, k, det_key(dev, u, d), pack);
+  u64 key = det_key(dev, u, d);
+  if (dev.ps.koff) key = psit_key(dev.ps, key);      // hf_to_psit: a determinant of this rank's C(T) share sorts into its segment
+  put_key(keys, vals, k, key, pack);
 }
 
 int sqmc_gpu_det_owner(sqmc_gpu_ctx *c, int64_t n, const uint64_t *up, const uint64_t *dn, int32_t nranks, int32_t *owner) {
@@ -114,6 +120,9 @@ int sqmc_gpu_set_owner_hash(sqmc_gpu_ctx *c, int32_t mode) {
   c->owner_mode = mode;
   return SQMC_OK;
 }
+
+// hf_to_psit over ranks: the 2P slots of row partials behind x_global (0 for every other walk)
+static long long psit_x_extra(const sqmc_gpu_ctx *c) { return c->psit_shard ? 2ll * c->shard_n : 0ll; }
 
 int sqmc_gpu_shard_config(sqmc_gpu_ctx *c, int32_t rank, int32_t nranks, int64_t n_imp_local, const int32_t *global_row) {
   if (!c || nranks < 1 || nranks > 255 || rank < 0 || rank >= nranks || n_imp_local < 0) return fail(SQMC_ERR_BAD_ARG, "bad argument");
@@ -152,7 +161,13 @@ static int shard_begin_impl(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double 
   StepP p; p.tau = sp->tau; p.e_trial = sp->e_trial; p.rfi = sp->reweight_factor_inv; p.r_init = sp->r_initiator; p.min_wt = sp->min_wt;
   p.cutoff = sp->always_spawn_cutoff_wt; p.ipow = sp->initiator_power; p.imind = sp->initiator_min_distance; p.cti = sp->c_t_initiator;
   p.semi = sp->semistochastic; p.reached = sp->reached_w_abs_gen;
+  if (c->psit_on) {
+    if (!sp->semistochastic) return fail(SQMC_ERR_BAD_ARG, "hf_to_psit needs a semistochastic step");
+    p.koff = c->dev.ps.koff; p.nct = c->dev.ps.n_ct;
+    if (c->nwalk < p.nct) return fail(SQMC_ERR_BAD_ARG, "hf_to_psit: the walker list does not hold this rank's C(T) share");
+  }
   const long long n0 = c->nwalk, M = c->mwalk;
+  const long long nx = c->n_imp + psit_x_extra(c);        // hf_to_psit: 2P slots of row partials behind the weights
   ScanWork sw0; sw0.state = c->d_scan_state; sw0.ticket = c->d_scan_ticket; sw0.cap_tiles = c->cap_tiles; sw0.self_clear = false;
   collect_timers(c);
   c->nt = 0;
@@ -166,7 +181,7 @@ static int shard_begin_impl(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double 
   const bool x_ready = c->shard_x_ready && x_global_dev == c->d_xg;
   const bool y_ok = x_ready && c->head_ready && c->shard_y_ok;
   c->shard_x_ready = false;
-  if (!side && !x_ready && x_global_dev && c->n_imp > 0) HIPCHK(hipMemsetAsync(x_global_dev, 0, c->n_imp * 8, st));
+  if (!side && !x_ready && x_global_dev && c->n_imp > 0) HIPCHK(hipMemsetAsync(x_global_dev, 0, nx * 8, st));
   const bool mail = (n0 > 0 && M > n0);
   u64 cseq;
   if (c->head_ready) {
@@ -225,6 +240,11 @@ static int shard_begin_impl(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double 
     }
     if (c->n_imp_local > 0 && !x_ready)
       hipLaunchKernelGGL(k_prj_gather_rows, dim3(nblk(c->n_imp_local)), dim3(TPB), 0, sx, c->w.wt, c->d_loc_imp, c->d_grow, x_global_dev, c->n_imp_local);
+    if (c->psit_shard && x_global_dev) {       // do_walk.f90:2285-2286 over ranks: this rank's partials of the first row, reduced with the weights
+      const PsitArgs &a = c->psit;
+      if (!a.seq && a.n_ct > 0) hipLaunchKernelGGL(k_psit_ct_terms, dim3((unsigned)((a.n_ct + 4095) / 4096)), dim3(64), 0, sx, a, (const double *)c->w.wt);
+      hipLaunchKernelGGL(k_psit_row_parts, dim3(1), dim3(128), 0, sx, a, (const double *)c->w.wt, x_global_dev + c->n_imp, p.tau, p.e_trial);
+    }
   }
   c->shard_y_used = y_ok; c->shard_x_used = x_ready;
   HIPCHK(hipGetLastError());
@@ -257,7 +277,8 @@ int sqmc_gpu_shard_begin(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double *x_
 static int shard_bucket(sqmc_gpu_ctx *c, const sqmc_step_params *sp, const double *x_global_dev, u32 **order, bool apply_rows = true) {
   hipStream_t st = c->st;
   const long long n0 = c->shard_n0, nch = c->shard_nch; const int P = c->shard_n;
-  if (apply_rows && c->n_imp_local > 0 && c->shard_y_used)
+  if (apply_rows && c->psit_shard) { int r = psit_shard_project(c, sp, x_global_dev); if (r) return r; }
+  else if (apply_rows && c->n_imp_local > 0 && c->shard_y_used)
     hipLaunchKernelGGL(k_prj_finish_rows, dim3(nblk(c->n_imp_local)), dim3(TPB), 0, st, (const double *)c->d_prj_y, x_global_dev, c->d_loc_imp, c->d_grow, c->w.wt, c->n_imp_local, sp->e_trial, sp->tau);
   else if (apply_rows && c->n_imp_local > 0)
     hipLaunchKernelGGL(k_prj_apply_rows, dim3(nblk(c->n_imp_local, TPB / 64)), dim3(TPB), 0, st, c->d_prj_ptr, c->d_prj_col, c->d_prj_val, x_global_dev,
@@ -265,7 +286,7 @@ static int shard_bucket(sqmc_gpu_ctx *c, const sqmc_step_params *sp, const doubl
   *order = nullptr;
   if (nch > 0) {
     u64 *okey = c->d_flags, *okey_alt = c->d_pos; u32 *oval = (u32 *)c->d_flags2, *oval_alt = (u32 *)c->d_pos2;
-    if (!c->owner_ready) hipLaunchKernelGGL(k_child_owner, dim3(nblk(nch)), dim3(TPB), 0, st, c->w, c->d_keys, okey, oval, n0, nch, c->invalid_key, P, c->pack, c->owner_mode);
+    if (!c->owner_ready) hipLaunchKernelGGL(k_child_owner, dim3(nblk(nch)), dim3(TPB), 0, st, c->w, c->d_keys, okey, oval, n0, nch, c->invalid_key, P, c->pack, c->owner_mode, c->dev.ps.koff);
     SortWork so; so.k_alt = okey_alt; so.v_alt = oval_alt; so.hist = c->d_hist; so.rowtot = c->d_rowtot; so.cap = c->mwalk;
     u64 *sk = okey; u32 *sv = oval;
     device_radix_sort(sk, sv, nch, 8, so, st, 0, true);      // one stable 8-bit pass (also for a single child); rowtot[d] = children per destination
@@ -306,6 +327,7 @@ static int shard_finish_impl(sqmc_gpu_ctx *c, const sqmc_step_params *sp, const 
   StepP p; p.tau = sp->tau; p.e_trial = sp->e_trial; p.rfi = sp->reweight_factor_inv; p.r_init = sp->r_initiator; p.min_wt = sp->min_wt;
   p.cutoff = sp->always_spawn_cutoff_wt; p.ipow = sp->initiator_power; p.imind = sp->initiator_min_distance; p.cti = sp->c_t_initiator;
   p.semi = sp->semistochastic; p.reached = sp->reached_w_abs_gen;
+  if (c->psit_on) { p.koff = c->dev.ps.koff; p.nct = c->dev.ps.n_ct; }
   const long long n0 = c->shard_n0;
   if (n0 + n_recv > c->mwalk) {
     hipMemset(c->d_scan_state, 0, 3 * c->cap_tiles * 8); hipMemset(c->d_scan_ticket, 0, 3 * 4);
@@ -317,6 +339,10 @@ static int shard_finish_impl(sqmc_gpu_ctx *c, const sqmc_step_params *sp, const 
     if (join) HIPCHK(hipStreamWaitEvent(st, c->e_join, 0));
     for (int i = 0; i < 16; i++) out[i] = 0.0;
     hipMemset(c->d_scan_state, 0, 3 * c->cap_tiles * 8); hipMemset(c->d_scan_ticket, 0, 3 * 4);
+    if (c->psit_shard) {            // still a party to the exchange of the T^-1 partials: nothing to add
+      HIPCHK(hipMemsetAsync(c->d_ps_tx, 0, (c->shard_n + 1) * 8, st));
+      int rx = psit_shard_exchange(c); if (rx) return rx;
+    }
     c->step_no++;
     if (c->comm) {                  // still a party to the all-reduce of the sums
       HIPCHK(hipMemsetAsync(c->d_sc->stats, 0, 16 * 8 + 8 * 8 + 8 * 8, st));       // stats, red and this rank's share of it: nothing to add, no status
@@ -351,7 +377,18 @@ static int shard_finish_impl(sqmc_gpu_ctx *c, const sqmc_step_params *sp, const 
   return r;
 }
 int sqmc_gpu_shard_finish(sqmc_gpu_ctx *c, const sqmc_step_params *sp, const uint64_t *recv_dev, int64_t n_recv, double out[16]) {
+  if (c && c->psit_shard && !c->comm) return fail(SQMC_ERR_BAD_ARG, "sharded hf_to_psit without a communicator: finish the step with sqmc_gpu_shard_finish_psit");
   return shard_finish_impl(c, sp, recv_dev, n_recv, out, false);
+}
+int sqmc_gpu_shard_finish_psit(sqmc_gpu_ctx *c, const sqmc_step_params *sp, const uint64_t *recv_dev, int64_t n_recv, double *reduce_buf_dev,
+                               sqmc_allreduce_fn allreduce, void *user, double out[16]) {
+  if (!c || !reduce_buf_dev || !allreduce) return fail(SQMC_ERR_BAD_ARG, "null argument");
+  if (!c->psit_shard) return fail(SQMC_ERR_BAD_ARG, "not a sharded hf_to_psit context (sqmc_gpu_set_hf_to_psit_shard)");
+  if (c->comm) return fail(SQMC_ERR_BAD_ARG, "a communicator is attached: the library exchanges the T^-1 partials itself (sqmc_gpu_shard_finish)");
+  c->psit_reduce = allreduce; c->psit_reduce_user = user; c->psit_reduce_buf = reduce_buf_dev;
+  const int r = shard_finish_impl(c, sp, recv_dev, n_recv, out, false);
+  c->psit_reduce = nullptr; c->psit_reduce_user = nullptr; c->psit_reduce_buf = nullptr;
+  return r;
 }
 
 
@@ -443,7 +480,7 @@ int sqmc_gpu_comm_init(sqmc_gpu_ctx *c, const uint8_t id[SQMC_COMM_ID_BYTES]) {
   NCCLCHK(g_rccl.CommInitRank(&c->comm, c->shard_n, u, c->shard_rank));
   const int P = c->shard_n;
   c->xch_cap = c->mwalk;             // a rank can neither spawn nor hold more than MWALK walkers
-  HIPCHK(hipMalloc(&c->d_xg, (c->n_imp + 9) * 8));      // + the eight sums that ride behind the weights in a pipelined run
+  HIPCHK(hipMalloc(&c->d_xg, (c->n_imp + 9 + 2 * P) * 8));      // + the eight sums that ride behind the weights in a pipelined run; hf_to_psit: 2P row partials
   HIPCHK(hipMalloc(&c->d_send, c->xch_cap * 32)); HIPCHK(hipMalloc(&c->d_recv, c->xch_cap * 32));
   // every rank contributes P send counts + its status + the room behind its walkers (SHARD_ROW words)
   HIPCHK(hipMalloc(&c->d_cnt_mine, SHARD_ROW(P) * 4)); HIPCHK(hipMalloc(&c->d_cnt_all, (size_t)P * SHARD_ROW(P) * 4));
@@ -512,9 +549,9 @@ static int shard_step_impl(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double o
   hipStream_t st = c->st;
   const int P = c->shard_n, me = c->shard_rank, ROW = SHARD_ROW(P);
   int64_t nch = 0;
-  const bool side = (c->comm2 != nullptr);
+  const bool side = (c->comm2 != nullptr) && !c->psit_shard;      // hf_to_psit: one stream (its row partials ride with the weights)
   static const bool diag_side_env = !(getenv("SQMC_SHARD_DIAG_SIDE") && getenv("SQMC_SHARD_DIAG_SIDE")[0] == '0');
-  const bool diag_side = !side && diag_side_env && c->st2 != c->st;
+  const bool diag_side = !side && diag_side_env && c->st2 != c->st && !c->psit_shard;
   int local = shard_begin_impl(c, sp, c->d_xg, &nch, false, side, diag_side);
   if (local < 0) return local;                     // argument / HIP failures are not walk statuses: nothing collective can be said about them
   const std::string local_msg = local ? g_err : std::string();
@@ -522,7 +559,7 @@ static int shard_step_impl(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double o
   t_us[1] = now_us();
   {   // deterministic projection: all-reduce of the weights, then the rows this rank owns
     hipStream_t sx = side ? c->st2 : st;
-    if (c->n_imp > 0 && !c->shard_x_used) NCCLCHK(g_rccl.AllReduce(c->d_xg, c->d_xg, (size_t)c->n_imp, ncclDouble, ncclSum, side ? c->comm2 : c->comm, sx));
+    if (c->n_imp > 0 && !c->shard_x_used) NCCLCHK(g_rccl.AllReduce(c->d_xg, c->d_xg, (size_t)(c->n_imp + psit_x_extra(c)), ncclDouble, ncclSum, side ? c->comm2 : c->comm, sx));
     if (side) {
       if (c->n_imp_local > 0 && !local)
         hipLaunchKernelGGL(k_prj_apply_rows, dim3(nblk(c->n_imp_local, TPB / 64)), dim3(TPB), 0, sx, c->d_prj_ptr, c->d_prj_col, c->d_prj_val, c->d_xg,
@@ -585,4 +622,112 @@ static int shard_step_impl(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double o
 
 int sqmc_gpu_shard_run(sqmc_gpu_ctx *c, sqmc_popctl *pc, int64_t nsteps, double *stats, double totals[16]) {
   return run_steps(c, pc, nsteps, stats, totals, sqmc_gpu_shard_step);
+}
+
+// ------------------------------------------------------------------ hf_to_psit over ranks
+// do_walk.f90:1808-1886 (set-up), 2272-2288 and 2304-2320 (before the merge), 2394-2442 (T^-1 after it), 2444-2462 and 2701-2722 (the
+// C(T) loops over the local share).  psit_kernels.h has the device side; DESIGN.md section 4b the exchanges and the sum order.
+int sqmc_gpu_set_hf_to_psit_shard(sqmc_gpu_ctx *c, int64_t n_ct_local, const int64_t *ct_index, const double *diag_elems, int64_t n_psit_local,
+                                  const int64_t *psit_slot, const int64_t *psit_mask, int64_t n_psit, const double *cdet_psi_t, int32_t sum_order) {
+  abandon_head(c);
+  if (!c || n_ct_local < 0 || n_psit_local < 0 || n_psit < 1 || !cdet_psi_t || (n_ct_local > 0 && (!ct_index || !diag_elems)) ||
+      (n_psit_local > 0 && (!psit_slot || !psit_mask))) return fail(SQMC_ERR_BAD_ARG, "bad argument");
+  if (c->mwalk <= 0) return fail(SQMC_ERR_BAD_ARG, "context has no walker arrays (mwalk=0)");
+  if (c->shard_n < 1 || !c->d_grow) return fail(SQMC_ERR_BAD_ARG, "call sqmc_gpu_shard_config before sqmc_gpu_set_hf_to_psit_shard");
+  if (c->dev.hb.on) return fail(SQMC_ERR_UNSUPPORTED, "hf_to_psit with proposal_method fast_heatbath is not built");
+  if (c->htab.sys_type == 2) return fail(SQMC_ERR_UNSUPPORTED, "hf_to_psit is not built for the Hubbard model");
+  if (!c->d_ct_up || c->n_ct < 1) return fail(SQMC_ERR_BAD_ARG, "set the (global) C(T) table first");
+  if (!c->d_prj_ptr || c->n_imp < 1) return fail(SQMC_ERR_BAD_ARG, "set the (global) deterministic-space matrix first");
+  if (sum_order != 0 && sum_order != 1) return fail(SQMC_ERR_BAD_ARG, "sum_order must be 0 (left to right) or 1 (64-ary tree)");
+  if (n_psit - 1 > PSIT_MAXTERMS || n_ct_local > PSIT_MAXTERMS) return fail(SQMC_ERR_UNSUPPORTED, "trial wave function or C(T) share longer than 64^3 determinants: the tree sums have three levels");
+  if (n_ct_local > c->n_ct || n_psit_local > n_psit) return fail(SQMC_ERR_BAD_ARG, "a share is longer than the global table");
+  if (cdet_psi_t[0] == 0.0) return fail(SQMC_ERR_BAD_ARG, "cdet_psi_t(1) = 0");
+  for (long long i = 0; i < n_ct_local; i++)
+    if (ct_index[i] < 1 || ct_index[i] > c->n_ct || (i && ct_index[i] <= ct_index[i - 1])) return fail(SQMC_ERR_BAD_ARG, "ct_index must be increasing 1-based positions in the C(T) list");
+  std::vector<int> loc(n_psit_local + 1), of(n_ct_local + 1, -1);
+  for (long long k = 0; k < n_psit_local; k++) {
+    const long long q = psit_slot[k] - 1;
+    if (q < 0 || q >= n_ct_local || (k && q <= loc[k - 1])) return fail(SQMC_ERR_BAD_ARG, "psit_slot must be increasing 1-based positions in this rank's C(T) share");
+    if (psit_mask[k] < 1 || psit_mask[k] > n_psit || (k && psit_mask[k] <= psit_mask[k - 1])) return fail(SQMC_ERR_BAD_ARG, "psit_mask must be increasing 1-based indices of Psi_T (label order)");
+    loc[k] = (int)q; of[q] = (int)k;
+  }
+  // iown_first = iown_psit1: the first state is C(T)'s and Psi_T's first determinant (host.psit_tables), at the head of its owner's share
+  const bool own_first = n_ct_local > 0 && ct_index[0] == 1;
+  if (own_first != (n_psit_local > 0 && psit_mask[0] == 1) || (own_first && loc[0] != 0))
+    return fail(SQMC_ERR_UNSUPPORTED, "hf_to_psit: the first determinant of Psi_T must be the first determinant of C(T), at slot 1 of its owner's share");
+  u64 total = 0;
+  { auto choose = [&](int n_, int k_) -> long double { long double r = 1; for (int q = 1; q <= k_; q++) r = r * (n_ - k_ + q) / q; return r; };
+    total = (u64)(choose(c->htab.norb, c->htab.nup) * choose(c->htab.norb, c->htab.ndn) + 0.5L); }
+  if (!c->base_key_bits) c->base_key_bits = c->key_bits;
+  if (c->base_key_bits + 1 > 62) return fail(SQMC_ERR_UNSUPPORTED, "determinant space too large for the hf_to_psit sort key");
+  psit_off(c);
+  // this rank's rows of the global C(T) table: determinants (the upload checks them), e_loc_num / den
+  const long long n_ct = c->n_ct, P = c->shard_n;
+  std::vector<u64> gu(n_ct), gd(n_ct); std::vector<double> gn(n_ct), gdn(n_ct);
+  HIPCHK(hipMemcpy(gu.data(), c->d_ct_up, n_ct * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(gd.data(), c->d_ct_dn, n_ct * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(gn.data(), c->d_ct_num, n_ct * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(gdn.data(), c->d_ct_den, n_ct * 8, hipMemcpyDeviceToHost));
+  c->ps_ct_up.assign(n_ct_local, 0); c->ps_ct_dn.assign(n_ct_local, 0);
+  std::vector<double> num(n_ct_local + 1, 0.0), den(n_ct_local + 1, 0.0), cl(n_psit_local + 1, 0.0);
+  for (long long i = 0; i < n_ct_local; i++) { const long long g = ct_index[i] - 1; c->ps_ct_up[i] = gu[g]; c->ps_ct_dn[i] = gd[g]; num[i] = gn[g]; den[i] = gdn[g]; }
+  for (long long k = 0; k < n_psit_local; k++) cl[k] = cdet_psi_t[psit_mask[k] - 1];
+  hipFree(c->d_ps_loc); hipFree(c->d_ps_of); hipFree(c->d_ps_impof); hipFree(c->d_ps_c); hipFree(c->d_ps_diag); hipFree(c->d_ps_dwct); hipFree(c->d_ps_dwps);
+  hipFree(c->d_ps_dwimp); hipFree(c->d_ps_p2); hipFree(c->d_ps_part); hipFree(c->d_ps_raw); hipFree(c->d_ps_num); hipFree(c->d_ps_den); hipFree(c->d_ps_tx);
+  c->d_ps_loc = c->d_ps_of = c->d_ps_impof = nullptr; c->d_ps_c = c->d_ps_diag = c->d_ps_dwct = c->d_ps_dwps = c->d_ps_dwimp = c->d_ps_p2 = c->d_ps_part = c->d_ps_raw = nullptr;
+  c->d_ps_num = c->d_ps_den = c->d_ps_tx = nullptr;
+  const long long nc1 = n_ct_local + 1, np1 = n_psit_local + 1;      // (+1: no zero-length allocation for an empty share)
+  HIPCHK(hipMalloc(&c->d_ps_raw, np1 * 8)); HIPCHK(hipMalloc(&c->d_ps_loc, np1 * 4)); HIPCHK(hipMalloc(&c->d_ps_of, nc1 * 4)); HIPCHK(hipMalloc(&c->d_ps_impof, nc1 * 4));
+  HIPCHK(hipMalloc(&c->d_ps_c, np1 * 8)); HIPCHK(hipMalloc(&c->d_ps_diag, nc1 * 8)); HIPCHK(hipMalloc(&c->d_ps_dwct, nc1 * 8)); HIPCHK(hipMalloc(&c->d_ps_dwps, np1 * 8));
+  HIPCHK(hipMalloc(&c->d_ps_dwimp, (c->n_imp + 1) * 8)); HIPCHK(hipMalloc(&c->d_ps_p2, ((n_ct_local + 4095) / 4096 + 1) * 8)); HIPCHK(hipMalloc(&c->d_ps_part, (size_t)PSIT_FB * NSTAT * 8));
+  HIPCHK(hipMalloc(&c->d_ps_num, nc1 * 8)); HIPCHK(hipMalloc(&c->d_ps_den, nc1 * 8)); HIPCHK(hipMalloc(&c->d_ps_tx, (P + 1) * 8));
+  HIPCHK(hipMemcpy(c->d_ps_loc, loc.data(), np1 * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(c->d_ps_of, of.data(), nc1 * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(c->d_ps_impof, 0xFF, nc1 * 4));               // filled by the upload
+  HIPCHK(hipMemcpy(c->d_ps_c, cl.data(), np1 * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(c->d_ps_diag, 0, nc1 * 8)); if (n_ct_local > 0) HIPCHK(hipMemcpy(c->d_ps_diag, diag_elems, n_ct_local * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(c->d_ps_num, num.data(), nc1 * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(c->d_ps_den, den.data(), nc1 * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(c->d_ps_tx, 0, (P + 1) * 8));
+  PsitArgs &a = c->psit; memset(&a, 0, sizeof(a));
+  a.n_ct = n_ct_local; a.n_psit = n_psit_local; a.n_imp = c->n_imp; a.loc_psit = c->d_ps_loc; a.cdet = c->d_ps_c; a.diag = c->d_ps_diag; a.psit_of = c->d_ps_of;
+  a.imp_of = c->d_ps_impof; a.cnum = c->d_ps_num; a.cden = c->d_ps_den; a.dw_ct = c->d_ps_dwct; a.dw_ps = c->d_ps_dwps; a.dw_imp = c->d_ps_dwimp; a.p2 = c->d_ps_p2;
+  a.n_perm = 0; a.seq = sum_order == 0 ? 1 : 0;
+  a.own_first = own_first ? 1 : 0; a.c1 = cdet_psi_t[0]; a.tx = c->d_ps_tx; a.shard_P = (int)P; a.shard_me = c->shard_rank;
+  c->dev.ps.koff = total; c->dev.ps.hkey = c->d_ct_hkey; c->dev.ps.hmask = c->ct_mask; c->dev.ps.first_up = gu[0]; c->dev.ps.first_dn = gd[0];
+  c->dev.ps.n_ct = n_ct_local; c->dev.ps.own_first = a.own_first;
+  c->key_bits = c->base_key_bits + 1; c->invalid_key = (1ull << c->key_bits) - 1ull;
+  c->pack = (c->key_bits <= 32 && !getenv("SQMC_FORCE_UNPACKED")) ? 1 : 0;
+  c->psit_on = true; c->psit_shard = true; c->nwalk = 0;           // walkers are uploaded anew: this rank's share of C(T) first
+  return SQMC_OK;
+}
+
+// before the merge, behind the all-reduce of x_global: the deterministic-space rows this rank owns (no E_T term), the first column over its
+// share with w_1 = x_global(1), the first rows on the owner (partials of all ranks in rank order), then the update slot by slot (2304-2320)
+static int psit_shard_project(sqmc_gpu_ctx *c, const sqmc_step_params *sp, const double *xg) {
+  hipStream_t st = c->st;
+  const PsitArgs &a = c->psit;
+  if (c->n_imp_local > 0) {
+    PrjPre pp; memset(&pp, 0, sizeof(pp));
+    pp.n_imp = (int)c->n_imp_local; pp.ptr = c->d_prj_ptr; pp.col = c->d_prj_col; pp.val = c->d_prj_val; pp.x = xg; pp.y = a.dw_imp; pp.grow = c->d_grow;
+    hipLaunchKernelGGL(k_psit_imp_rows, dim3(nblk(c->n_imp_local, TPB / 64)), dim3(TPB), 0, st, pp);
+  }
+  if (a.n_ct > 0) hipLaunchKernelGGL(k_psit_ct_col, dim3(nblk(a.n_ct)), dim3(TPB), 0, st, a, (const double *)c->w.wt, xg);
+  hipLaunchKernelGGL(k_psit_rows_fin_shard, dim3(1), dim3(TPB), 0, st, a, xg, sp->tau, sp->e_trial);
+  if (a.n_ct > 0) hipLaunchKernelGGL(k_psit_apply, dim3(nblk(a.n_ct)), dim3(TPB), 0, st, a, c->w.wt, sp->tau, sp->e_trial);
+  HIPCHK(hipGetLastError());
+  return SQMC_OK;
+}
+// the P + 1 doubles of the T^-1 exchange, summed over ranks in place: RCCL with a communicator, else the caller's all-reduce
+static int psit_shard_exchange(sqmc_gpu_ctx *c) {
+  hipStream_t st = c->st;
+  const size_t n = (size_t)c->shard_n + 1;
+  if (c->comm) { NCCLCHK(g_rccl.AllReduce(c->d_ps_tx, c->d_ps_tx, n, ncclDouble, ncclSum, c->comm, st)); return SQMC_OK; }
+  if (!c->psit_reduce) return fail(SQMC_ERR_BAD_ARG, "sharded hf_to_psit without a communicator: finish the step with sqmc_gpu_shard_finish_psit");
+  HIPCHK(hipMemcpyAsync(c->psit_reduce_buf, c->d_ps_tx, n * 8, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (c->psit_reduce(c->psit_reduce_buf, (int64_t)n, c->psit_reduce_user) != 0) return fail(SQMC_ERR_BAD_ARG, "the caller's all-reduce of the T^-1 partials failed");
+  HIPCHK(hipMemcpyAsync(c->d_ps_tx, c->psit_reduce_buf, n * 8, hipMemcpyDeviceToDevice, st));
+  return SQMC_OK;
+}
+static int psit_shard_tinv(sqmc_gpu_ctx *c, const double *ps_raw) {
+  hipLaunchKernelGGL(k_psit_tinv_part, dim3(1), dim3(64), 0, c->st, c->psit, ps_raw, c->d_ps_tx);
+  HIPCHK(hipGetLastError());
+  return psit_shard_exchange(c);
 }

@@ -62,7 +62,8 @@ struct PsitDev {
   u64 koff;                             // 0: off
   const u64 *hkey; u64 hmask;           // C(T) membership: the open-addressed hash of sqmc_gpu_set_ct_table on the determinant's rank
   u64 first_up, first_dn;               // dets_up/dn_psi_t(1) = the first state: no stochastic move from it (3574) or onto it (3676, 7642)
-  long long n_ct;
+  long long n_ct;                       // length of the C(T) segment (sharded: this rank's share)
+  int own_first;                        // slot 0 is the first state (sharded: on its owner only)
 };
 struct ChemDev {                        // pointers into HBM, passed by value
   const ChemTab *tab; int tab_words;

@@ -24,6 +24,12 @@
 // a fixed order any implementation can reproduce bit for bit (the tests' CPU restatement does), rounding-level different from the reference.
 //
 // All HBM/latency bound; n_ct = 7.7e4 for C2 cc-pVDZ with a 100-determinant Psi_T: every kernel here is a few microseconds.
+//
+// Sharded over ranks (do_walk.f90:1808-1886, 2272-2288, 2304-2320, 2394-2442; sqmc_gpu_set_hf_to_psit_shard): the tables are this rank's
+// share -- its C(T) determinants in C(T) order at the head of its list, its Psi_T entries -- and the first state sits at slot 0 of its
+// owner only (own_first).  What needs all of C(T) / Psi_T becomes per-rank partials that travel in P slots each behind the
+// deterministic-space weights (before the merge: k_psit_row_parts, k_psit_rows_fin_shard) or in a vector of P + 1 (T^-1 after the
+// merge: k_psit_tinv_part); every rank adds the P partials in rank order, so one rank is the one-rank step bit for bit.
 
 // (struct PsitArgs: sqmc_gpu.hip, in front of the context that keeps one)
 #define PSIT_MAXTERMS (64ll * 64 * 64)      // three tree levels
@@ -80,13 +86,14 @@ __device__ __forceinline__ double wave_tree_sum(F term, long long n, double (*s_
 
 // term i of the first row over C(T), more_tools.f90:3657-3660: E_num(1)/E_den(1) w_1, then E_num(i) w_i
 __device__ __forceinline__ double psit_ct_term(const PsitArgs &a, const double *__restrict__ wt, long long i) {
-  return i == 0 ? a.cnum[0] / a.cden[0] * wt[0] : a.cnum[i] * wt[i];
+  return (i == 0 && a.own_first) ? a.cnum[0] / a.cden[0] * wt[0] : a.cnum[i] * wt[i];
 }
-// deltaw of the C(T) slots (first column + extra diagonal of the transformed projector), elementwise
-__global__ void __launch_bounds__(TPB) k_psit_ct_col(PsitArgs a, const double *__restrict__ wt) {
+// deltaw of the C(T) slots (first column + extra diagonal of the transformed projector), elementwise; w1p[0]: the first state's weight
+// (one rank: its slot; sharded: global row 0 of the all-reduced deterministic-space weights)
+__global__ void __launch_bounds__(TPB) k_psit_ct_col(PsitArgs a, const double *__restrict__ wt, const double *__restrict__ w1p) {
   const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
-  if (i >= a.n_ct || i == 0) return;
-  double d = 0.0 + a.cnum[i] * wt[0]; d = d + a.diag[i] * wt[i];
+  if (i >= a.n_ct || (i == 0 && a.own_first)) return;
+  double d = 0.0 + a.cnum[i] * w1p[0]; d = d + a.diag[i] * wt[i];
   a.dw_ct[i] = d;
 }
 // One wavefront per 4096 slots of C(T): two tree levels of the first row's sum.
@@ -115,6 +122,47 @@ __global__ void __launch_bounds__(TPB) k_psit_rows_fin(PsitArgs a, const double 
   const double v1 = wt[a.loc_psit[0]];
   for (long long k = 1 + threadIdx.x; k < a.n_psit; k += TPB) a.dw_ps[k] = 0.0 + (one_plus * a.cdet[k]) * v1;
 }
+// Sharded, in front of the all-reduce of the deterministic-space weights: this rank's partials of the first row over its C(T) share
+// (wave 0; level 3 over k_psit_ct_terms's blocks, or left to right) and over its Psi_T entries other than the first state (wave 1),
+// into slots xs[me] and xs[P + me] -- the caller zeroed all 2P, so the all-reduce of each slot adds one non-zero term and is exact
+__global__ void __launch_bounds__(128) k_psit_row_parts(PsitArgs a, const double *__restrict__ wt, double *__restrict__ xs, double tau, double e_trial) {
+  __shared__ double s_scr[2][64][65];
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const double one_plus = 1.0 + tau * e_trial;
+  const int f = a.own_first ? 1 : 0;
+  double tot = 0.0;
+  if (wv == 0) {
+    if (a.seq) tot = wave_tree_sum([&](long long i) { return psit_ct_term(a, wt, i); }, a.n_ct, s_scr[0], 1);
+    else if (lane == 0) { const long long nb = (a.n_ct + 4095) / 4096; if (nb > 0) { tot = a.p2[0]; for (long long b = 1; b < nb; b++) tot = tot + a.p2[b]; } }
+    if (lane == 0) xs[a.shard_me] = tot;
+  } else {
+    tot = wave_tree_sum([&](long long i) { return (one_plus * a.cdet[i + f]) * wt[a.loc_psit[i + f]]; }, a.n_psit - f, s_scr[1], a.seq);
+    if (lane == 0) xs[a.shard_P + a.shard_me] = tot;
+  }
+}
+// Sharded, behind the all-reduce: the owner of the first state adds the P partials of each row in rank order; every rank makes the first
+// column over its Psi_T entries with w_1 = x_global(1)
+__global__ void __launch_bounds__(TPB) k_psit_rows_fin_shard(PsitArgs a, const double *__restrict__ xg, double tau, double e_trial) {
+  const double one_plus = 1.0 + tau * e_trial;
+  const double *xs = xg + a.n_imp;
+  const int P = a.shard_P;
+  if (a.own_first && threadIdx.x == 0) {
+    double t = xs[0]; for (int q = 1; q < P; q++) t = t + xs[q];
+    a.dw_ct[0] = 0.0 + t;
+    double u = xs[P]; for (int q = 1; q < P; q++) u = u + xs[P + q];
+    a.dw_ps[0] = 0.0 + u;
+  }
+  const double v1 = xg[0];
+  for (long long k = (a.own_first ? 1 : 0) + threadIdx.x; k < a.n_psit; k += TPB) a.dw_ps[k] = 0.0 + (one_plus * a.cdet[k]) * v1;
+}
+// Sharded, between the merge and k_psit_finish: this rank's partial of T^-1's sum, sum_k c_k w_k over its Psi_T entries other than the
+// first state, into tx[me]; the owner's merged weight of the first state into tx[P]; zeros elsewhere (P + 1 doubles, then all-reduced)
+__global__ void __launch_bounds__(64) k_psit_tinv_part(PsitArgs a, const double *__restrict__ ps_raw, double *__restrict__ tx) {
+  __shared__ double s_scr[64][65];
+  const int f = a.own_first ? 1 : 0;
+  const double t = wave_tree_sum([&](long long i) { return a.cdet[i + f] * ps_raw[i + f]; }, a.n_psit - f, s_scr, a.seq);
+  for (int q = threadIdx.x; q <= a.shard_P; q += 64) tx[q] = q == a.shard_me ? t : ((q == a.shard_P && f) ? ps_raw[0] : 0.0);
+}
 // do_walk.f90:2313-2323, slot by slot in the reference's order: the C(T) line, then the Psi_T row, then the deterministic-space product
 __global__ void __launch_bounds__(TPB) k_psit_apply(PsitArgs a, double *__restrict__ wt, double tau, double e_trial) {
   const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
@@ -141,7 +189,13 @@ __global__ void __launch_bounds__(TPB) k_psit_finish(PsitArgs a, double *__restr
   // are being overwritten by other blocks.  One kernel less on the step's critical path.
   __shared__ double s_scr[64][65];
   __shared__ double s_w1;
-  if (threadIdx.x < 64) {
+  if (a.tx) {                                            // sharded: the P partials (rank order) and the owner's weight, all-reduced
+    if (threadIdx.x == 0) {
+      double tmp = a.tx[0]; for (int q = 1; q < a.shard_P; q++) tmp = tmp + a.tx[q];
+      tmp = 0.0 + tmp;
+      double w1 = a.tx[a.shard_P]; w1 = w1 - tmp; w1 = w1 / a.c1; w1 = w1 / a.c1; s_w1 = w1;
+    }
+  } else if (threadIdx.x < 64) {
     double tmp = 0.0;
     if (a.n_psit > 1) tmp = 0.0 + wave_tree_sum([&](long long i) { return a.cdet[i + 1] * go.ps_raw[i + 1]; }, a.n_psit - 1, s_scr, a.seq);
     if (threadIdx.x == 0) { double w1 = go.ps_raw[0]; w1 = w1 - tmp; w1 = w1 / a.cdet[0]; w1 = w1 / a.cdet[0]; s_w1 = w1; }
@@ -151,10 +205,10 @@ __global__ void __launch_bounds__(TPB) k_psit_finish(PsitArgs a, double *__restr
   double s[NSTAT];
 #pragma unroll
   for (int k = 0; k < NSTAT; k++) s[k] = 0.0;
-  const double r0 = a.cnum[0] / a.cden[0];
+  const double r0 = a.own_first ? a.cnum[0] / a.cden[0] : 0.0;
   for (long long i = (long long)blockIdx.x * TPB + threadIdx.x; i < a.n_ct; i += (long long)gridDim.x * TPB) {
     double w = wt[i]; const u32 f = flg[i];
-    { const int kp = a.psit_of[i]; if (kp == 0) w = w1; else if (kp > 0) w = w - a.cdet[kp] * w1; }
+    { const int kp = a.psit_of[i]; if (kp == 0 && a.own_first) w = w1; else if (kp >= 0) w = w - a.cdet[kp] * w1; }
     int d = flg_impd(f), ini = flg_init(f); const int ps = flg_psign(f);
     if (!p.cti || i < a.n_perm) {                       // 2447-2461: with c_t_initiator only the first n_permanent_initiator slots are visited
       const int dd = d - p.imind > 0 ? d - p.imind : 0;
@@ -168,14 +222,14 @@ __global__ void __launch_bounds__(TPB) k_psit_finish(PsitArgs a, double *__restr
     if (go.on) {
       u64 nc; double wc;
       gate_children(w, go.cutoff, seed, go.step_next, go.keys[i] >> 32, nc, wc);
-      if (i == 0) { nc = 0; wc = 0.0; }                 // all moves of the first state are deterministic (do_walk.f90:3574)
+      if (i == 0 && a.own_first) { nc = 0; wc = 0.0; }  // all moves of the first state are deterministic (do_walk.f90:3574)
       go.nchild[i] = nc; go.wchild[i] = wc;
     }
     s[0] += w; s[1] += fabs(w); s[8] += w * w;          // 2590-2598
     if (ini == 3) s[4] += w * ps;
     if (d == 0 || (d == -2 && p.cti)) s[6] += fabs(w);
     double e_num, e_den;                                // 2701-2722
-    if (i == 0) { e_num = r0 * w; e_den = w; } else { e_num = a.cnum[i] * w; e_den = a.cden[i] * w; }
+    if (i == 0 && a.own_first) { e_num = r0 * w; e_den = w; } else { e_num = a.cnum[i] * w; e_den = a.cden[i] * w; }
     if (fabs(e_den) < 1e-22) e_den = fabs(e_den);
     s[2] += e_den; s[3] += e_num; s[9] += e_num * e_num; s[10] += e_den * e_den;
     s[11] += e_num * copysign(1.0, e_den); s[12] += fabs(e_den); s[5] += e_num * e_den;

@@ -145,6 +145,11 @@ struct PsitArgs {
   double *p2;                 // first-row sum over C(T): one partial per 4096 terms (two tree levels)
   int n_perm;                 // n_permanent_initiator (0 or 1: only the first state can be one, do_walk.f90:1276-1292)
   int seq;
+  // sharded (sqmc_gpu_set_hf_to_psit_shard): the tables above are this rank's share; one rank: own_first = 1, tx = null, shard_P = 1
+  int own_first;              // iown_first: slot 0 is the first state
+  double c1;                  // cdet_psi_t(1)
+  const double *tx;           // [shard_P + 1] T^-1 partials of all ranks and the owner's merged first weight, all-reduced (k_psit_tinv_part)
+  int shard_P, shard_me;
 };
 
 // staging buffer of the two-kernel annihilation of long lists (walk_kernels.h, k_anneal<., 0, 1>): the kept walkers of every tile, compacted
@@ -226,11 +231,16 @@ struct sqmc_gpu_ctx {
   HbHost *hb_host;
   long long dbg_n0, dbg_nall;          // sizes of the last step's list in front of the merge (sqmc_gpu_debug_premerge)
   bool psit_on; int base_key_bits; PsitArgs psit; int *d_ps_loc, *d_ps_of, *d_ps_impof; double *d_ps_c, *d_ps_diag, *d_ps_dwct, *d_ps_dwps, *d_ps_dwimp, *d_ps_p2, *d_ps_part, *d_ps_raw;
+  // hf_to_psit sharded over ranks (sqmc_gpu_set_hf_to_psit_shard): this rank's C(T) share (host copy, for the upload's check), its
+  // e_loc_num / den, the T^-1 exchange vector, and the caller's all-reduce of it (three-phase steps without a communicator)
+  bool psit_shard; std::vector<u64> ps_ct_up, ps_ct_dn; double *d_ps_num, *d_ps_den, *d_ps_tx;
+  sqmc_allreduce_fn psit_reduce; void *psit_reduce_user; double *psit_reduce_buf;
 };
 // a head enqueued for a step that is not going to be the next thing that happens (chained runs): forget it
 static void abandon_head(sqmc_gpu_ctx *c);
 static void psit_off(sqmc_gpu_ctx *c);
 static int shard_head_project(sqmc_gpu_ctx *c, bool with_sums, bool empty, const FinArgs *fin = nullptr);      // abi_shard.inc
+static int psit_shard_tinv(sqmc_gpu_ctx *c, const double *ps_raw);                                               // abi_shard.inc
 
 
 #include "walk_kernels.h"
@@ -461,6 +471,7 @@ int sqmc_gpu_finalize(sqmc_gpu_ctx *c) {
   hipFree(c->d_ct_up); hipFree(c->d_ct_dn); hipFree(c->d_ct_num); hipFree(c->d_ct_den); hipFree(c->d_ct_hkey); hipFree(c->d_ct_hidx);
   hipFree(c->d_ps_loc); hipFree(c->d_ps_of); hipFree(c->d_ps_impof); hipFree(c->d_ps_c); hipFree(c->d_ps_diag); hipFree(c->d_ps_dwct); hipFree(c->d_ps_dwps);
   hipFree(c->d_ps_dwimp); hipFree(c->d_ps_p2); hipFree(c->d_ps_part); hipFree(c->d_ps_raw); hipFree(c->stage_mem); hipFree(c->d_bpar);
+  hipFree(c->d_ps_num); hipFree(c->d_ps_den); hipFree(c->d_ps_tx);
   hipFree(c->d_sc); hipHostFree(c->h_sc); if (c->h_mail) hipHostFree((void *)c->h_mail);
   for (int i = 0; i < NTIMERS; i++) { hipEventDestroy(c->ev0[i]); hipEventDestroy(c->ev1[i]); }
   hipEventDestroy(c->e_fork); hipEventDestroy(c->e_join); hipEventDestroy(c->e_cnt); hipEventDestroy(c->e_spawned);
@@ -546,7 +557,7 @@ int sqmc_gpu_set_ct_table(sqmc_gpu_ctx *c, int64_t n, const uint64_t *up, const 
 // hf_to_psit off: the tables it was set up with are about to change
 static void psit_off(sqmc_gpu_ctx *c) {
   if (!c->psit_on) return;
-  c->psit_on = false; c->dev.ps.koff = 0;
+  c->psit_on = false; c->psit_shard = false; c->dev.ps.koff = 0;
   c->key_bits = c->base_key_bits; c->invalid_key = (1ull << c->key_bits) - 1ull;
   c->pack = (c->key_bits <= 32 && !getenv("SQMC_FORCE_UNPACKED")) ? 1 : 0;
 }
@@ -591,9 +602,11 @@ int sqmc_gpu_set_hf_to_psit(sqmc_gpu_ctx *c, int64_t n_psit, const int64_t *psit
   PsitArgs &a = c->psit; memset(&a, 0, sizeof(a));
   a.n_ct = n_ct; a.n_psit = n_psit; a.n_imp = c->n_imp; a.loc_psit = d_loc; a.cdet = d_c; a.diag = d_diag; a.psit_of = d_of; a.imp_of = d_impof;
   a.cnum = c->d_ct_num; a.cden = c->d_ct_den; a.dw_ct = d_dwct; a.dw_ps = d_dwps; a.dw_imp = d_dwimp; a.p2 = d_p2; a.n_perm = 0; a.seq = sum_order == 0 ? 1 : 0;
+  a.own_first = 1; a.c1 = cdet_psi_t[0]; a.tx = nullptr; a.shard_P = 1; a.shard_me = 0;
   u64 first[2];
   HIPCHK(hipMemcpy(&first[0], c->d_ct_up, 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&first[1], c->d_ct_dn, 8, hipMemcpyDeviceToHost));
   c->dev.ps.koff = total; c->dev.ps.hkey = c->d_ct_hkey; c->dev.ps.hmask = c->ct_mask; c->dev.ps.first_up = first[0]; c->dev.ps.first_dn = first[1]; c->dev.ps.n_ct = n_ct;
+  c->dev.ps.own_first = 1;
   c->key_bits = c->base_key_bits + 1; c->invalid_key = (1ull << c->key_bits) - 1ull;
   c->pack = (c->key_bits <= 32 && !getenv("SQMC_FORCE_UNPACKED")) ? 1 : 0;
   c->psit_on = true; c->nwalk = 0;           // walkers are uploaded anew, in the layout of this variant
@@ -614,22 +627,25 @@ int sqmc_gpu_upload_walkers(sqmc_gpu_ctx *c, int64_t n, const uint64_t *up, cons
     if (i && i != seg && !(up[i - 1] < up[i] || (up[i - 1] == up[i] && dn[i - 1] < dn[i]))) return fail(SQMC_ERR_BAD_ARG, "walkers must be sorted by (up,dn) and unique");
   }
   if (c->psit_on) {
-    if (n < seg) return fail(SQMC_ERR_BAD_ARG, "hf_to_psit: the walker list begins with ALL determinants of C(T)");
-    std::vector<u64> cu(seg), cd(seg);
-    HIPCHK(hipMemcpy(cu.data(), c->d_ct_up, seg * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(cd.data(), c->d_ct_dn, seg * 8, hipMemcpyDeviceToHost));
+    if (n < seg) return fail(SQMC_ERR_BAD_ARG, c->psit_shard ? "hf_to_psit: the walker list begins with ALL determinants of this rank's C(T) share"
+                                                              : "hf_to_psit: the walker list begins with ALL determinants of C(T)");
+    std::vector<u64> cu, cd;
+    if (c->psit_shard) { cu = c->ps_ct_up; cd = c->ps_ct_dn; }        // sharded: this rank's share of C(T), in C(T) order
+    else { cu.resize(seg); cd.resize(seg);
+           HIPCHK(hipMemcpy(cu.data(), c->d_ct_up, seg * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(cd.data(), c->d_ct_dn, seg * 8, hipMemcpyDeviceToHost)); }
     std::vector<int> impof(seg, -1); int row = 0, n_perm = 0;
     for (long long i = 0; i < seg; i++) {
-      if (up[i] != cu[i] || dn[i] != cd[i]) return fail(SQMC_ERR_BAD_ARG, "hf_to_psit: the first n_ct walkers must be the C(T) list");
+      if (up[i] != cu[i] || dn[i] != cd[i]) return fail(SQMC_ERR_BAD_ARG, c->psit_shard ? "hf_to_psit: the first walkers must be this rank's C(T) share" : "hf_to_psit: the first n_ct walkers must be the C(T) list");
       if (impd[i] != 0 && impd[i] != -2) return fail(SQMC_ERR_BAD_ARG, "hf_to_psit: a C(T) walker carries imp_distance 0 or -2");
       if (impd[i] == 0) impof[i] = row++;
-      if (init[i] == 3) { if (i != 0) return fail(SQMC_ERR_UNSUPPORTED, "hf_to_psit: only the first state can be a permanent initiator (do_walk.f90:1276-1292)"); n_perm = 1; }
+      if (init[i] == 3) { if (i != 0 || !c->dev.ps.own_first) return fail(SQMC_ERR_UNSUPPORTED, "hf_to_psit: only the first state can be a permanent initiator (do_walk.f90:1276-1292)"); n_perm = 1; }
     }
     for (long long i = seg; i < n; i++) {
       if (impd[i] < 1) return fail(SQMC_ERR_BAD_ARG, "hf_to_psit: a walker outside C(T) carries imp_distance >= 1 (the deterministic space lies inside C(T))");
       if (init[i] == 3) return fail(SQMC_ERR_UNSUPPORTED, "hf_to_psit: only the first state can be a permanent initiator");
     }
-    if (row != c->n_imp) return fail(SQMC_ERR_IMP_BROKEN, "number of imp_distance==0 walkers != n_imp");
-    HIPCHK(hipMemcpy(c->d_ps_impof, impof.data(), seg * 4, hipMemcpyHostToDevice));
+    if (row != (c->psit_shard ? c->n_imp_local : c->n_imp)) return fail(SQMC_ERR_IMP_BROKEN, "number of imp_distance==0 walkers != n_imp");
+    if (seg > 0) HIPCHK(hipMemcpy(c->d_ps_impof, impof.data(), seg * 4, hipMemcpyHostToDevice));
     c->psit.n_perm = n_perm;
   }
   HIPCHK(hipMemcpy(c->w.up, up, n * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(c->w.dn, dn, n * 8, hipMemcpyHostToDevice));
@@ -972,7 +988,7 @@ static int launch_side_kernels(sqmc_gpu_ctx *c, const StepP &p, long long n0, bo
     PrjPre pp; memset(&pp, 0, sizeof(pp));
     pp.n_imp = (int)c->n_imp; pp.ptr = c->d_prj_ptr; pp.col = c->d_prj_col; pp.val = c->d_prj_val; pp.x = c->d_prj_x; pp.y = a.dw_imp;
     hipLaunchKernelGGL(k_psit_imp_rows, dim3(nblk(c->n_imp, TPB / 64)), dim3(TPB), 0, st3, pp);
-    hipLaunchKernelGGL(k_psit_ct_col, dim3(nblk(a.n_ct)), dim3(TPB), 0, st3, a, (const double *)c->w.wt);
+    hipLaunchKernelGGL(k_psit_ct_col, dim3(nblk(a.n_ct)), dim3(TPB), 0, st3, a, (const double *)c->w.wt, (const double *)c->w.wt);
     hipLaunchKernelGGL(k_psit_ct_terms, dim3((unsigned)((a.n_ct + 4095) / 4096)), dim3(64), 0, st3, a, (const double *)c->w.wt);
     hipLaunchKernelGGL(k_psit_rows_fin, dim3(1), dim3(TPB), 0, st3, a, (const double *)c->w.wt, p.tau, p.e_trial);
     hipLaunchKernelGGL(k_psit_apply, dim3(nblk(a.n_ct)), dim3(TPB), 0, st3, a, c->w.wt, p.tau, p.e_trial);
@@ -1173,6 +1189,7 @@ static int step_tail_impl(sqmc_gpu_ctx *c, const StepP &p_in, long long n0, long
     std::swap(c->w.up, c->m.up); std::swap(c->w.dn, c->m.dn); std::swap(c->w.wt, c->m.wt); std::swap(c->w.flg, c->m.flg);
     std::swap(c->w.me, c->m.me); std::swap(c->w.en, c->m.en); std::swap(c->w.ed, c->m.ed); std::swap(c->w.irk, c->m.irk);
     if (c->psit_on) {          // do_walk.f90:2394-2462, 2487, 2590-2598, 2701-2722 on the C(T) segment of the NEW list
+      if (c->psit_shard) { int rx = psit_shard_tinv(c, go.ps_raw); if (rx) return rx; }      // 2394-2442 over ranks: the T^-1 partials of all of them
       TBEG(psit_fin, st);
       hipLaunchKernelGGL(k_psit_finish, dim3(PSIT_FB), dim3(TPB), 0, st, c->psit, c->w.wt, c->w.flg, p, c->d_ps_part, go, seed);
       TEND(psit_fin, st);
@@ -1446,7 +1463,7 @@ static int run_steps(sqmc_gpu_ctx *c, sqmc_popctl *pc, int64_t nsteps, double *s
     sp.reached_w_abs_gen = pc->reached_w_abs_gen; sp.reserved = 0;
     // pipelined head: once the target population has been reached tau and r_initiator stay put, and the head of a step
     // (gate, scan, spawn) depends on nothing else that this step's sums could change
-    c->pipeline_next = ((one_step == (step_fn)sqmc_gpu_step || (one_step == (step_fn)sqmc_gpu_shard_step && c->comm != nullptr && !getenv("SQMC_SHARD_NO_PIPELINE"))) && (it + 1 < nsteps || (c->chained_runs && one_step == (step_fn)sqmc_gpu_step)) &&
+    c->pipeline_next = ((one_step == (step_fn)sqmc_gpu_step || (one_step == (step_fn)sqmc_gpu_shard_step && c->comm != nullptr && !c->psit_on && !getenv("SQMC_SHARD_NO_PIPELINE"))) && (it + 1 < nsteps || (c->chained_runs && one_step == (step_fn)sqmc_gpu_step)) &&
                         pc->reached_w_abs_gen == 2 && c->rng_mode != SQMC_RNG_REPLAY && !getenv("SQMC_NO_PIPELINE"));
     double out[16];
     int r = one_step(c, &sp, out);

@@ -77,7 +77,7 @@ __global__ void __launch_bounds__(TPB) k_gate(ChemDev dev, const u64 *__restrict
   put_key(keys, vals, i, kk + ((p.koff && i >= p.nct) ? p.koff : 0ull), pack);      // sort key of the walker itself (hf_to_psit: the survivors outside C(T) sort behind C(T))
   u64 nc; double wc;
   gate_children(wt[i], p.cutoff, seed, step, kk, nc, wc);
-  if (p.koff && i == 0) { nc = 0; wc = 0.0; }      // hf_to_psit: all moves of the first state are deterministic (do_walk.f90:3574)
+  if (p.koff && i == 0 && dev.ps.own_first) { nc = 0; wc = 0.0; }      // hf_to_psit: all moves of the first state are deterministic (do_walk.f90:3574)
   nchild[i] = nc; wchild[i] = wc;
 }
 
@@ -255,10 +255,11 @@ __device__ __forceinline__ u64 spawn_emit(const ChemDev &dev, const WalkArr &w, 
     // not stored, k_merge supplies them for every slot >= n0
     SpawnRec r; r.up = ju; r.dn = jd; r.wt = wj; r.flg = pack_flg(d, ini, 0);
     w.sp[c] = r;
-    u64 key = det_key(dev, ju, jd);
+    const u64 rk = det_key(dev, ju, jd);
+    u64 key = rk;
     if (p.koff) key = psit_key(dev.ps, key);
     put_key(keys, vals, k, key, pack);
-    if (oo.okey) { oo.okey[c] = (u64)det_owner_any(oo.mode, key, ju, jd, oo.nranks); oo.oval[c] = (u32)c; }
+    if (oo.okey) { oo.okey[c] = (u64)det_owner_any(oo.mode, rk, ju, jd, oo.nranks); oo.oval[c] = (u32)c; }      // the owner of the determinant, not of its hf_to_psit sort key
     return key;
   } else {
     w.sp[c].wt = 0.0; put_key(keys, vals, k, invalid_key, pack);     // sorts behind every real determinant

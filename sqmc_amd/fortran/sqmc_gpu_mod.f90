@@ -18,6 +18,7 @@ module sqmc_gpu_mod
   public :: sqmc_gpu_annihilate, sqmc_gpu_build_spmv_plan, sqmc_gpu_hci_connections_slice
   public :: sqmc_gpu_comm_unique_id, sqmc_gpu_comm_init, sqmc_gpu_comm_size, sqmc_gpu_set_owner_hash, sqmc_gpu_tail_stats, sqmc_gpu_slowest_steps, sqmc_gpu_set_chained_runs, sqmc_gpu_hci_pt2, sqmc_gpu_hci_set_active_space, sqmc_gpu_set_heatbath_tables, sqmc_gpu_propose_heatbath_batch, sqmc_heatbath_tables, sqmc_gpu_shard_step, sqmc_gpu_shard_run, sqmc_gpu_shard_time_split, sqmc_gpu_davidson
   public :: sqmc_gpu_set_hf_to_psit, sqmc_gpu_setup_efficient_heatbath, sqmc_gpu_get_heatbath_tables
+  public :: sqmc_gpu_set_hf_to_psit_shard, sqmc_gpu_shard_finish_psit
   public :: sqmc_gpu_check
 
   integer(c_int), parameter, public :: SQMC_RNG_REPLAY = 0, SQMC_RNG_COUNTER = 1
@@ -214,6 +215,21 @@ module sqmc_gpu_mod
     integer(c_int) function sqmc_gpu_set_hf_to_psit(ctx, n_psit, psit_ct_index, cdet_psi_t, diag_elems, sum_order) bind(C, name='sqmc_gpu_set_hf_to_psit')
       import; type(c_ptr), value :: ctx; integer(c_int64_t), value :: n_psit; integer(c_int64_t), intent(in) :: psit_ct_index(*)
       real(c_double), intent(in) :: cdet_psi_t(*), diag_elems(*); integer(c_int32_t), value :: sum_order
+    end function
+    ! hf_to_psit on a sharded walk (do_walk.f90:1808-1886): this rank's C(T) share and Psi_T entries, after sqmc_gpu_shard_config
+    integer(c_int) function sqmc_gpu_set_hf_to_psit_shard(ctx, n_ct_local, ct_index, diag_elems, n_psit_local, psit_slot, psit_mask, &
+                                                         n_psit, cdet_psi_t, sum_order) bind(C, name='sqmc_gpu_set_hf_to_psit_shard')
+      import; type(c_ptr), value :: ctx; integer(c_int64_t), value :: n_ct_local, n_psit_local, n_psit
+      integer(c_int64_t), intent(in) :: ct_index(*), psit_slot(*), psit_mask(*)
+      real(c_double), intent(in) :: diag_elems(*), cdet_psi_t(*); integer(c_int32_t), value :: sum_order
+    end function
+    ! shard_finish of a sharded hf_to_psit step without a communicator: allreduce is an integer(c_int) function(buf_dev, n, user)
+    ! bind(C) that sums the n doubles at buf_dev over ranks in place (e.g. MPI_Allreduce through a host copy), passed as c_funloc
+    integer(c_int) function sqmc_gpu_shard_finish_psit(ctx, p, recv_dev, n_recv, reduce_buf_dev, allreduce, user, out_stats) &
+        bind(C, name='sqmc_gpu_shard_finish_psit')
+      import; type(c_ptr), value :: ctx; type(sqmc_step_params), intent(in) :: p; type(c_ptr), value :: recv_dev
+      integer(c_int64_t), value :: n_recv; type(c_ptr), value :: reduce_buf_dev; type(c_funptr), value :: allreduce
+      type(c_ptr), value :: user; real(c_double), intent(out) :: out_stats(16)
     end function
     integer(c_int) function sqmc_gpu_upload_walkers(ctx, n, up, dn, wt, imp_distance, initiator, perm_sign, matrix_elements, e_num, e_den) &
         bind(C, name='sqmc_gpu_upload_walkers')

@@ -473,6 +473,32 @@ def initial_walkers_psit(s, cdet, in_imp, w_abs_gen_begin):
                 perm_sign=psign, matrix_elements=np.full(n, 1e51), e_num=np.full(n, 1e51), e_den=np.full(n, 1e51))
 
 
+def psit_shard_tables(s, psit_ct_index, cdet, diag, in_imp, owner, rank, w_abs_gen_begin):
+    """One rank's share of the hf_to_psit tables on a sharded walk (do_walk.f90:1808-1886), from the global ones of psit_tables and an
+    owner rank for every C(T) determinant (C(T) order).  Returns a dict:
+      ct_index   1-based positions in C(T) of the determinants this rank owns (my_ndet_psi_t_connected), in C(T) order
+      diag       their diag_elems
+      psit_slot  1-based slots, in that share, of this rank's Psi_T determinants (my_locations_of_psit)
+      psit_mask  their 1-based indices in Psi_T, label order (ndet_psit_mask)
+      own_first  this rank holds the first state (iown_first = iown_psit1: Psi_T's first determinant is C(T)'s first)
+      imp_rows   global rows of the deterministic-space walkers of the share (sqmc_gpu_shard_config's global_row)
+      walkers    the share of initial_walkers_psit: weight only on the first state, on its owner
+    Pure: the owner array decides everything, so it runs without a GPU."""
+    owner = np.asarray(owner)
+    n_ct = len(s.ct_up)
+    if owner.shape != (n_ct,):
+        raise ValueError("one owner per C(T) determinant")
+    share = np.flatnonzero(owner == rank)
+    ix0 = np.asarray(psit_ct_index, np.int64) - 1
+    mine = owner[ix0] == rank
+    in_imp = np.asarray(in_imp, bool)
+    grow = np.cumsum(in_imp) - 1                              # deterministic space and C(T) are both in (up, dn) order
+    wk = initial_walkers_psit(s, cdet, in_imp, w_abs_gen_begin)
+    return dict(ct_index=share + 1, diag=np.asarray(diag, float)[share], psit_slot=np.searchsorted(share, ix0[mine]) + 1,
+                psit_mask=np.flatnonzero(mine) + 1, own_first=bool(owner[0] == rank), imp_rows=grow[share[in_imp[share]]].astype(np.int32),
+                walkers={k: v[share] for k, v in wk.items()})
+
+
 class PopControl:
     """Scalars around sqmc_gpu_step: tau/r_initiator ramp until the target population is first
     reached (do_walk.f90:2175-2184, 2913-2923), e_est / e_trial / reweight_factor_inv
@@ -733,9 +759,12 @@ class ShardedWalk:
 
     def __init__(self, host, w_target, rank, world, w_begin=None, mwalk=None, n_truncate_trial_wf=100, size_deterministic=1000,
                  tau_multiplier=0.1, e_trial=None, seed=(1346, 5634, 6635, 4361), min_wt=0.5, device_index=0, n_equil_steps=10**9, owner_hash=0,
-                 semistochastic=True):
+                 semistochastic=True, hf_to_psit=False, sum_order=1):
         import torch
         self.rank, self.world, self.min_wt = rank, world, min_wt
+        self.psit = bool(hf_to_psit)
+        if self.psit and not semistochastic:
+            raise ValueError("hf_to_psit needs a semistochastic walk")
         self.semi = 1 if semistochastic else 0          # 0: semistochastic = f, no deterministic space; join_walker2 is local to a rank (do_walk.f90:2475)
         w_begin = w_begin if w_begin is not None else w_target
         per_rank = w_target / world
@@ -743,6 +772,11 @@ class ShardedWalk:
         self.g = g = host.gpu(rng_mode=RNG_COUNTER, seed=rank_seed(seed, rank), mwalk=mwalk)
         if owner_hash:
             g.set_owner_hash(owner_hash)       # 1: the reference's get_det_owner (djb_hash), mpi_routines.f90:354-445
+        if self.psit:
+            g, s, wk, mwalk = self._setup_psit(host, g, rank, world, w_begin, mwalk, per_rank, n_truncate_trial_wf, size_deterministic,
+                                               tau_multiplier, seed, owner_hash, sum_order)
+            self._finish_init(torch, g, s, wk, mwalk, w_target, e_trial, n_equil_steps, device_index)
+            return
         self.setup = s = host.setup_walk(g, n_truncate_trial_wf, size_deterministic, tau_multiplier)
         if self.semi:
             g.set_projector(s.prj_counts, s.prj_indices, s.prj_values)
@@ -759,9 +793,36 @@ class ShardedWalk:
         rows = [imp_index[(int(a), int(b))] for a, b, d in zip(mine["up"], mine["dn"], mine["imp_distance"]) if d == 0]
         g.shard_config(rank, world, rows)
         g.upload_walkers(mine)
+        self._finish_init(torch, g, s, wk, mwalk, w_target, e_trial, n_equil_steps, device_index)
+
+    def _setup_psit(self, host, g, rank, world, w_begin, mwalk, per_rank, n_truncate_trial_wf, size_deterministic, tau_multiplier, seed,
+                    owner_hash, sum_order):
+        """hf_to_psit: the global tables on every rank, this rank's share of them (psit_shard_tables), MWALK from the share"""
+        self.setup = s = host.setup_walk(g, n_truncate_trial_wf, size_deterministic, tau_multiplier, rediagonalize=True)
+        ix, cdet, diag, pc_, pi_, pv_, in_imp = psit_tables(g, s)
+        owner = g.det_owner(s.ct_up, s.ct_dn, world)
+        tb = psit_shard_tables(s, ix, cdet, diag, in_imp, owner, rank, w_begin)
+        need = int(3 * (per_rank / self.min_wt + len(tb["ct_index"])))          # do_walk.f90:653-655 with this rank's share of C(T)
+        if mwalk < need:
+            g.close()
+            self.g = g = host.gpu(rng_mode=RNG_COUNTER, seed=rank_seed(seed, rank), mwalk=need)
+            if owner_hash:
+                g.set_owner_hash(owner_hash)
+            mwalk = need
+        g.set_projector(pc_, pi_, pv_)
+        g.set_ct_table(s.ct_up, s.ct_dn, s.ct_num, s.ct_den)
+        g.shard_config(rank, world, tb["imp_rows"])
+        g.set_hf_to_psit_shard(tb["ct_index"], tb["diag"], tb["psit_slot"], tb["psit_mask"], cdet, sum_order)
+        g.upload_walkers(tb["walkers"])
+        self.shard_tables, self.owner_ct = tb, owner
+        return g, s, initial_walkers_psit(s, cdet, in_imp, w_begin), mwalk
+
+    def _finish_init(self, torch, g, s, wk, mwalk, w_target, e_trial, n_equil_steps, device_index):
         dev = torch.device("cuda", device_index)
         self.dev = dev
-        self.xg = torch.zeros(max(len(s.imp_up), 1), dtype=torch.float64, device=dev)
+        # hf_to_psit: 2 * world slots of row partials behind the weights, and the world + 1 doubles of the T^-1 exchange
+        self.xg = torch.zeros(max(len(s.imp_up), 1) + (2 * self.world if self.psit else 0), dtype=torch.float64, device=dev)
+        self.tx = torch.zeros(self.world + 1, dtype=torch.float64, device=dev) if self.psit else None
         cap = mwalk
         self.send = torch.empty((cap, 4), dtype=torch.int64, device=dev)
         self.recv = torch.empty((cap, 4), dtype=torch.int64, device=dev)
@@ -810,7 +871,13 @@ class ShardedWalk:
         counts = self.g.shard_pack(prm, self.xg.data_ptr(), self.send.data_ptr(), self.cap, self.world)
         nr = exchange_records(self.send, counts, self.recv)
         torch.cuda.synchronize()
-        local = self.g.shard_finish(prm, self.recv.data_ptr(), nr)
+        if self.psit:
+            def tinv_allreduce():
+                _allreduce_dev(self.tx)
+                torch.cuda.synchronize()
+            local = self.g.shard_finish_psit(prm, self.recv.data_ptr(), nr, self.tx.data_ptr(), tinv_allreduce)
+        else:
+            local = self.g.shard_finish(prm, self.recv.data_ptr(), nr)
         out = allreduce_step_sums(local, device=self.dev)
         r = self.pc.post_step(out)
         if r != 1.0 and self.semi:
