@@ -146,6 +146,24 @@ int sqmc_gpu_get_heatbath_tables(sqmc_gpu_ctx *ctx, sqmc_heatbath_tables *t, int
 int sqmc_gpu_propose_heatbath_batch(sqmc_gpu_ctx *ctx, int64_t n, double tau, const uint64_t *up, const uint64_t *dn, const int32_t *seeds,
                                     uint64_t *det_j_up, uint64_t *det_j_dn, double *weight_j, int32_t *seeds_after);
 
+/* proposal_method 'CauchySchwarz' (chem only, time_sym = 0).
+ * replaces: setup_orb_by_symm's CauchySchwarz block (chemistry.f90:2505-2523): sqrt_integrals(i,j) = sqrt((ij|ij)), cs_sqrt_orb and
+ * sym_sum_cs_sqrt, built from the context's integrals in the reference's loop order.  Like the reference it stops on an exchange
+ * integral below -1e-6 (a default-real literal: -9.999999974752427e-07) -- SQMC_ERR_BAD_ARG, last error "Negative integrals!", nothing
+ * changed -- and overwrites every slightly negative one with 0 in the integrals themselves (host and device), which H then uses
+ * everywhere; *n_clamped (may be null) counts them.  As in system_setup_chem, this comes before anything built from H: with a projector,
+ * C(T), Psi_T tables, HCI tables or walkers present it fails with SQMC_ERR_BAD_ARG.  Fast heat-bath and Cauchy-Schwarz exclude each other
+ * on one context (the second set-up fails with SQMC_ERR_BAD_ARG, the first stays).  After this call sqmc_gpu_step / _run and the sharded
+ * steps spawn with off_diagonal_move_chem_cauchySchwarz (2530-4233, do_walk.f90:3613-3614, 3937-3938), one walker slot per child,
+ * both RNG disciplines; the intrinsic random_number draws of the reference come from the walk's own stream
+ * (tests/golden/README_cauchyschwarz.md).  hf_to_psit with this proposal is refused (SQMC_ERR_UNSUPPORTED). */
+int sqmc_gpu_setup_cauchy_schwarz(sqmc_gpu_ctx *ctx, int32_t *n_clamped);
+/* n proposals of off_diagonal_move_chem_cauchySchwarz (chemistry.f90:2530-4233), each from its own rannyu state seeds[4 i .. 4 i + 3]
+ * (test door, like sqmc_gpu_propose_batch): det_j and weight_j = -tau H_ij / proposal_prob (4204); weight 0 and det_j = det_i where
+ * the reference returns early or a cumulative search falls through. */
+int sqmc_gpu_propose_cauchy_schwarz_batch(sqmc_gpu_ctx *ctx, int64_t n, double tau, const uint64_t *up, const uint64_t *dn, const int32_t *seeds,
+                                          uint64_t *det_j_up, uint64_t *det_j_dn, double *weight_j, int32_t *seeds_after);
+
 /* replaces: dtm_hb / pq_ind / pq_count built by setup_efficient_heatbath (chemistry.f90:900-993).
  * hb_r/hb_s/hb_absH: n_hb records sorted by descending absH inside each (p,q) class;
  * pq_ind (1-based start) / pq_count indexed by combine_2_indices(p,q) in [1, n_pq]. */

@@ -22,7 +22,7 @@ RNG_REPLAY, RNG_COUNTER = 0, 1
 _LIB = None
 
 EXPORTS = [
-    "sqmc_gpu_set_device", "sqmc_gpu_init_chem", "sqmc_gpu_init_heg", "sqmc_gpu_init_hubbard", "sqmc_gpu_finalize", "sqmc_gpu_last_error", "sqmc_gpu_set_hb_tables", "sqmc_gpu_set_heatbath_tables", "sqmc_gpu_setup_efficient_heatbath", "sqmc_gpu_get_heatbath_tables", "sqmc_gpu_propose_heatbath_batch", "sqmc_gpu_set_projector",
+    "sqmc_gpu_set_device", "sqmc_gpu_init_chem", "sqmc_gpu_init_heg", "sqmc_gpu_init_hubbard", "sqmc_gpu_finalize", "sqmc_gpu_last_error", "sqmc_gpu_set_hb_tables", "sqmc_gpu_set_heatbath_tables", "sqmc_gpu_setup_efficient_heatbath", "sqmc_gpu_get_heatbath_tables", "sqmc_gpu_propose_heatbath_batch", "sqmc_gpu_setup_cauchy_schwarz", "sqmc_gpu_propose_cauchy_schwarz_batch", "sqmc_gpu_set_projector",
     "sqmc_gpu_scale_projector", "sqmc_gpu_set_ct_table", "sqmc_gpu_set_hf_to_psit", "sqmc_gpu_set_hf_to_psit_shard", "sqmc_gpu_upload_walkers", "sqmc_gpu_num_walkers",
     "sqmc_gpu_download_walkers", "sqmc_gpu_step", "sqmc_gpu_run", "sqmc_gpu_annihilate", "sqmc_gpu_det_owner", "sqmc_gpu_set_owner_hash", "sqmc_gpu_shard_config",
     "sqmc_gpu_shard_begin", "sqmc_gpu_shard_pack", "sqmc_gpu_shard_finish", "sqmc_gpu_shard_finish_psit", "sqmc_gpu_comm_unique_id", "sqmc_gpu_comm_init", "sqmc_gpu_comm_size",
@@ -500,6 +500,24 @@ class GpuChem:
         self.L.sqmc_gpu_propose_heatbath_batch.argtypes = [C.c_void_p, C.c_int64, C.c_double] + [C.c_void_p] * 7
         _chk(self.L.sqmc_gpu_propose_heatbath_batch(self.h, n, float(tau), _p(u), _p(d), _p(s), _p(ju), _p(jd), _p(wj), _p(sa)))
         return ju.reshape(n, 2), jd.reshape(n, 2), wj.reshape(n, 2), sa.reshape(n, 4)
+
+    def setup_cauchy_schwarz(self):
+        """proposal_method CauchySchwarz from here on: setup_orb_by_symm's tables, with its stop on an exchange integral below -1e-6
+        (SqmcGpuError "Negative integrals!") and its clamp of the slightly negative ones to 0.  Returns how many were clamped."""
+        n = C.c_int32(0)
+        self.L.sqmc_gpu_setup_cauchy_schwarz.argtypes = [C.c_void_p, C.c_void_p]
+        _chk(self.L.sqmc_gpu_setup_cauchy_schwarz(self.h, C.byref(n)))
+        return int(n.value)
+
+    def propose_cauchy_schwarz_batch(self, tau, up, dn, seeds):
+        """n Cauchy-Schwarz proposals, proposal i from the rannyu state seeds[i] (4 limbs): det_j, weight_j (0: no move), seeds after"""
+        u, d = _u64(up), _u64(dn)
+        s = np.ascontiguousarray(seeds, np.int32).reshape(-1)
+        n = len(u)
+        ju, jd, wj, sa = np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.zeros(n), np.zeros(4 * n, np.int32)
+        self.L.sqmc_gpu_propose_cauchy_schwarz_batch.argtypes = [C.c_void_p, C.c_int64, C.c_double] + [C.c_void_p] * 7
+        _chk(self.L.sqmc_gpu_propose_cauchy_schwarz_batch(self.h, n, float(tau), _p(u), _p(d), _p(s), _p(ju), _p(jd), _p(wj), _p(sa)))
+        return ju, jd, wj, sa.reshape(n, 4)
 
     def propose_batch(self, tau, up, dn, seeds):
         u, d = _u64(up), _u64(dn)

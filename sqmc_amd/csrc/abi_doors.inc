@@ -225,6 +225,7 @@ int sqmc_gpu_propose_batch(sqmc_gpu_ctx *c, int64_t n, double tau, const uint64_
 int sqmc_gpu_set_heatbath_tables(sqmc_gpu_ctx *c, const sqmc_heatbath_tables *t) {
   abandon_head(c);          // a head enqueued with one walker slot per child must not meet a tail that counts two
   if (!c || !t) return fail(SQMC_ERR_BAD_ARG, "null argument");
+  if (c->dev.cs.on) return fail(SQMC_ERR_BAD_ARG, "the context already proposes by Cauchy-Schwarz (sqmc_gpu_setup_cauchy_schwarz)");
   if (c->htab.sys_type != 0) return fail(SQMC_ERR_UNSUPPORTED, "the efficient heat-bath proposal is a 'chem' proposal");
   if (t->norb != c->htab.norb) return fail(SQMC_ERR_BAD_ARG, "norb of the tables differs from the context's");
   const int n = t->norb; const long long npairs = ((long long)n * (n - 1)) / 2 + n;
@@ -274,6 +275,80 @@ int sqmc_gpu_propose_heatbath_batch(sqmc_gpu_ctx *c, int64_t n, double tau, cons
   HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(c->st));
   HIPCHK(hipMemcpy(ju, dju, 2 * n * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(jd, djd, 2 * n * 8, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(wj, dw, 2 * n * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(s.data(), dso, n * 8, hipMemcpyDeviceToHost));
+  for (long long i = 0; i < n; i++) { u64 x = s[i]; seeds_after[4 * i] = (int)((x >> 36) & 4095); seeds_after[4 * i + 1] = (int)((x >> 24) & 4095);
+    seeds_after[4 * i + 2] = (int)((x >> 12) & 4095); seeds_after[4 * i + 3] = (int)(x & 4095); }
+  hipFree(du); hipFree(dd); hipFree(ds); hipFree(dju); hipFree(djd); hipFree(dso); hipFree(dw);
+  return SQMC_OK;
+}
+
+// setup_orb_by_symm, chemistry.f90:2505-2523, with proposal_method = 'CauchySchwarz'
+int sqmc_gpu_setup_cauchy_schwarz(sqmc_gpu_ctx *c, int32_t *n_clamped) {
+  abandon_head(c);
+  if (!c) return fail(SQMC_ERR_BAD_ARG, "null ctx");
+  if (c->htab.sys_type != 0) return fail(SQMC_ERR_UNSUPPORTED, "the Cauchy-Schwarz proposal is a 'chem' proposal");
+  if (c->htab.time_sym) return fail(SQMC_ERR_UNSUPPORTED, "the Cauchy-Schwarz proposal with time_sym = .true. is not built");
+  if (c->dev.hb.on) return fail(SQMC_ERR_BAD_ARG, "the context already proposes by fast heat-bath");
+  // the tables may change integrals that H depends on: nothing built from them may exist yet (system_setup_chem order)
+  if (c->n_imp > 0 || c->d_prj_ptr || c->d_ct_up || c->psit_on || c->nwalk > 0 || c->d_hb_r)
+    return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_setup_cauchy_schwarz must come before the projector, C(T), Psi_T, the HCI tables and the walkers");
+  const ChemTab &t = c->htab;
+  const int n = t.norb;
+  std::vector<double> ints((size_t)c->n_ints + 1);
+  HIPCHK(hipMemcpy(ints.data(), c->d_ints, ints.size() * sizeof(double), hipMemcpyDeviceToHost));
+  auto idx = [&](int i, int j) { const long long a = t.c2[i * t.c2_stride + j]; return (size_t)((a * (a - 1)) / 2 + a); };    // integral_index(i,j,i,j)
+  const double stop_below = (double)-1e-6f;           // the literal is default real (2514)
+  for (int i = 1; i <= n; i++) for (int j = 1; j <= n; j++)
+    if (ints[idx(i, j)] < stop_below) return fail(SQMC_ERR_BAD_ARG, "Negative integrals!");
+  int nclamp = 0;
+  std::vector<double> sq((size_t)n * n, 0.0), orb(n, 0.0), sym((size_t)SQ_MAXSYM * n, 0.0);
+  for (int i = 1; i <= n; i++)
+    for (int j = 1; j <= n; j++) {
+      const int s1 = t.orbsym[j];
+      double &v = ints[idx(i, j)];
+      if (v < 0) { v = 0; nclamp++; }
+      const double r = sqrt(v);
+      sq[(size_t)(i - 1) * n + (j - 1)] = r;
+      sym[(size_t)(s1 - 1) * n + (i - 1)] = sym[(size_t)(s1 - 1) * n + (i - 1)] + r;
+      orb[i - 1] = orb[i - 1] + r;
+    }
+  // the new tables are complete on the device before the old ones go: a failure part way leaves the context as it was
+  const std::vector<double> *src[3] = {&sq, &orb, &sym};
+  double *fresh[3] = {nullptr, nullptr, nullptr};
+  for (int q = 0; q < 3; q++) {
+    if (hipMalloc(&fresh[q], src[q]->size() * sizeof(double)) != hipSuccess ||
+        hipMemcpy(fresh[q], src[q]->data(), src[q]->size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+      for (int k = 0; k <= q; k++) hipFree(fresh[k]);
+      return fail(SQMC_ERR_HIP, "sqmc_gpu_setup_cauchy_schwarz: table upload failed");
+    }
+  }
+  if (nclamp && hipMemcpy(c->d_ints, ints.data(), ints.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+    for (int k = 0; k < 3; k++) hipFree(fresh[k]);
+    return fail(SQMC_ERR_HIP, "sqmc_gpu_setup_cauchy_schwarz: integral upload failed");
+  }
+  for (int q = 0; q < 3; q++) { hipFree(c->d_cs[q]); c->d_cs[q] = fresh[q]; }
+  CsDev cs; memset(&cs, 0, sizeof(cs));
+  cs.on = 1; cs.norb = n; cs.sq = c->d_cs[0]; cs.orb = c->d_cs[1]; cs.sym = c->d_cs[2];
+  c->dev.cs = cs;
+  if (n_clamped) *n_clamped = nclamp;
+  return SQMC_OK;
+}
+
+int sqmc_gpu_propose_cauchy_schwarz_batch(sqmc_gpu_ctx *c, int64_t n, double tau, const uint64_t *up, const uint64_t *dn, const int32_t *seeds,
+                                          uint64_t *ju, uint64_t *jd, double *wj, int32_t *seeds_after) {
+  if (!c) return fail(SQMC_ERR_BAD_ARG, "null ctx");
+  if (!c->dev.cs.on) return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_setup_cauchy_schwarz not called");
+  if (n <= 0) return SQMC_OK;
+  std::vector<u64> s(n);
+  for (long long i = 0; i < n; i++) s[i] = (((u64)seeds[4 * i] << 36) + ((u64)seeds[4 * i + 1] << 24) + ((u64)seeds[4 * i + 2] << 12) + (u64)seeds[4 * i + 3]) & SQ_MASK48;
+  u64 *du, *dd, *ds, *dju, *djd, *dso; double *dw;
+  HIPCHK(hipMalloc(&du, n * 8)); HIPCHK(hipMalloc(&dd, n * 8)); HIPCHK(hipMalloc(&ds, n * 8)); HIPCHK(hipMalloc(&dju, n * 8));
+  HIPCHK(hipMalloc(&djd, n * 8)); HIPCHK(hipMalloc(&dso, n * 8)); HIPCHK(hipMalloc(&dw, n * 8));
+  HIPCHK(hipMemcpy(du, up, n * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dd, dn, n * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(ds, s.data(), n * 8, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_propose_cauchy_batch, dim3(nblk(n)), dim3(TPB), 0, c->st, c->dev, du, dd, ds, dju, djd, dw, dso, (long long)n, tau);
+  HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(c->st));
+  HIPCHK(hipMemcpy(ju, dju, n * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(jd, djd, n * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(wj, dw, n * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(s.data(), dso, n * 8, hipMemcpyDeviceToHost));
   for (long long i = 0; i < n; i++) { u64 x = s[i]; seeds_after[4 * i] = (int)((x >> 36) & 4095); seeds_after[4 * i + 1] = (int)((x >> 24) & 4095);
     seeds_after[4 * i + 2] = (int)((x >> 12) & 4095); seeds_after[4 * i + 3] = (int)(x & 4095); }
   hipFree(du); hipFree(dd); hipFree(ds); hipFree(dju); hipFree(djd); hipFree(dso); hipFree(dw);

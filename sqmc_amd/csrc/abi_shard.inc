@@ -207,7 +207,7 @@ static int shard_begin_impl(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double 
     if (n0 > 0) {
       TBEG(spawn, st);
       if (M > n0)      // first: it posts the child count to the host mailbox as soon as it starts
-        SPAWN_LAUNCH(c->dev.hb.on, 0, dim3(nblk(M - n0)), dim3(TPB), 0, st, c->dev, c->w, c->d_child_off, c->d_wchild, c->d_child_state, c->d_keys, c->d_vals,
+        SPAWN_LAUNCH(spawn_kind(c), 0, dim3(nblk(M - n0)), dim3(TPB), 0, st, c->dev, c->w, c->d_child_off, c->d_wchild, c->d_child_state, c->d_keys, c->d_vals,
                            n0, M, p, c->rng_mode, c->seed64, c->step_no, c->invalid_key, (const DevScalars *)c->d_sc, c->d_mail, cseq, c->pack, 0, shard_owner_out(c), BucketArgs{}, FinArgs{}, PrjPre{}, 0);
       TEND(spawn, st);
     }
@@ -635,6 +635,7 @@ int sqmc_gpu_set_hf_to_psit_shard(sqmc_gpu_ctx *c, int64_t n_ct_local, const int
   if (c->mwalk <= 0) return fail(SQMC_ERR_BAD_ARG, "context has no walker arrays (mwalk=0)");
   if (c->shard_n < 1 || !c->d_grow) return fail(SQMC_ERR_BAD_ARG, "call sqmc_gpu_shard_config before sqmc_gpu_set_hf_to_psit_shard");
   if (c->dev.hb.on) return fail(SQMC_ERR_UNSUPPORTED, "hf_to_psit with proposal_method fast_heatbath is not built");
+  if (c->dev.cs.on) return fail(SQMC_ERR_UNSUPPORTED, "hf_to_psit with proposal_method CauchySchwarz is not built");
   if (c->htab.sys_type == 2) return fail(SQMC_ERR_UNSUPPORTED, "hf_to_psit is not built for the Hubbard model");
   if (!c->d_ct_up || c->n_ct < 1) return fail(SQMC_ERR_BAD_ARG, "set the (global) C(T) table first");
   if (!c->d_prj_ptr || c->n_imp < 1) return fail(SQMC_ERR_BAD_ARG, "set the (global) deterministic-space matrix first");

@@ -55,6 +55,13 @@ struct HbDev {
   const double *htot_opp;                // [norb][norb][norb]
 };
 
+// Cauchy-Schwarz proposal tables on the device (cauchy_device.h), 0-based: sq[(i-1)*norb + (j-1)] = sqrt_integrals(i,j),
+// orb[i-1] = cs_sqrt_orb(i), sym[(s-1)*norb + (i-1)] = sym_sum_cs_sqrt(s,i)
+struct CsDev {
+  int on, norb;
+  const double *sq, *orb, *sym;
+};
+
 #define SQ_BINOM_STRIDE 68              // C(c, i) for every i <= 64, + 3 entries the 4-wide rounds of colex_rank may touch
 // hf_to_psit = .true. (do_walk.f90:378-386, psit_kernels.h): the walker list is [C(T), fixed | survivors outside C(T)], which is
 // the list sorted by  key' = rank + (determinant outside C(T) ? koff : 0),  koff = number of determinants of the space
@@ -75,6 +82,7 @@ struct ChemDev {                        // pointers into HBM, passed by value
   const int *hb_r, *hb_s; const double *hb_absH; const long long *pq_ind; const int *pq_count;
   double max_double;
   HbDev hb;                             // proposal_method fast_heatbath (hb.on) instead of uniform2
+  CsDev cs;                             // proposal_method CauchySchwarz (cs.on) instead of uniform2
 };
 
 // 32-bit words of a ChemTab that are in use: header + the used part of combine_2 only (norb=26:

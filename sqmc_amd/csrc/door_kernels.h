@@ -93,6 +93,19 @@ __global__ void __launch_bounds__(TPB) k_propose_heatbath_batch(ChemDev dev, con
   for (int k = 0; k < 2; k++) { ju[2 * i + k] = a[k]; jd[2 * i + k] = b[k]; wj[2 * i + k] = w[k]; }
   state_out[i] = g.x;
 }
+__global__ void __launch_bounds__(TPB) k_propose_cauchy_batch(ChemDev dev, const u64 *up, const u64 *dn, const u64 *state_in, u64 *ju, u64 *jd,
+                                                              double *wj, u64 *state_out, long long n, double tau) {
+  __shared__ ChemTab t;
+  stage_tab(&t, dev.tab, dev.tab_words);
+  long long i = (long long)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  Rng g; g.mode = 0; g.x = state_in[i];
+  u64 a, b; double prob;
+  const int level = propose_cauchy_schwarz(t, dev.cs, g, up[i], dn[i], a, b, prob);
+  double w = 0.0;
+  if (level > 0) w = proposal_weight(t, dev.integrals, tau, up[i], dn[i], a, b, level, prob);
+  ju[i] = a; jd[i] = b; wj[i] = w; state_out[i] = g.x;
+}
 __global__ void __launch_bounds__(TPB) k_propose_batch(ChemDev dev, const u64 *up, const u64 *dn, const u64 *state_in, u64 *ju, u64 *jd,
                                                        double *wj, u64 *state_out, long long n, double tau) {
   __shared__ ChemTab t;

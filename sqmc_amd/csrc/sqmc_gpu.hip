@@ -31,6 +31,7 @@
 #include "../../include/sqmc_gpu.h"
 #include "chem_device.h"
 #include "heatbath_device.h"
+#include "cauchy_device.h"
 #include "scan_sort.h"
 #include "bucket_partition.h"
 #include "hii_group.h"
@@ -161,6 +162,7 @@ struct sqmc_gpu_ctx {
   ChemTab htab; ChemTab *d_tab; double *d_ints; ChemDev dev;
   int *d_hb_r, *d_hb_s; double *d_hb_absH; long long *d_pq_ind; int *d_pq_count;
   void *d_hbt[16];                     // device copies of the efficient heat-bath tables (sqmc_gpu_set_heatbath_tables)
+  double *d_cs[3]; long long n_ints;   // Cauchy-Schwarz tables (sqmc_gpu_setup_cauchy_schwarz); length of the integral table - 1
   long long mwalk, nwalk;
   WalkArr w, m;                        // walkers (main + appended spawns), merge results
   u64 *d_nchild; u64 *d_child_off; double *d_wchild; u64 *d_child_state;
@@ -245,8 +247,14 @@ static int psit_shard_tinv(sqmc_gpu_ctx *c, const double *ps_raw);              
 
 #include "walk_kernels.h"
 #include "psit_kernels.h"
-#define SPAWN_LAUNCH(HB_, FUSE_, ...) do { if (HB_) hipLaunchKernelGGL((k_spawn<1, 1>), __VA_ARGS__); else if (FUSE_) hipLaunchKernelGGL((k_spawn<0, 1>), __VA_ARGS__); else hipLaunchKernelGGL((k_spawn<0, 0>), __VA_ARGS__); } while (0)
-#define SPAWN_LAUNCH_EXT(HB_, FUSE_, ...) do { if (HB_) hipExtLaunchKernelGGL((k_spawn<1, 1>), __VA_ARGS__); else if (FUSE_) hipExtLaunchKernelGGL((k_spawn<0, 1>), __VA_ARGS__); else hipExtLaunchKernelGGL((k_spawn<0, 0>), __VA_ARGS__); } while (0)
+// PK_: spawn_kind(c).  Heat-bath and Cauchy-Schwarz have one instantiation each (FUSE = 1 with no spare blocks and no partition is the plain spawn)
+static inline int spawn_kind(const sqmc_gpu_ctx *c) { return c->dev.hb.on ? SPAWN_HEATBATH : (c->dev.cs.on ? SPAWN_CAUCHY : SPAWN_UNIFORM); }
+#define SPAWN_LAUNCH(PK_, FUSE_, ...) do { const int pk_ = (PK_); if (pk_ == SPAWN_HEATBATH) hipLaunchKernelGGL((k_spawn<SPAWN_HEATBATH, 1>), __VA_ARGS__); \
+  else if (pk_ == SPAWN_CAUCHY) hipLaunchKernelGGL((k_spawn<SPAWN_CAUCHY, 1>), __VA_ARGS__); \
+  else if (FUSE_) hipLaunchKernelGGL((k_spawn<SPAWN_UNIFORM, 1>), __VA_ARGS__); else hipLaunchKernelGGL((k_spawn<SPAWN_UNIFORM, 0>), __VA_ARGS__); } while (0)
+#define SPAWN_LAUNCH_EXT(PK_, FUSE_, ...) do { const int pk_ = (PK_); if (pk_ == SPAWN_HEATBATH) hipExtLaunchKernelGGL((k_spawn<SPAWN_HEATBATH, 1>), __VA_ARGS__); \
+  else if (pk_ == SPAWN_CAUCHY) hipExtLaunchKernelGGL((k_spawn<SPAWN_CAUCHY, 1>), __VA_ARGS__); \
+  else if (FUSE_) hipExtLaunchKernelGGL((k_spawn<SPAWN_UNIFORM, 1>), __VA_ARGS__); else hipExtLaunchKernelGGL((k_spawn<SPAWN_UNIFORM, 0>), __VA_ARGS__); } while (0)
 #include "bucket_kernels.h"
 #include "door_kernels.h"
 #include "hci_kernels.h"
@@ -377,6 +385,7 @@ int sqmc_gpu_init_chem(const sqmc_chem_cfg *cfg, sqmc_gpu_ctx **out) {
   }
   HIPCHK(hipMalloc(&c->d_ints, (cfg->n_integrals + 1) * sizeof(double)));
   HIPCHK(hipMemcpy(c->d_ints, cfg->integrals, (cfg->n_integrals + 1) * sizeof(double), hipMemcpyHostToDevice));
+  c->n_ints = cfg->n_integrals;
   return init_common(c, cfg->norb, cfg->nup, cfg->ndn, cfg->rng_mode, cfg->irand_seed, cfg->mwalk, out);
 }
 
@@ -465,6 +474,7 @@ int sqmc_gpu_finalize(sqmc_gpu_ctx *c) {
   }
   hipFree(c->d_binom); hipFree(c->d_grow); hipFree(c->d_ginv);
   for (int q = 0; q < 16; q++) hipFree(c->d_hbt[q]);
+  for (int q = 0; q < 3; q++) hipFree(c->d_cs[q]);
   comm_release(c);
   hipFree(c->d_tab); hipFree(c->d_ints); hipFree(c->d_hb_r); hipFree(c->d_hb_s); hipFree(c->d_hb_absH); hipFree(c->d_pq_ind); hipFree(c->d_pq_count);
   hipFree(c->d_prj_ptr); hipFree(c->d_prj_col); hipFree(c->d_prj_val); hipFree(c->d_loc_imp); hipFree(c->d_prj_x); hipFree(c->d_prj_xs[0]); hipFree(c->d_prj_xs[1]); hipFree(c->d_prj_y);
@@ -933,10 +943,10 @@ static int enqueue_head(sqmc_gpu_ctx *c, const StepP &p, u64 step, long long n0,
   const size_t spawn_lds = std::max<size_t>(hb.B > 0 ? (size_t)BK_PART_LDS(hb.B) : 0, hq_blk > 0 ? (size_t)(TPB / 16) * bk_hii_terms_of(c->htab.nup, c->htab.ndn) * 8 : 0);
   if (nfree > 0) {
     if (s0)
-      SPAWN_LAUNCH_EXT(c->dev.hb.on, spawn_fuse, dim3(nblk(nfree) + (spawn_fin.on ? 1 : 0) + hq_blk + (pp.n_imp > 0 ? nblk(pp.n_imp, TPB / 64) : 0) + ((hb.kb || hb.kb_out) ? 1 : 0)), dim3(TPB), spawn_lds, st, s0, s1, 0, c->dev, c->w, c->d_child_off, c->d_wchild,
+      SPAWN_LAUNCH_EXT(spawn_kind(c), spawn_fuse, dim3(nblk(nfree) + (spawn_fin.on ? 1 : 0) + hq_blk + (pp.n_imp > 0 ? nblk(pp.n_imp, TPB / 64) : 0) + ((hb.kb || hb.kb_out) ? 1 : 0)), dim3(TPB), spawn_lds, st, s0, s1, 0, c->dev, c->w, c->d_child_off, c->d_wchild,
                             c->d_child_state, c->d_keys, c->d_vals, n0, M, p, c->rng_mode, c->seed64, step, c->invalid_key, (const DevScalars *)c->d_sc, c->d_mail, *cseq, c->pack, dev_n ? 1 : 0, oo, hb, spawn_fin, pp, (spawn_fin.on ? 1 : 0) + hq_blk + (pp.n_imp > 0 ? nblk(pp.n_imp, TPB / 64) : 0) + ((hb.kb || hb.kb_out) ? 1 : 0));
     else
-      SPAWN_LAUNCH(c->dev.hb.on, spawn_fuse, dim3(nblk(nfree) + (spawn_fin.on ? 1 : 0) + hq_blk + (pp.n_imp > 0 ? nblk(pp.n_imp, TPB / 64) : 0) + ((hb.kb || hb.kb_out) ? 1 : 0)), dim3(TPB), spawn_lds, st, c->dev, c->w, c->d_child_off, c->d_wchild, c->d_child_state, c->d_keys, c->d_vals,
+      SPAWN_LAUNCH(spawn_kind(c), spawn_fuse, dim3(nblk(nfree) + (spawn_fin.on ? 1 : 0) + hq_blk + (pp.n_imp > 0 ? nblk(pp.n_imp, TPB / 64) : 0) + ((hb.kb || hb.kb_out) ? 1 : 0)), dim3(TPB), spawn_lds, st, c->dev, c->w, c->d_child_off, c->d_wchild, c->d_child_state, c->d_keys, c->d_vals,
                          n0, M, p, c->rng_mode, c->seed64, step, c->invalid_key, (const DevScalars *)c->d_sc, c->d_mail, *cseq, c->pack, dev_n ? 1 : 0, oo, hb, spawn_fin, pp, (spawn_fin.on ? 1 : 0) + hq_blk + (pp.n_imp > 0 ? nblk(pp.n_imp, TPB / 64) : 0) + ((hb.kb || hb.kb_out) ? 1 : 0));
   } else if (s0) { hipEventRecord(s0, st); hipEventRecord(s1, st); }
   HIPCHK(hipEventRecord(c->e_spawned, st)); c->spawned_valid = true;
@@ -1356,6 +1366,7 @@ int sqmc_gpu_step(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double out[16]) {
   if (c->psit_on) {
     if (!sp->semistochastic) return fail(SQMC_ERR_BAD_ARG, "hf_to_psit needs a semistochastic step");
     if (c->dev.hb.on) return fail(SQMC_ERR_UNSUPPORTED, "hf_to_psit with proposal_method fast_heatbath is not built");
+    if (c->dev.cs.on) return fail(SQMC_ERR_UNSUPPORTED, "hf_to_psit with proposal_method CauchySchwarz is not built");
     p.koff = c->dev.ps.koff; p.nct = c->dev.ps.n_ct;
     if (c->nwalk < p.nct) return fail(SQMC_ERR_BAD_ARG, "hf_to_psit: the walker list does not hold the C(T) segment");
   }
@@ -1400,10 +1411,10 @@ int sqmc_gpu_step(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double out[16]) {
     cseq = ++c->cnt_seq;
     if (M > n0) {
       if (t_spawn >= 0)
-        SPAWN_LAUNCH_EXT(c->dev.hb.on, 0, dim3(nblk(M - n0)), dim3(TPB), 0, st, c->ev0[t_spawn], c->ev1[t_spawn], 0, c->dev, c->w, c->d_child_off, c->d_wchild,
+        SPAWN_LAUNCH_EXT(spawn_kind(c), 0, dim3(nblk(M - n0)), dim3(TPB), 0, st, c->ev0[t_spawn], c->ev1[t_spawn], 0, c->dev, c->w, c->d_child_off, c->d_wchild,
                               c->d_child_state, c->d_keys, c->d_vals, n0, M, p, mode, seed, step, c->invalid_key, (const DevScalars *)c->d_sc, c->d_mail, cseq, c->pack, 0, OwnerOut{nullptr, nullptr, 0, 0}, BucketArgs{}, FinArgs{}, PrjPre{}, 0);
       else
-        SPAWN_LAUNCH(c->dev.hb.on, 0, dim3(nblk(M - n0)), dim3(TPB), 0, st, c->dev, c->w, c->d_child_off, c->d_wchild, c->d_child_state, c->d_keys, c->d_vals,
+        SPAWN_LAUNCH(spawn_kind(c), 0, dim3(nblk(M - n0)), dim3(TPB), 0, st, c->dev, c->w, c->d_child_off, c->d_wchild, c->d_child_state, c->d_keys, c->d_vals,
                            n0, M, p, mode, seed, step, c->invalid_key, (const DevScalars *)c->d_sc, c->d_mail, cseq, c->pack, 0, OwnerOut{nullptr, nullptr, 0, 0}, BucketArgs{}, FinArgs{}, PrjPre{}, 0);
     } else if (t_spawn >= 0) { hipEventRecord(c->ev0[t_spawn], st); hipEventRecord(c->ev1[t_spawn], st); }
   } else {

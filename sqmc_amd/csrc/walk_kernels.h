@@ -83,8 +83,8 @@ __global__ void __launch_bounds__(TPB) k_gate(ChemDev dev, const u64 *__restrict
 
 // REPLAY discipline: one lane walks the walkers in order, consuming the single rannyu
 // stream exactly as the reference does, and records where every child starts in it.
-// (proposal_method fast_heatbath: the same walk with propose_heatbath -- how many draws a proposal takes depends on the tables and on the
-//  matrix elements it computes, so the lane runs the whole proposal, not just its control flow)
+// (proposal_method fast_heatbath / CauchySchwarz: the same walk with propose_heatbath / propose_cauchy_schwarz -- how many draws a proposal
+//  takes depends on the tables and on the values it computes, so the lane runs the whole proposal, not just its control flow)
 __global__ void __launch_bounds__(64) k_replay_prepass(const ChemTab *__restrict__ gtab, const u64 *__restrict__ up, const u64 *__restrict__ dn,
                                                        const double *__restrict__ wt, u64 *__restrict__ nchild, double *__restrict__ wchild,
                                                        u64 *__restrict__ child_off, u64 *__restrict__ child_state, long long n,
@@ -110,6 +110,7 @@ __global__ void __launch_bounds__(64) k_replay_prepass(const ChemTab *__restrict
     for (long long k = 0; k < nc; k++) {
       if ((long long)c < cap_children) child_state[c] = g.x;
       if (dev.hb.on) { u64 ju2[2], jd2[2]; double wj2[2]; propose_heatbath(t, dev.integrals, dev.hb, g, p.tau, iu, id, ju2, jd2, wj2); }
+      else if (dev.cs.on) { u64 ju, jd; double pr; propose_cauchy_schwarz(t, dev.cs, g, iu, id, ju, jd, pr); }
       else { u64 ju, jd; double pr; propose_any(t, g, iu, id, ju, jd, pr); }
       c++;
     }
@@ -299,10 +300,14 @@ extern "C" int sqmc_gpu_debug_prof(unsigned long long *out) { return (int)hipMem
 #define PROF(K)
 #endif
 // one thread per child proposal; parent found by binary search in the child offsets
-// HB: proposal_method fast_heatbath (two walker slots per child) -- a kernel of its own, so that the uniform proposal keeps its registers
+// PK: the proposal -- SPAWN_UNIFORM (uniform2 / HEG / Hubbard), SPAWN_HEATBATH (fast_heatbath, two walker slots per child),
+//     SPAWN_CAUCHY (CauchySchwarz, one slot) -- each a kernel of its own, so that the uniform proposal keeps its registers
 // FUSE: the short-list extras (children grouped by key range for the bucket tail, the block with the final sums, the projector rows);
 //       large populations run FUSE = 0, whose register and LDS budget is the plain spawn's (7 waves per SIMD)
-template <int HB, int FUSE>
+#define SPAWN_UNIFORM 0
+#define SPAWN_HEATBATH 1
+#define SPAWN_CAUCHY 2
+template <int PK, int FUSE>
 __global__ void __launch_bounds__(TPB) k_spawn(ChemDev dev, WalkArr w, const u64 *__restrict__ child_off, const double *__restrict__ wchild,
                                                const u64 *__restrict__ child_state, u64 *__restrict__ keys, u32 *__restrict__ vals,
                                                long long n0_arg, long long cap_all, StepP p, int mode, u64 seed, u64 step, u64 invalid_key, const DevScalars *sc,
@@ -388,7 +393,7 @@ __global__ void __launch_bounds__(TPB) k_spawn(ChemDev dev, WalkArr w, const u64
   if (mail && bx == 0 && threadIdx.x == 0) {      // the host sizes the sort from this while the kernel runs
     mail->n_children = (u64)nchildren; __threadfence_system(); mail->cnt_seq = cnt_seq;
   }
-  const long long spc = HB ? 2 : 1;             // walker slots per child: the heat-bath proposal may return a single AND a double
+  const long long spc = (PK == SPAWN_HEATBATH) ? 2 : 1;      // walker slots per child: the heat-bath proposal may return a single AND a double
   if (c0 >= nchildren || n0 + spc * nchildren > cap_all) return;
   const bool part = FUSE && ba.B > 0 && (int)bx < ba.nsb;                  // rows beyond the room the host provided: the tail will see that and use its own partition
   if (part) bucket_partition_stage(s_spl, s_wcnt, pws, keys, n0, ba);     // resident keys [0, n0) of the same array the children's keys go to; a barrier follows below
@@ -430,13 +435,13 @@ __global__ void __launch_bounds__(TPB) k_spawn(ChemDev dev, WalkArr w, const u64
     const u32 pflg = w.flg[ip]; const double wch = wchild[ip];     // needed at the end: fetched in the same round trip
     u64 ju, jd; double prob;
     PROF(3);
-    if (HB) {                    // proposal_method fast_heatbath: both slots of the child are written (weight 0: no walker), do_walk.f90:3604-3611
+    if (PK == SPAWN_HEATBATH) {  // proposal_method fast_heatbath: both slots of the child are written (weight 0: no walker), do_walk.f90:3604-3611
       u64 ju2[2], jd2[2]; double wj2[2];
       propose_heatbath(t, dev.integrals, dev.hb, g, p.tau, iu, id, ju2, jd2, wj2);
       spawn_emit(dev, w, keys, vals, n0, 2 * c, pflg, ju2[0], jd2[0], wch * wj2[0], p, invalid_key, pack, oo);
       spawn_emit(dev, w, keys, vals, n0, 2 * c + 1, pflg, ju2[1], jd2[1], wch * wj2[1], p, invalid_key, pack, oo);
     } else {
-    const int level = propose_any(t, g, iu, id, ju, jd, prob);
+    const int level = (PK == SPAWN_CAUCHY) ? propose_cauchy_schwarz(t, dev.cs, g, iu, id, ju, jd, prob) : propose_any(t, g, iu, id, ju, jd, prob);
     PROF(4);
     double wj = 0.0;
     if (level > 0) {

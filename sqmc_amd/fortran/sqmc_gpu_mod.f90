@@ -19,6 +19,7 @@ module sqmc_gpu_mod
   public :: sqmc_gpu_comm_unique_id, sqmc_gpu_comm_init, sqmc_gpu_comm_size, sqmc_gpu_set_owner_hash, sqmc_gpu_tail_stats, sqmc_gpu_slowest_steps, sqmc_gpu_set_chained_runs, sqmc_gpu_hci_pt2, sqmc_gpu_hci_set_active_space, sqmc_gpu_set_heatbath_tables, sqmc_gpu_propose_heatbath_batch, sqmc_heatbath_tables, sqmc_gpu_shard_step, sqmc_gpu_shard_run, sqmc_gpu_shard_time_split, sqmc_gpu_davidson
   public :: sqmc_gpu_set_hf_to_psit, sqmc_gpu_setup_efficient_heatbath, sqmc_gpu_get_heatbath_tables
   public :: sqmc_gpu_set_hf_to_psit_shard, sqmc_gpu_shard_finish_psit
+  public :: sqmc_gpu_setup_cauchy_schwarz, sqmc_gpu_propose_cauchy_schwarz_batch
   public :: sqmc_gpu_check
 
   integer(c_int), parameter, public :: SQMC_RNG_REPLAY = 0, SQMC_RNG_COUNTER = 1
@@ -142,6 +143,16 @@ module sqmc_gpu_mod
     end function
     integer(c_int) function sqmc_gpu_propose_heatbath_batch(ctx, n, tau, up, dn, seeds, det_j_up, det_j_dn, weight_j, seeds_after) &
         bind(C, name='sqmc_gpu_propose_heatbath_batch')
+      import; type(c_ptr), value :: ctx; integer(c_int64_t), value :: n; real(c_double), value :: tau
+      integer(c_int64_t), intent(in) :: up(*), dn(*); integer(c_int32_t), intent(in) :: seeds(*)
+      integer(c_int64_t), intent(out) :: det_j_up(*), det_j_dn(*); real(c_double), intent(out) :: weight_j(*); integer(c_int32_t), intent(out) :: seeds_after(*)
+    end function
+    ! proposal_method 'CauchySchwarz': setup_orb_by_symm's tables (chemistry.f90:2505-2523), before any H-dependent state
+    integer(c_int) function sqmc_gpu_setup_cauchy_schwarz(ctx, n_clamped) bind(C, name='sqmc_gpu_setup_cauchy_schwarz')
+      import; type(c_ptr), value :: ctx; integer(c_int32_t), intent(out) :: n_clamped
+    end function
+    integer(c_int) function sqmc_gpu_propose_cauchy_schwarz_batch(ctx, n, tau, up, dn, seeds, det_j_up, det_j_dn, weight_j, seeds_after) &
+        bind(C, name='sqmc_gpu_propose_cauchy_schwarz_batch')
       import; type(c_ptr), value :: ctx; integer(c_int64_t), value :: n; real(c_double), value :: tau
       integer(c_int64_t), intent(in) :: up(*), dn(*); integer(c_int32_t), intent(in) :: seeds(*)
       integer(c_int64_t), intent(out) :: det_j_up(*), det_j_dn(*); real(c_double), intent(out) :: weight_j(*); integer(c_int32_t), intent(out) :: seeds_after(*)

@@ -207,9 +207,44 @@ class ChemHost:
         c2[n1, n1] = (n1 * n) // 2 + n1
         self.combine_2 = c2
 
-    def gpu(self, **kw):
-        return GpuChem(self.norb, self.nup, self.ndn, self.orbsym, self.prod.reshape(-1), self.combine_2.reshape(-1), self.integrals,
-                       n_group=self.n_group, time_sym=self.time_sym, z=self.z, n_core_orb=self.n_core_orb, **kw)
+    def gpu(self, proposal="uniform", **kw):
+        """a context for this molecule.  proposal="cauchyschwarz": proposal_method CauchySchwarz -- the exchange integrals are
+        checked and clamped here first (cauchy_schwarz_clamp), so that the host's tables and the context's agree, then the
+        library builds its tables before anything built from H exists (sqmc_gpu_setup_cauchy_schwarz)."""
+        if proposal not in ("uniform", "cauchyschwarz"):
+            raise ValueError("ChemHost.gpu: proposal %r (uniform or cauchyschwarz; fast heat-bath is set up on the context)" % (proposal,))
+        if proposal == "cauchyschwarz":
+            if self.time_sym:
+                raise ValueError("the Cauchy-Schwarz proposal with time_sym = .true. is not built")
+            self.cauchy_schwarz_clamp()
+        g = GpuChem(self.norb, self.nup, self.ndn, self.orbsym, self.prod.reshape(-1), self.combine_2.reshape(-1), self.integrals,
+                    n_group=self.n_group, time_sym=self.time_sym, z=self.z, n_core_orb=self.n_core_orb, **kw)
+        if proposal == "cauchyschwarz":
+            try:
+                g.setup_cauchy_schwarz()
+            except Exception:
+                g.close()
+                raise
+        return g
+
+    def cauchy_schwarz_clamp(self):
+        """setup_orb_by_symm with proposal_method CauchySchwarz (chemistry.f90:2508-2523) on this host's integrals: stop on an
+        exchange integral (ij|ij) below the default-real literal -1e-6, overwrite the slightly negative ones with 0.  Returns how
+        many were clamped; a clamp drops the HCI tables built from the old values."""
+        n1 = self.norb + 1
+        i, j = np.meshgrid(np.arange(1, n1), np.arange(1, n1), indexing="ij")
+        a = self.combine_2[i, j].astype(np.int64)
+        ix = np.unique((a * (a - 1)) // 2 + a)
+        v = self.integrals[ix]
+        if np.any(v < float(np.float32(-1e-6))):
+            raise ValueError("Negative integrals!")
+        neg = ix[v < 0]
+        if len(neg):
+            self.integrals[neg] = 0.0
+            if hasattr(self, "hb"):
+                del self.hb
+        self.n_cs_clamped = int(len(neg))
+        return self.n_cs_clamped
 
     def connected_all(self, up, dn):
         """Every symmetry-allowed single and double excitation of one determinant plus itself, sorted
@@ -573,7 +608,9 @@ class GpuWalk:
         self.host = host
         w_begin = w_begin if w_begin is not None else w_target
         mwalk = mwalk or int(max(4 * (w_target / min_wt + size_deterministic), 200000))
-        self.g = host.gpu(rng_mode=rng_mode, seed=seed, mwalk=mwalk)
+        if proposal == "cauchyschwarz" and hf_to_psit:
+            raise ValueError("proposal_method CauchySchwarz with hf_to_psit = t is not built")
+        self.g = host.gpu(rng_mode=rng_mode, seed=seed, mwalk=mwalk, **({"proposal": proposal} if proposal == "cauchyschwarz" else {}))
         if proposal == "heatbath":          # proposal_method fast_heatbath: the library builds the tables and refuses what the reference refuses
             if not self.g.setup_efficient_heatbath():
                 self.g.close()
@@ -759,17 +796,23 @@ class ShardedWalk:
 
     def __init__(self, host, w_target, rank, world, w_begin=None, mwalk=None, n_truncate_trial_wf=100, size_deterministic=1000,
                  tau_multiplier=0.1, e_trial=None, seed=(1346, 5634, 6635, 4361), min_wt=0.5, device_index=0, n_equil_steps=10**9, owner_hash=0,
-                 semistochastic=True, hf_to_psit=False, sum_order=1):
+                 semistochastic=True, hf_to_psit=False, sum_order=1, proposal="uniform"):
+        """proposal: "uniform" (the system's own) or "cauchyschwarz" (chem: proposal_method CauchySchwarz)"""
         import torch
         self.rank, self.world, self.min_wt = rank, world, min_wt
         self.psit = bool(hf_to_psit)
+        if proposal not in ("uniform", "cauchyschwarz"):
+            raise ValueError("ShardedWalk: proposal %r (uniform or cauchyschwarz)" % (proposal,))
+        if proposal == "cauchyschwarz" and self.psit:
+            raise ValueError("proposal_method CauchySchwarz with hf_to_psit = t is not built")
+        pkw = {"proposal": proposal} if proposal != "uniform" else {}
         if self.psit and not semistochastic:
             raise ValueError("hf_to_psit needs a semistochastic walk")
         self.semi = 1 if semistochastic else 0          # 0: semistochastic = f, no deterministic space; join_walker2 is local to a rank (do_walk.f90:2475)
         w_begin = w_begin if w_begin is not None else w_target
         per_rank = w_target / world
         mwalk = mwalk or int(max(6 * (per_rank / min_wt + size_deterministic), 200000))
-        self.g = g = host.gpu(rng_mode=RNG_COUNTER, seed=rank_seed(seed, rank), mwalk=mwalk)
+        self.g = g = host.gpu(rng_mode=RNG_COUNTER, seed=rank_seed(seed, rank), mwalk=mwalk, **pkw)
         if owner_hash:
             g.set_owner_hash(owner_hash)       # 1: the reference's get_det_owner (djb_hash), mpi_routines.f90:354-445
         if self.psit:
@@ -930,7 +973,9 @@ class HegHost:
         self.k_rel = np.rint(self.k_vectors * L / (2 * pi)).astype(np.int64)
         self.hf_up, self.hf_dn = (1 << nup) - 1, (1 << self.ndn) - 1
 
-    def gpu(self, **kw):
+    def gpu(self, proposal="uniform", **kw):
+        if proposal != "uniform":
+            raise ValueError("the heg context has the one proposal of its system (Cauchy-Schwarz is chemistry only)")
         return GpuChem.heg(self.n_dim, self.norb, self.nup, self.ndn, self.length_cell, self.k_vectors, **kw)
 
     def madelung_energy(self):
@@ -1073,7 +1118,9 @@ class HubbardHost:
                 ok = y2 != y1
         return (y2 - 1) * lx + x2 if ok else 0
 
-    def gpu(self, **kw):
+    def gpu(self, proposal="uniform", **kw):
+        if proposal != "uniform":
+            raise ValueError("the hubbard context has the one proposal of its system (Cauchy-Schwarz is chemistry only)")
         return GpuChem.hubbard(self.l_x, self.l_y, self.pbc, self.nup, self.ndn, self.t, self.U, **kw)
 
     def connected(self, up, dn):

@@ -9,7 +9,7 @@ per-block line, `Energy=`).  Every step runs inside libsqmc_gpu (sqmc_gpu_run, o
 block); this module only parses, schedules blocks and does the statistics.
 
 Not every deck is a GPU deck: the proposal must be `uniform2` (the one the reference itself uses
-for C2, SURVEY finding 4), importance_sampling 0, hf_to_psit f, and the trial wavefunction /
+for C2, SURVEY finding 4), or for chem `fast_heatbath` or `CauchySchwarz`, importance_sampling 0, hf_to_psit f, and the trial wavefunction /
 deterministic space come from ONE connect-diagonalise-truncate pass (diff_from_psi_t f with
 size_deterministic; trial_wf_iterations <= 1).  Anything else stops with a message naming the line."""
 import math
@@ -20,6 +20,9 @@ import time
 import numpy as np
 
 from .run import _logical, _numbers
+
+
+_PROPOSAL_NAME = {"cauchyschwarz": "CauchySchwarz"}          # the deck's spelling, echoed on the proposal line
 
 
 def parse_walk_deck(text):
@@ -78,10 +81,15 @@ def parse_walk_deck(text):
         a = _numbers(nxt(), 2); d.update(nup=int(a[0]), ndn=int(a[1]))
     else:
         raise SystemExit("sqmc_amd.walk_run: hamiltonian_type %r has no GPU operator (chem, heg, hubbard2)" % d["hamiltonian_type"])
-    if d["proposal_method"] not in ("uniform2", "uniform") and not (d["proposal_method"] == "fast_heatbath" and d["hamiltonian_type"] == "chem"):
-        raise SystemExit("sqmc_amd.walk_run: proposal_method %r is not on the GPU path (uniform2: off_diagonal_move_chem / _heg / _hubbard; fast_heatbath: chem)" % d["proposal_method"])
+    if d["proposal_method"] not in ("uniform2", "uniform") and not (d["proposal_method"] in ("fast_heatbath", "cauchyschwarz") and d["hamiltonian_type"] == "chem"):
+        raise SystemExit("sqmc_amd.walk_run: proposal_method %r is not on the GPU path (uniform2: off_diagonal_move_chem / _heg / _hubbard; "
+                         "fast_heatbath, CauchySchwarz: chem)" % d["proposal_method"])
     if d["proposal_method"] == "fast_heatbath" and d["hf_to_psit"]:
         raise SystemExit("sqmc_amd.walk_run: proposal_method fast_heatbath with hf_to_psit = t is not built")
+    if d["proposal_method"] == "cauchyschwarz" and d["hf_to_psit"]:
+        raise SystemExit("sqmc_amd.walk_run: proposal_method CauchySchwarz with hf_to_psit = t is not built")
+    if d["proposal_method"] == "cauchyschwarz" and d["time_sym"]:
+        raise SystemExit("sqmc_amd.walk_run: proposal_method CauchySchwarz with time_sym = t is not built")
     if d["importance_sampling"] != 0:
         raise SystemExit("sqmc_amd.walk_run: importance_sampling must be 0")
     if d["hf_to_psit"] and d["hamiltonian_type"] == "hubbard2":
@@ -210,13 +218,23 @@ def run_walk(deck, fcidump="FCIDUMP", out=sys.stdout, walkalize=None, max_equil_
     p("tau_multiplier, tau=%13.8f%13.8f" % (d["tau_multiplier"], d["tau"]))
     p("population_control_exponent, e_trial_initial, min_wt=%11.5f%11.5f%6.2f" % (d["population_control_exponent"], d["e_trial_initial"], d["min_wt"]))
     p("proposal_method, importance_sampling, r_initiator, initiator_power, initiator_min_distance, initiator_rescale_power= %s%3d%6.2f%3d%3d%6.3f"
-      % (d["proposal_method"], 0, d["r_initiator"], d["initiator_power"], 0, d["initiator_rescale_power"]))
+      % (_PROPOSAL_NAME.get(d["proposal_method"], d["proposal_method"]), 0, d["r_initiator"], d["initiator_power"], 0, d["initiator_rescale_power"]))
     p("\nsemistochastic run" if semi else "\nnot semistochastic run")
     target = d["w_abs_gen_target"]
     mwalk = int(max(d["mwalk"], 4 * (target / d["min_wt"] + d["size_deterministic"])))      # do_walk.f90:665, 856
     psit = bool(d["hf_to_psit"]) and semi
     p(" Replacing HF state with trial wave function" if psit else " NOT replacing HF state with trial wave function")      # do_walk.f90:383-387
-    g = hst.gpu(rng_mode=H.RNG_COUNTER, seed=tuple(d["irand_seed"][1]), mwalk=mwalk)
+    gkw = {}
+    if d["proposal_method"] == "cauchyschwarz":
+        # setup_orb_by_symm (chemistry.f90:2505-2523) runs in system_setup_chem, before anything is built from H
+        try:
+            ncl = hst.cauchy_schwarz_clamp()
+        except ValueError:
+            p(" Negative integrals!")
+            raise SystemExit("Negative integrals!")
+        p(" CauchySchwarz: %d exchange integrals (ij|ij) slightly below 0 set to 0" % ncl)
+        gkw["proposal"] = "cauchyschwarz"
+    g = hst.gpu(rng_mode=H.RNG_COUNTER, seed=tuple(d["irand_seed"][1]), mwalk=mwalk, **gkw)
     t0 = time.perf_counter()
     # the trial wave function is rediagonalised among its own determinants, as generate_space_iterate leaves it (semistoch.f90:575, 706-712)
     s = hst.setup_walk(g, rediagonalize=True, **skw) if d["hamiltonian_type"] != "hubbard2" else hst.setup_walk(g, **skw)
