@@ -56,7 +56,7 @@ typedef struct sqmc_gpu_ctx sqmc_gpu_ctx;
  * (chemistry.f90:299-537, 538-869, 2461-2527) and keeps in module chemistry. */
 typedef struct {
   int32_t norb, nup, ndn, n_core_orb;
-  int32_t time_sym, z;              /* chemistry.f90:163-181 (walk kernels need time_sym=0) */
+  int32_t time_sym, z;              /* chemistry.f90:163-181; walks are over representatives */
   int32_t n_group;                  /* order of the abelian point group (<= 8)             */
   const int32_t *product_table;     /* [9*9], 1-based: product_table(i,j) at [i*9+j]       */
   const int32_t *orbital_symmetries;/* [norb+1], 1-based, after orbital reordering         */
@@ -146,7 +146,7 @@ int sqmc_gpu_get_heatbath_tables(sqmc_gpu_ctx *ctx, sqmc_heatbath_tables *t, int
 int sqmc_gpu_propose_heatbath_batch(sqmc_gpu_ctx *ctx, int64_t n, double tau, const uint64_t *up, const uint64_t *dn, const int32_t *seeds,
                                     uint64_t *det_j_up, uint64_t *det_j_dn, double *weight_j, int32_t *seeds_after);
 
-/* proposal_method 'CauchySchwarz' (chem only, time_sym = 0).
+/* proposal_method 'CauchySchwarz' (chem only; time_sym = 0 or 1, z = +-1).
  * replaces: setup_orb_by_symm's CauchySchwarz block (chemistry.f90:2505-2523): sqrt_integrals(i,j) = sqrt((ij|ij)), cs_sqrt_orb and
  * sym_sum_cs_sqrt, built from the context's integrals in the reference's loop order.  Like the reference it stops on an exchange
  * integral below -1e-6 (a default-real literal: -9.999999974752427e-07) -- SQMC_ERR_BAD_ARG, last error "Negative integrals!", nothing
@@ -156,11 +156,14 @@ int sqmc_gpu_propose_heatbath_batch(sqmc_gpu_ctx *ctx, int64_t n, double tau, co
  * on one context (the second set-up fails with SQMC_ERR_BAD_ARG, the first stays).  After this call sqmc_gpu_step / _run and the sharded
  * steps spawn with off_diagonal_move_chem_cauchySchwarz (2530-4233, do_walk.f90:3613-3614, 3937-3938), one walker slot per child,
  * both RNG disciplines; the intrinsic random_number draws of the reference come from the walk's own stream
- * (tests/golden/README_cauchyschwarz.md).  hf_to_psit with this proposal is refused (SQMC_ERR_UNSUPPORTED). */
+ * (tests/golden/README_cauchyschwarz.md).  With time_sym the move ends as 4093-4162 do: the second pathway through the time-reversed
+ * det_j from the Cauchy-Schwarz arm of is_connected_chem (tests/golden/README_cauchyschwarz_time_sym.md) and det_j replaced by its
+ * representative (up <= dn).  hf_to_psit with this proposal is refused (SQMC_ERR_UNSUPPORTED). */
 int sqmc_gpu_setup_cauchy_schwarz(sqmc_gpu_ctx *ctx, int32_t *n_clamped);
 /* n proposals of off_diagonal_move_chem_cauchySchwarz (chemistry.f90:2530-4233), each from its own rannyu state seeds[4 i .. 4 i + 3]
  * (test door, like sqmc_gpu_propose_batch): det_j and weight_j = -tau H_ij / proposal_prob (4204); weight 0 and det_j = det_i where
- * the reference returns early or a cumulative search falls through. */
+ * the reference returns early or a cumulative search falls through.  With time_sym, det_j is the representative and weight_j the
+ * combined weight of both pathways (4093-4162). */
 int sqmc_gpu_propose_cauchy_schwarz_batch(sqmc_gpu_ctx *ctx, int64_t n, double tau, const uint64_t *up, const uint64_t *dn, const int32_t *seeds,
                                           uint64_t *det_j_up, uint64_t *det_j_dn, double *weight_j, int32_t *seeds_after);
 

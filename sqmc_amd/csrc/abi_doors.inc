@@ -286,7 +286,6 @@ int sqmc_gpu_setup_cauchy_schwarz(sqmc_gpu_ctx *c, int32_t *n_clamped) {
   abandon_head(c);
   if (!c) return fail(SQMC_ERR_BAD_ARG, "null ctx");
   if (c->htab.sys_type != 0) return fail(SQMC_ERR_UNSUPPORTED, "the Cauchy-Schwarz proposal is a 'chem' proposal");
-  if (c->htab.time_sym) return fail(SQMC_ERR_UNSUPPORTED, "the Cauchy-Schwarz proposal with time_sym = .true. is not built");
   if (c->dev.hb.on) return fail(SQMC_ERR_BAD_ARG, "the context already proposes by fast heat-bath");
   // the tables may change integrals that H depends on: nothing built from them may exist yet (system_setup_chem order)
   if (c->n_imp > 0 || c->d_prj_ptr || c->d_ct_up || c->psit_on || c->nwalk > 0 || c->d_hb_r)

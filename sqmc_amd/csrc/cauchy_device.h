@@ -37,6 +37,10 @@ __device__ __forceinline__ double cs_pair_sum(const double *__restrict__ sq, int
   for (u64 b = bits; b; b &= b - 1) { const int x = ctz64(b) + 1; acc = acc + CS_SQ(o2, x) + CS_SQ(o1, x); }
   return acc;
 }
+// sym_sum_cs_sqrt(sym, o2) + sym_sum_cs_sqrt(sym, o1): the first two terms of every second-hole denominator
+__device__ __forceinline__ double ssum_pair(const double *__restrict__ ssum, int n, int s, int o1, int o2) {
+  return ssum[(size_t)(s - 1) * n + (o2 - 1)] + ssum[(size_t)(s - 1) * n + (o1 - 1)];
+}
 // second hole: cumulative search over the open orbitals `open` ascending with weight (sqrt(o2,x)+sqrt(o1,x))/den; 0 = fell through
 __device__ __forceinline__ int cs_pick_second(const double *__restrict__ sq, int n, int o1, int o2, u64 open, double den, double r) {
   double ep = 0.0;
@@ -208,3 +212,139 @@ __device__ inline int propose_cauchy_schwarz(const ChemTab &t, const CsDev &cs, 
   return 2;
 }
 #undef CS_SQ
+
+// ---------------------------------------------------------------------------------------------------- time-reversal symmetry
+// The Cauchy-Schwarz arm of is_connected_chem (chemistry.f90:2203-2450; singles: the uniform formula, 2131-2152) for det_i -> target:
+// the excitation level and the probability of the move reaching the target, without the n_single / n_total or n_double / n_total
+// factor.  As the product means it (tests/golden/README_cauchyschwarz_time_sym.md): the move tables are det_i's own, computed here
+// (the reference reads module state the move fills only on its double branch, item 2), and the up-up second path sums with `+`
+// (2288 has `-`, item 1).  Operation order otherwise that of the text.  Draws nothing.
+#define CS_SQ(i, j) sq[(size_t)((i) - 1) * n + ((j) - 1)]
+#define CS_SYM(s, o) ssum[(size_t)((s) - 1) * n + ((o) - 1)]
+__device__ inline bool cs_is_connected_prob(const ChemTab &t, const CsDev &cs, u64 iu, u64 id, u64 ju, u64 jd, int &level, double &prob) {
+  const double *__restrict__ sq = cs.sq;
+  const double *__restrict__ orb = cs.orb;
+  const double *__restrict__ ssum = cs.sym;
+  const int n = t.norb;
+  int upc = 0, dnc = 0, du1 = 0, du2 = 0, du3 = 0, du4 = 0, dd1 = 0, dd2 = 0, dd3 = 0, dd4 = 0;
+  level = -1; prob = 0.0;
+  if (iu != ju) {
+    const u64 a = iu & ~ju, b = ju & ~iu;
+    upc = popc64(a);
+    if (upc > 2 || upc != popc64(b)) return false;
+    du1 = ctz64(a) + 1; du3 = ctz64(b) + 1;
+    if (upc == 2) { du2 = ctz64(a & (a - 1)) + 1; du4 = ctz64(b & (b - 1)) + 1; }
+  }
+  if (id != jd) {
+    const u64 a = id & ~jd, b = jd & ~id;
+    dnc = popc64(a);
+    if (dnc > 2 || dnc != popc64(b)) return false;
+    dd1 = ctz64(a) + 1; dd3 = ctz64(b) + 1;
+    if (dnc == 2) { dd2 = ctz64(a & (a - 1)) + 1; dd4 = ctz64(b & (b - 1)) + 1; }
+  }
+  level = upc + dnc;
+  if (level > 2) { level = -1; return false; }
+  const int ne = t.nelec - 2 * t.ncore;
+  if (level == 1) {
+    u64 det = id; int d1 = dd1, d2 = dd3;
+    if (upc == 1) { det = iu; d1 = du1; d2 = du3; }
+    const int sym1 = t.orbsym[d1];
+    if (sym1 != t.orbsym[d2]) return false;
+    const int i_open = popc64(t.sym_mask[sym1] & ~det);
+    prob = 1.0 / ((ne) * (i_open));
+    return true;
+  }
+  if (level != 2) return true;
+  int o1, o2, k, l;
+  if (upc == 2) { o1 = du1; o2 = du2; k = du3; l = du4; }
+  else if (dnc == 2) { o1 = dd1; o2 = dd2; k = dd3; l = dd4; }
+  else { o1 = du1; o2 = dd1; k = du3; l = dd3; }
+  if (t.prod[t.orbsym[o1]][t.orbsym[o2]] != t.prod[t.orbsym[k]][t.orbsym[l]]) return false;
+  // sum_cs_sqrt_prime of det_i (2729-2737): active up electrons, then active dn electrons
+  u64 au = iu, ad = id;
+  for (int q = 0; q < t.ncore; q++) { au &= au - 1; ad &= ad - 1; }
+  double s = 0.0;
+  for (u64 b = au; b; b &= b - 1) s = s + cs_prime_spin(sq, orb, n, ctz64(b) + 1, iu, id);
+  for (u64 b = ad; b; b &= b - 1) s = s + cs_prime_spin(sq, orb, n, ctz64(b) + 1, iu, id);
+  const double c1 = cs_prime_spin(sq, orb, n, o1, iu, id), c2 = cs_prime_spin(sq, orb, n, o2, iu, id);
+  const double pp = (c1 / s * c2 / (s - c1) + c2 / s * c1 / (s - c2));
+  double tmp;
+  if (upc == 2 || dnc == 2) {
+    // both electrons of one spin (2220-2375); i_open is never 0 (l, and k, are open), the tests are the text's
+    const u64 own = (upc == 2) ? iu : id;
+    int sym1 = t.orbsym[l];
+    int i_open = popc64(t.sym_mask[sym1] & ~own) - (sym1 == t.orbsym[k] ? 1 : 0);
+    if (i_open == 0) return true;
+    double den = ssum_pair(ssum, n, sym1, o1, o2) - cs_pair_sum(sq, n, o1, o2, t.sym_mask[sym1] & own);
+    if (sym1 == t.orbsym[k]) den = den - CS_SQ(o2, k) - CS_SQ(o1, k);
+    const double den1 = cs_prime(sq, orb, n, o1, own) + cs_prime(sq, orb, n, o2, own);
+    tmp = (CS_SQ(o1, k) + CS_SQ(o2, k)) / den1 * (CS_SQ(o2, l) + CS_SQ(o1, l)) / den;
+    sym1 = t.orbsym[k];
+    i_open = popc64(t.sym_mask[sym1] & ~own) - (sym1 == t.orbsym[l] ? 1 : 0);
+    if (i_open != 0) {
+      if (sym1 == t.orbsym[l]) den = den + CS_SQ(o2, k) - CS_SQ(o2, l) + CS_SQ(o1, k) - CS_SQ(o1, l);
+      else den = ssum_pair(ssum, n, sym1, o1, o2) - cs_pair_sum(sq, n, o1, o2, t.sym_mask[sym1] & own);
+      tmp = tmp + (CS_SQ(o1, l) + CS_SQ(o2, l)) / den1 * (CS_SQ(o2, k) + CS_SQ(o1, k)) / den;
+    }
+  } else {
+    // one up and one dn electron (2376-2444)
+    int sym1 = t.orbsym[l];
+    if (popc64(t.sym_mask[sym1] & ~id) == 0) return true;
+    double den = ssum_pair(ssum, n, sym1, o1, o2) - cs_pair_sum(sq, n, o1, o2, t.sym_mask[sym1] & id);
+    const double den1 = c1 + c2;
+    tmp = (CS_SQ(o1, k) + CS_SQ(o2, k)) / den1 * (CS_SQ(o2, l) + CS_SQ(o1, l)) / den;
+    sym1 = t.orbsym[k];
+    if (popc64(t.sym_mask[sym1] & ~iu) != 0) {
+      den = ssum_pair(ssum, n, sym1, o1, o2) - cs_pair_sum(sq, n, o1, o2, t.sym_mask[sym1] & iu);
+      tmp = tmp + (CS_SQ(o1, l) + CS_SQ(o2, l)) / den1 * (CS_SQ(o2, k) + CS_SQ(o1, k)) / den;
+    }
+  }
+  prob = pp * tmp;
+  return true;
+}
+#undef CS_SYM
+#undef CS_SQ
+
+// weight_j of a Cauchy-Schwarz proposal det_i -> det_j (level, prob).  time_sym: the end of off_diagonal_move_chem_cauchySchwarz
+// (4093-4162) -- proposal_weight's time-symmetric branch, but for det_j with up == dn (z = 1) the probability and norm_j are
+// rescaled by the arm's value for det_j itself (4098-4108) -- the second pathway through flip(det_j) from cs_is_connected_prob, and
+// det_j replaced by its representative.  The walk runs it in a kernel of its own (SPAWN_CAUCHY_TS): inlined there, out of the plain
+// Cauchy-Schwarz kernel.
+__device__ inline double cs_time_sym_weight(const ChemTab &t, const CsDev &cs, const double *__restrict__ ints, double tau, u64 iu, u64 id, u64 &ju,
+                                                  u64 &jd, int level, double prob) {
+  const double sqrt2 = sqrt(2.0);
+  const double norm_i = (iu == id) ? sqrt2 : 1.0;
+  if ((ju == iu && jd == id) || (jd == iu && ju == id)) return 0.0;
+  const int nup = t.nup, ndn = t.ndn, norb = t.norb, nc = t.ncore;
+  const int n_single = (nup - nc) * (norb - nup) + (ndn - nc) * (norb - ndn);
+  const int n_double = (nup - nc) * (nup - nc - 1) * (norb - nup) * (norb - nup - 1) / 4 + (ndn - nc) * (ndn - nc - 1) * (norb - ndn) * (norb - ndn - 1) / 4
+                     + (nup - nc) * (norb - nup) * (ndn - nc) * (norb - ndn);
+  const int n_total = n_single + n_double;
+  int lsym; double psym;
+  double me;
+  if (ju == jd) {
+    if (t.z != 1) return 0.0;
+    cs_is_connected_prob(t, cs, iu, id, jd, ju, lsym, psym);
+    double norm_j = 1 / prob;
+    if (lsym == 1) prob = (prob + psym * (n_single / (double)n_total)) / 2;
+    else prob = (prob + psym * (n_double / (double)n_total)) / 2;
+    norm_j = 2 * norm_j / sqrt2 * (prob);
+    me = h_level(t, ints, iu, id, ju, jd, level);
+    me = (norm_j / norm_i) * me;
+  } else {
+    const double m1 = h_level(t, ints, iu, id, ju, jd, level);
+    if (cs_is_connected_prob(t, cs, iu, id, jd, ju, lsym, psym)) {
+      const double m2 = h_level(t, ints, iu, id, jd, ju, lsym);
+      if (lsym == 1) prob = prob + (psym * (n_single / (double)n_total));
+      if (lsym == 2) prob = prob + (psym * (n_double / (double)n_total));
+      me = (1.0 / norm_i) * (m1 + t.z * m2);
+    } else me = (1.0 / norm_i) * (m1);
+  }
+  if (ju > jd) { const u64 x = ju; ju = jd; jd = x; me = me * t.z; }
+  return -tau * me / prob;
+}
+__device__ __forceinline__ double cs_proposal_weight(const ChemTab &t, const CsDev &cs, const double *__restrict__ ints, double tau, u64 iu, u64 id, u64 &ju,
+                                                     u64 &jd, int level, double prob) {
+  if (!t.time_sym) return -tau * h_level(t, ints, iu, id, ju, jd, level) / prob;
+  return cs_time_sym_weight(t, cs, ints, tau, iu, id, ju, jd, level, prob);
+}

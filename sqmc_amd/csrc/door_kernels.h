@@ -103,7 +103,7 @@ __global__ void __launch_bounds__(TPB) k_propose_cauchy_batch(ChemDev dev, const
   u64 a, b; double prob;
   const int level = propose_cauchy_schwarz(t, dev.cs, g, up[i], dn[i], a, b, prob);
   double w = 0.0;
-  if (level > 0) w = proposal_weight(t, dev.integrals, tau, up[i], dn[i], a, b, level, prob);
+  if (level > 0) w = cs_proposal_weight(t, dev.cs, dev.integrals, tau, up[i], dn[i], a, b, level, prob);
   ju[i] = a; jd[i] = b; wj[i] = w; state_out[i] = g.x;
 }
 __global__ void __launch_bounds__(TPB) k_propose_batch(ChemDev dev, const u64 *up, const u64 *dn, const u64 *state_in, u64 *ju, u64 *jd,

@@ -247,13 +247,18 @@ static int psit_shard_tinv(sqmc_gpu_ctx *c, const double *ps_raw);              
 
 #include "walk_kernels.h"
 #include "psit_kernels.h"
-// PK_: spawn_kind(c).  Heat-bath and Cauchy-Schwarz have one instantiation each (FUSE = 1 with no spare blocks and no partition is the plain spawn)
-static inline int spawn_kind(const sqmc_gpu_ctx *c) { return c->dev.hb.on ? SPAWN_HEATBATH : (c->dev.cs.on ? SPAWN_CAUCHY : SPAWN_UNIFORM); }
+// PK_: spawn_kind(c).  Heat-bath and Cauchy-Schwarz (without and with time_sym) have one instantiation each (FUSE = 1 with no spare blocks
+// and no partition is the plain spawn)
+static inline int spawn_kind(const sqmc_gpu_ctx *c) {
+  return c->dev.hb.on ? SPAWN_HEATBATH : (c->dev.cs.on ? (c->htab.time_sym ? SPAWN_CAUCHY_TS : SPAWN_CAUCHY) : SPAWN_UNIFORM);
+}
 #define SPAWN_LAUNCH(PK_, FUSE_, ...) do { const int pk_ = (PK_); if (pk_ == SPAWN_HEATBATH) hipLaunchKernelGGL((k_spawn<SPAWN_HEATBATH, 1>), __VA_ARGS__); \
   else if (pk_ == SPAWN_CAUCHY) hipLaunchKernelGGL((k_spawn<SPAWN_CAUCHY, 1>), __VA_ARGS__); \
+  else if (pk_ == SPAWN_CAUCHY_TS) hipLaunchKernelGGL((k_spawn<SPAWN_CAUCHY_TS, 1>), __VA_ARGS__); \
   else if (FUSE_) hipLaunchKernelGGL((k_spawn<SPAWN_UNIFORM, 1>), __VA_ARGS__); else hipLaunchKernelGGL((k_spawn<SPAWN_UNIFORM, 0>), __VA_ARGS__); } while (0)
 #define SPAWN_LAUNCH_EXT(PK_, FUSE_, ...) do { const int pk_ = (PK_); if (pk_ == SPAWN_HEATBATH) hipExtLaunchKernelGGL((k_spawn<SPAWN_HEATBATH, 1>), __VA_ARGS__); \
   else if (pk_ == SPAWN_CAUCHY) hipExtLaunchKernelGGL((k_spawn<SPAWN_CAUCHY, 1>), __VA_ARGS__); \
+  else if (pk_ == SPAWN_CAUCHY_TS) hipExtLaunchKernelGGL((k_spawn<SPAWN_CAUCHY_TS, 1>), __VA_ARGS__); \
   else if (FUSE_) hipExtLaunchKernelGGL((k_spawn<SPAWN_UNIFORM, 1>), __VA_ARGS__); else hipExtLaunchKernelGGL((k_spawn<SPAWN_UNIFORM, 0>), __VA_ARGS__); } while (0)
 #include "bucket_kernels.h"
 #include "door_kernels.h"

@@ -301,12 +301,14 @@ extern "C" int sqmc_gpu_debug_prof(unsigned long long *out) { return (int)hipMem
 #endif
 // one thread per child proposal; parent found by binary search in the child offsets
 // PK: the proposal -- SPAWN_UNIFORM (uniform2 / HEG / Hubbard), SPAWN_HEATBATH (fast_heatbath, two walker slots per child),
-//     SPAWN_CAUCHY (CauchySchwarz, one slot) -- each a kernel of its own, so that the uniform proposal keeps its registers
+//     SPAWN_CAUCHY (CauchySchwarz, one slot), SPAWN_CAUCHY_TS (CauchySchwarz with time_sym: the move ends in cs_time_sym_weight) -- each a
+//     kernel of its own, so that the uniform proposal and the plain Cauchy-Schwarz one keep their registers
 // FUSE: the short-list extras (children grouped by key range for the bucket tail, the block with the final sums, the projector rows);
 //       large populations run FUSE = 0, whose register and LDS budget is the plain spawn's (7 waves per SIMD)
 #define SPAWN_UNIFORM 0
 #define SPAWN_HEATBATH 1
 #define SPAWN_CAUCHY 2
+#define SPAWN_CAUCHY_TS 3
 template <int PK, int FUSE>
 __global__ void __launch_bounds__(TPB) k_spawn(ChemDev dev, WalkArr w, const u64 *__restrict__ child_off, const double *__restrict__ wchild,
                                                const u64 *__restrict__ child_state, u64 *__restrict__ keys, u32 *__restrict__ vals,
@@ -441,11 +443,13 @@ __global__ void __launch_bounds__(TPB) k_spawn(ChemDev dev, WalkArr w, const u64
       spawn_emit(dev, w, keys, vals, n0, 2 * c, pflg, ju2[0], jd2[0], wch * wj2[0], p, invalid_key, pack, oo);
       spawn_emit(dev, w, keys, vals, n0, 2 * c + 1, pflg, ju2[1], jd2[1], wch * wj2[1], p, invalid_key, pack, oo);
     } else {
-    const int level = (PK == SPAWN_CAUCHY) ? propose_cauchy_schwarz(t, dev.cs, g, iu, id, ju, jd, prob) : propose_any(t, g, iu, id, ju, jd, prob);
+    const int level = (PK == SPAWN_CAUCHY || PK == SPAWN_CAUCHY_TS) ? propose_cauchy_schwarz(t, dev.cs, g, iu, id, ju, jd, prob)
+                                                                     : propose_any(t, g, iu, id, ju, jd, prob);
     PROF(4);
     double wj = 0.0;
     if (level > 0) {
-      wj = proposal_weight(t, dev.integrals, p.tau, iu, id, ju, jd, level, prob);
+      wj = (PK == SPAWN_CAUCHY_TS) ? cs_time_sym_weight(t, dev.cs, dev.integrals, p.tau, iu, id, ju, jd, level, prob)
+                                   : proposal_weight(t, dev.integrals, p.tau, iu, id, ju, jd, level, prob);
       wj = wch * wj;
     }
     ckey = spawn_emit(dev, w, keys, vals, n0, c, pflg, ju, jd, wj, p, invalid_key, pack, oo);

@@ -214,8 +214,6 @@ class ChemHost:
         if proposal not in ("uniform", "cauchyschwarz"):
             raise ValueError("ChemHost.gpu: proposal %r (uniform or cauchyschwarz; fast heat-bath is set up on the context)" % (proposal,))
         if proposal == "cauchyschwarz":
-            if self.time_sym:
-                raise ValueError("the Cauchy-Schwarz proposal with time_sym = .true. is not built")
             self.cauchy_schwarz_clamp()
         g = GpuChem(self.norb, self.nup, self.ndn, self.orbsym, self.prod.reshape(-1), self.combine_2.reshape(-1), self.integrals,
                     n_group=self.n_group, time_sym=self.time_sym, z=self.z, n_core_orb=self.n_core_orb, **kw)

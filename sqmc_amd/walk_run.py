@@ -88,8 +88,6 @@ def parse_walk_deck(text):
         raise SystemExit("sqmc_amd.walk_run: proposal_method fast_heatbath with hf_to_psit = t is not built")
     if d["proposal_method"] == "cauchyschwarz" and d["hf_to_psit"]:
         raise SystemExit("sqmc_amd.walk_run: proposal_method CauchySchwarz with hf_to_psit = t is not built")
-    if d["proposal_method"] == "cauchyschwarz" and d["time_sym"]:
-        raise SystemExit("sqmc_amd.walk_run: proposal_method CauchySchwarz with time_sym = t is not built")
     if d["importance_sampling"] != 0:
         raise SystemExit("sqmc_amd.walk_run: importance_sampling must be 0")
     if d["hf_to_psit"] and d["hamiltonian_type"] == "hubbard2":

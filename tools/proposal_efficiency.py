@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Statistical efficiency of the chemistry proposals: uniform2 against CauchySchwarz on the C2 cc-pVDZ walk (COUNTER discipline).
 
-  python tools/proposal_efficiency.py [--targets 1e5 1e6] [--steps 20000] [--equil 2000] [--block 500]
+  python tools/proposal_efficiency.py [--targets 1e5 1e6] [--steps 20000] [--equil 2000] [--block 500] [--time-sym]
+
+--time-sym walks the same molecule in the conventions of the shipped HCI decks (time_sym = t, z = 1, hf_symmetry = 1): the walkers are
+representatives (up <= dn), and both proposals take the second pathway through the time-reversed determinant.
 
 One JSON line per (proposal, w_abs_gen_target): ms_per_step of sqmc_gpu_run, the k_spawn time per step from the library's HIP
 events (a separate pass of --timed-steps steps, sqmc_gpu_set_timing), E_proj with its error bar from --block-step blocks of the
@@ -41,6 +44,7 @@ def measure(H, host, proposal, target, args):
         e = float(num.sum() / den.sum())
         err = float(np.std(e_blk, ddof=1) / np.sqrt(nb))
         return {"proposal": {"uniform": "uniform2", "cauchyschwarz": "CauchySchwarz"}[proposal], "w_abs_gen_target": target,
+                "time_sym": bool(host.time_sym), "z": int(host.z),
                 "steps": args.steps, "ms_per_step": dt / args.steps * 1e3, "k_spawn_ms_per_step": float(np.median(spawn)),
                 "e_proj": e, "e_proj_err": err, "blocks": nb, "block_steps": args.block,
                 "err2_x_time_Ha2s": err * err * dt, "n_walkers": int(w.g.num_walkers())}
@@ -55,6 +59,7 @@ def main():
     ap.add_argument("--equil", type=int, default=2000)
     ap.add_argument("--timed-steps", type=int, default=100)
     ap.add_argument("--block", type=int, default=500)
+    ap.add_argument("--time-sym", action="store_true", help="time_sym = t, z = 1, hf_symmetry = 1 (the c2_hci conventions)")
     args = ap.parse_args()
     import torch  # noqa: F401  one libamdhip64 per process
     import sqmc_amd
@@ -62,7 +67,8 @@ def main():
     sqmc_amd.set_device(0)
     for target in args.targets:
         for proposal in ("uniform", "cauchyschwarz"):
-            host = H.ChemHost(FCIDUMP, 8, 4, "d2h")
+            host = (H.ChemHost(FCIDUMP, 8, 4, "d2h", time_sym=True, z=1, hf_symmetry=1) if args.time_sym
+                    else H.ChemHost(FCIDUMP, 8, 4, "d2h"))
             print(json.dumps(measure(H, host, proposal, target, args)), flush=True)
 
 
