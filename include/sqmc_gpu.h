@@ -447,6 +447,39 @@ int sqmc_gpu_hci_set_active_space(sqmc_gpu_ctx *ctx, uint64_t core_up, uint64_t 
  * (convert_time_symmetrized_to_dets, hci.f90:4365-4564) on a context initialised with time_sym = 0. */
 int sqmc_gpu_hci_pt2(sqmc_gpu_ctx *ctx, int64_t n_var, const uint64_t *var_up, const uint64_t *var_dn, const double *coeffs, double e_var,
                      double eps_pt, int32_t n_slices, double *delta_e, int64_t *n_connections);
+/* replaces: one sample of second_order_pt_alias (hci.f90:1314-1660), the semistochastic Epstein-Nesbet correction every HCI run uses
+ * once the connected space no longer fits (the reference switches to it by itself, hci.f90:688-702).  The alias tables
+ * (setup_alias, more_tools.f90:5603-5662), the 2 n_mc draws per sample of the serial rannyu stream (hci.f90:1438-1446), the merge of
+ * repeats, Welford and the stopping rule stay in the caller; everything that scales with the connections is done here.
+ *
+ * prepare (hci.f90:1373-1436): uploads the variational wavefunction once -- determinants, coefficients, their sorted ranks -- and
+ * owns the work buffers, which are reused from sample to sample and grow only when a sample has more raw connections than any before
+ * it.  The list must be sorted by (up, dn) without repeats (hci.f90:1373-1380: an unsorted one is refused); n_mc >= 2.  Chemistry
+ * (sqmc_gpu_set_hb_tables first) and HEG; hubbard2 is refused as the generator refuses it.  p_i = |c_i| / sum |c|.
+ * The plan borrows ctx: free it before sqmc_gpu_finalize.  Active-space masks (sqmc_gpu_hci_set_active_space) are generator
+ * state of ctx and apply to every sample as they stand when it runs. */
+typedef struct sqmc_pt2s_plan sqmc_pt2s_plan;
+int sqmc_gpu_hci_pt2_stochastic_prepare(sqmc_gpu_ctx *ctx, int64_t n_var, const uint64_t *var_up, const uint64_t *var_dn, const double *coeffs,
+                                        double e_var, double eps_pt, double eps_pt_big, int32_t n_mc, sqmc_pt2s_plan **plan);
+/* replaces: the body of the sample loop, hci.f90:1448-1640 (find_important_connected_dets of the sampled determinants, sort,
+ * the term1 / term2 sums per connected determinant, binary_search against the variational list, H_kk, the sum).  ids: the n_distinct
+ * distinct sampled determinants as 0-based positions in the variational list, ascending (what sort_and_merge_count_repeats,
+ * tools.f90:1574-1602, leaves); counts: their multiplicities w_i >= 1.
+ *   value = sum_k (term1^2 + term2 - term1_big^2 - term2_big) / (E_var - H_kk) / (n_mc (n_mc - 1))
+ * over the connected determinants k outside the variational space, term1 = sum_i H_ki c_i w_i/p_i,
+ * term2 = sum_i (H_ki c_i)^2 ((n_mc-1) w_i/p_i - (w_i/p_i)^2) over the connections the generator keeps at eps_pt, the _big sums over
+ * those with |H_ki c_i| > eps_pt_big; n_connected = the number of those k.  The additions have one fixed order (generation order
+ * within k, a fixed tree over k), so a sample returns the same bits run to run.  ids and counts go in, one double and one count
+ * come back; nothing else crosses the bus.  A sample whose raw connection count reaches 2^31 is refused: this entry does not slice.
+ * A refused sample leaves the plan usable. */
+int sqmc_gpu_hci_pt2_stochastic_sample(sqmc_pt2s_plan *plan, int64_t n_distinct, const int64_t *ids, const int64_t *counts, double *value,
+                                       int64_t *n_connected);
+/* the plan's bookkeeping (any pointer may be NULL): n_alloc = how many times the per-connection buffers were (re)allocated, capacity =
+ * connections they hold, last_raw = raw connections of the latest sample (before the merge; hci.f90:1452 n_connected_dets),
+ * n_samples = samples evaluated */
+int sqmc_gpu_hci_pt2_stochastic_stats(sqmc_pt2s_plan *plan, int64_t *n_alloc, int64_t *capacity, int64_t *last_raw, int64_t *n_samples);
+/* replaces: the deallocations at the end of second_order_pt_alias (hci.f90:1642-1660) */
+int sqmc_gpu_hci_pt2_stochastic_free(sqmc_pt2s_plan *plan);
 void sqmc_gpu_free(void *p);
 
 /* HIP-event timing on the library's streams.  level 0 off; 1 = only the longest kernel on the

@@ -28,7 +28,7 @@ EXPORTS = [
     "sqmc_gpu_shard_begin", "sqmc_gpu_shard_pack", "sqmc_gpu_shard_finish", "sqmc_gpu_shard_finish_psit", "sqmc_gpu_comm_unique_id", "sqmc_gpu_comm_init", "sqmc_gpu_comm_size",
     "sqmc_gpu_shard_step", "sqmc_gpu_shard_run", "sqmc_gpu_shard_time_split", "sqmc_gpu_get_rng", "sqmc_gpu_set_rng", "sqmc_gpu_tail_stats", "sqmc_gpu_slowest_steps", "sqmc_gpu_set_chained_runs", "sqmc_gpu_spmv_prepare", "sqmc_gpu_davidson",
     "sqmc_gpu_spmv_apply", "sqmc_gpu_spmv_free", "sqmc_gpu_build_spmv_plan", "sqmc_gpu_spmv_sym_upper", "sqmc_gpu_hamiltonian_batch",
-    "sqmc_gpu_propose_batch", "sqmc_gpu_hamiltonian_chem_batch", "sqmc_gpu_build_sparse_ham", "sqmc_gpu_hci_connections", "sqmc_gpu_hci_connections_slice", "sqmc_gpu_hci_pt2", "sqmc_gpu_hci_set_active_space", "sqmc_gpu_free", "sqmc_gpu_set_timing", "sqmc_gpu_get_timing",
+    "sqmc_gpu_propose_batch", "sqmc_gpu_hamiltonian_chem_batch", "sqmc_gpu_build_sparse_ham", "sqmc_gpu_hci_connections", "sqmc_gpu_hci_connections_slice", "sqmc_gpu_hci_pt2", "sqmc_gpu_hci_pt2_stochastic_prepare", "sqmc_gpu_hci_pt2_stochastic_sample", "sqmc_gpu_hci_pt2_stochastic_stats", "sqmc_gpu_hci_pt2_stochastic_free", "sqmc_gpu_hci_set_active_space", "sqmc_gpu_free", "sqmc_gpu_set_timing", "sqmc_gpu_get_timing",
 ]
 
 
@@ -610,6 +610,52 @@ class SpmvPlan:
         if self.h:
             self.L.sqmc_gpu_spmv_free(self.h)
             self.h = None
+
+
+class Pt2StochasticPlan:
+    """sqmc_gpu_hci_pt2_stochastic_prepare / _sample / _free: the samples of second_order_pt_alias (hci.f90:1314-1660) on the device.
+    up, dn sorted by (up, dn); the plan borrows the context g: close it before g."""
+
+    def __init__(self, g, up, dn, coeffs, e_var, eps_pt, eps_pt_big, n_mc):
+        self.L = g.L
+        u, d, c = _u64(up), _u64(dn), _f64(coeffs)
+        h = C.c_void_p()
+        self.L.sqmc_gpu_hci_pt2_stochastic_prepare.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double,
+                                                               C.c_int32, C.c_void_p]
+        self.L.sqmc_gpu_hci_pt2_stochastic_sample.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 4
+        self.L.sqmc_gpu_hci_pt2_stochastic_stats.argtypes = [C.c_void_p] * 5
+        self.L.sqmc_gpu_hci_pt2_stochastic_free.argtypes = [C.c_void_p]
+        self.h = None
+        _chk(self.L.sqmc_gpu_hci_pt2_stochastic_prepare(g.h, len(u), _p(u), _p(d), _p(c), float(e_var), float(eps_pt), float(eps_pt_big), int(n_mc), C.byref(h)))
+        self.h, self.g = h, g
+
+    def sample(self, ids, counts):
+        """ids: 0-based ascending positions of the distinct sampled determinants, counts: their multiplicities.
+        Returns (the sample's value, connected determinants outside the variational space)."""
+        i, w = np.ascontiguousarray(ids, np.int64), np.ascontiguousarray(counts, np.int64)
+        if len(i) != len(w):
+            raise ValueError("ids and counts differ in length")
+        v, n = C.c_double(), C.c_int64()
+        _chk(self.L.sqmc_gpu_hci_pt2_stochastic_sample(self.h, len(i), _p(i), _p(w), C.byref(v), C.byref(n)))
+        return v.value, n.value
+
+    def stats(self):
+        """dict(n_alloc, capacity, last_raw, n_samples): (re)allocations of the connection buffers so far, what they hold, the raw
+        connections of the latest sample, samples evaluated"""
+        a = [C.c_int64() for _ in range(4)]
+        _chk(self.L.sqmc_gpu_hci_pt2_stochastic_stats(self.h, *[C.byref(x) for x in a]))
+        return dict(zip(("n_alloc", "capacity", "last_raw", "n_samples"), (x.value for x in a)))
+
+    def close(self):
+        if self.h:
+            self.L.sqmc_gpu_hci_pt2_stochastic_free(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 GpuChem.hci_pt2 = _gpuchem_hci_pt2

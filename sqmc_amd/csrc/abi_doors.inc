@@ -515,6 +515,163 @@ int sqmc_gpu_hci_pt2(sqmc_gpu_ctx *c, int64_t n_var, const uint64_t *var_up, con
   return SQMC_OK;
 }
 
+// ----------------------------------------------------------------------- semistochastic PT2
+// One sample of second_order_pt_alias (hci.f90:1314-1660) on the device.  The plan keeps the variational wavefunction, its sorted
+// ranks and every work buffer; a sample allocates only when its raw connection count exceeds the capacity (n_alloc counts those
+// events, the first included).
+#define PT2S_MAXBLK 1024             // blocks of k_pt2s_terms at most (its partials are added by one wavefront)
+struct sqmc_pt2s_plan {
+  sqmc_gpu_ctx *c; long long n_var; int n_mc; double e_var, eps_pt, eps_pt_big;
+  std::vector<double> prob;          // p_i = |c_i| / sum |c|
+  u64 *vu, *vd, *vk, *vkalt, *skey; double *vc;                       // variational determinants, coefficients, sorted ranks (skey: vk or vkalt)
+  char *h_in; u64 *h_out;                                             // pinned: a sample's (w/p, ids) on the way in; total / (sum, count) on the way out
+  char *d_in; u64 *d_ru, *d_rd, *d_cnt, *d_off, *d_tot, *d_scan, *d_out; double *d_rc; long long scan_tiles;
+  long long cap; u64 *du, *dd, *keys, *kalt; double *dx, *dsrc; u32 *vals, *valt, *hist, *rowtot;     // per connection, capacity cap
+  double *d_part; u64 *d_pcnt;
+  long long n_alloc, n_samples, last_raw, max_raw;
+};
+// sum of n doubles in the blocked pairwise order (leaves of at most 128 summed in 8 interleaved accumulators, halves split on a
+// multiple of 8): error O(log n) ulp, and the order numpy's sum uses, so that p_i has the bits of the host path
+static double pt2s_pairwise_sum(const double *a, long long n) {
+  if (n < 8) { double r = 0.0; for (long long i = 0; i < n; i++) r += a[i]; return r; }
+  if (n <= 128) {
+    double r[8]; for (int k = 0; k < 8; k++) r[k] = a[k];
+    long long i;
+    for (i = 8; i < n - (n % 8); i += 8) for (int k = 0; k < 8; k++) r[k] += a[i + k];
+    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; i < n; i++) res += a[i];
+    return res;
+  }
+  long long n2 = n / 2; n2 -= n2 % 8;
+  return pt2s_pairwise_sum(a, n2) + pt2s_pairwise_sum(a + n2, n - n2);
+}
+static void pt2s_free_conn(sqmc_pt2s_plan *p) {
+  void *fr[] = {p->du, p->dd, p->keys, p->kalt, p->dx, p->dsrc, p->vals, p->valt, p->hist};
+  for (void *q : fr) hipFree(q);
+  p->du = p->dd = p->keys = p->kalt = nullptr; p->dx = p->dsrc = nullptr; p->vals = p->valt = p->hist = nullptr; p->cap = 0;
+}
+static int pt2s_grow(sqmc_pt2s_plan *p, long long need) {
+  pt2s_free_conn(p);
+  long long cap = need + need / 4 + 1024;
+  if (cap > (1ll << 31) - 1) cap = (1ll << 31) - 1;
+  HIPCHK(hipMalloc(&p->du, cap * 8)); HIPCHK(hipMalloc(&p->dd, cap * 8)); HIPCHK(hipMalloc(&p->dx, cap * 8)); HIPCHK(hipMalloc(&p->dsrc, cap * 8));
+  HIPCHK(hipMalloc(&p->keys, cap * 8)); HIPCHK(hipMalloc(&p->kalt, cap * 8)); HIPCHK(hipMalloc(&p->vals, cap * 4)); HIPCHK(hipMalloc(&p->valt, cap * 4));
+  HIPCHK(hipMalloc(&p->hist, (size_t)RS_MAX_RADIX * ((cap + RS_TILE - 1) / RS_TILE + 1) * 4));
+  p->cap = cap; p->n_alloc++;
+  return SQMC_OK;
+}
+int sqmc_gpu_hci_pt2_stochastic_free(sqmc_pt2s_plan *p) {
+  if (!p) return SQMC_OK;
+  pt2s_free_conn(p);
+  void *fr[] = {p->vu, p->vd, p->vk, p->vkalt, p->vc, p->d_in, p->d_ru, p->d_rd, p->d_cnt, p->d_off, p->d_tot, p->d_scan, p->d_out, p->d_rc, p->rowtot, p->d_part, p->d_pcnt};
+  for (void *q : fr) hipFree(q);
+  if (p->h_in) hipHostFree(p->h_in);
+  if (p->h_out) hipHostFree(p->h_out);
+  delete p;
+  return SQMC_OK;
+}
+static int pt2s_prepare(sqmc_pt2s_plan *p, const uint64_t *var_up, const uint64_t *var_dn, const double *coeffs) {
+  sqmc_gpu_ctx *c = p->c; hipStream_t st = c->st; const long long n = p->n_var, m = p->n_mc;
+  HIPCHK(hipMalloc(&p->vu, n * 8)); HIPCHK(hipMalloc(&p->vd, n * 8)); HIPCHK(hipMalloc(&p->vc, n * 8)); HIPCHK(hipMalloc(&p->vk, n * 8)); HIPCHK(hipMalloc(&p->vkalt, n * 8));
+  u32 *vv, *vvalt, *hist;
+  HIPCHK(hipMalloc(&vv, n * 4)); HIPCHK(hipMalloc(&vvalt, n * 4));
+  HIPCHK(hipMalloc(&hist, (size_t)RS_MAX_RADIX * ((n + RS_TILE - 1) / RS_TILE + 1) * 4)); HIPCHK(hipMalloc(&p->rowtot, RS_MAX_RADIX * 4));
+  HIPCHK(hipMemcpy(p->vu, var_up, n * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(p->vd, var_dn, n * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(p->vc, coeffs, n * 8, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_main_keys, dim3(nblk(n)), dim3(TPB), 0, st, c->dev, p->vu, p->vd, p->vk, vv, n, 0);
+  SortWork so; so.k_alt = p->vkalt; so.v_alt = vvalt; so.hist = hist; so.rowtot = p->rowtot; so.cap = n;
+  u64 *skey = p->vk; u32 *sperm = vv;
+  device_radix_sort(skey, sperm, n, c->key_bits, so, st);
+  HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(st));
+  p->skey = skey;
+  hipFree(vv); hipFree(vvalt); hipFree(hist);
+  HIPCHK(hipHostMalloc(&p->h_in, m * 12 + 16)); HIPCHK(hipHostMalloc(&p->h_out, 32));
+  HIPCHK(hipMalloc(&p->d_in, m * 12 + 16)); HIPCHK(hipMalloc(&p->d_ru, m * 8)); HIPCHK(hipMalloc(&p->d_rd, m * 8)); HIPCHK(hipMalloc(&p->d_rc, m * 8));
+  HIPCHK(hipMalloc(&p->d_cnt, m * 8)); HIPCHK(hipMalloc(&p->d_off, m * 8)); HIPCHK(hipMalloc(&p->d_tot, 8)); HIPCHK(hipMalloc(&p->d_out, 16));
+  p->scan_tiles = (m + SCAN_TILE - 1) / SCAN_TILE + 1;
+  HIPCHK(hipMalloc(&p->d_scan, (p->scan_tiles + 1) * 8));
+  HIPCHK(hipMalloc(&p->d_part, PT2S_MAXBLK * 8)); HIPCHK(hipMalloc(&p->d_pcnt, PT2S_MAXBLK * 8));
+  return SQMC_OK;
+}
+int sqmc_gpu_hci_pt2_stochastic_prepare(sqmc_gpu_ctx *c, int64_t n_var, const uint64_t *var_up, const uint64_t *var_dn, const double *coeffs, double e_var,
+                                        double eps_pt, double eps_pt_big, int32_t n_mc, sqmc_pt2s_plan **plan) {
+  if (!c || !plan || !var_up || !var_dn || !coeffs || n_var <= 0) return fail(SQMC_ERR_BAD_ARG, "bad argument");
+  *plan = nullptr;
+  if (n_mc < 2) return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_hci_pt2_stochastic_prepare: n_mc must be at least 2 (the estimator divides by n_mc (n_mc - 1))");
+  if (n_var >= (1ll << 31)) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_hci_pt2_stochastic_prepare: more than 2^31 variational determinants");
+  if (c->htab.sys_type == 2) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_hci_pt2_stochastic_prepare: hubbard2 has no heat-bath connection generator (find_connected_dets_hubbard is the host's)");
+  if (c->htab.sys_type == 0 && !c->dev.hb_r) return fail(SQMC_ERR_BAD_ARG, "heat-bath tables not set (sqmc_gpu_set_hb_tables)");
+  if (c->htab.sys_type == 1 && c->htab.heg_nmax > 4) return fail(SQMC_ERR_UNSUPPORTED, "HEG connections: plane-wave index beyond +-4");
+  for (long long i = 1; i < n_var; i++)
+    if (var_up[i - 1] > var_up[i] || (var_up[i - 1] == var_up[i] && var_dn[i - 1] >= var_dn[i]))
+      return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_hci_pt2_stochastic_prepare: the variational determinants must be sorted by (up, dn) without repeats (hci.f90:1373-1380)");
+  sqmc_pt2s_plan *p = new sqmc_pt2s_plan();       // value-initialised: every pointer null, every counter 0
+  p->c = c; p->n_var = n_var; p->n_mc = n_mc; p->e_var = e_var; p->eps_pt = eps_pt; p->eps_pt_big = eps_pt_big;
+  p->prob.resize(n_var);
+  for (long long i = 0; i < n_var; i++) p->prob[i] = fabs(coeffs[i]);
+  double norm = 0.0;                              // numpy adds the pairwise sums of consecutive 8192-element pieces left to right
+  for (long long i = 0; i < n_var; i += 8192) { const double part = pt2s_pairwise_sum(p->prob.data() + i, std::min<long long>(8192, n_var - i)); norm = i ? norm + part : part; }
+  if (!(norm > 0.0)) { delete p; return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_hci_pt2_stochastic_prepare: all coefficients are zero"); }
+  for (long long i = 0; i < n_var; i++) p->prob[i] = p->prob[i] / norm;
+  const int rc = pt2s_prepare(p, var_up, var_dn, coeffs);
+  if (rc != SQMC_OK) { const std::string m = g_err; sqmc_gpu_hci_pt2_stochastic_free(p); return fail(rc, m); }
+  *plan = p;
+  return SQMC_OK;
+}
+int sqmc_gpu_hci_pt2_stochastic_sample(sqmc_pt2s_plan *p, int64_t n_distinct, const int64_t *ids, const int64_t *counts, double *value, int64_t *n_connected) {
+  if (!p || !ids || !counts || !value || !n_connected) return fail(SQMC_ERR_BAD_ARG, "null argument");
+  if (n_distinct < 1 || n_distinct > p->n_mc) return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_hci_pt2_stochastic_sample: n_distinct must be in [1, n_mc]");
+  sqmc_gpu_ctx *c = p->c; hipStream_t st = c->st; const long long m = n_distinct;
+  double *h_wop = (double *)p->h_in; int *h_ids = (int *)(p->h_in + (size_t)p->n_mc * 8);
+  for (long long i = 0; i < m; i++) {
+    if (ids[i] < 0 || ids[i] >= p->n_var) return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_hci_pt2_stochastic_sample: id out of range (0-based positions in the variational list)");
+    if (i > 0 && ids[i] <= ids[i - 1]) return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_hci_pt2_stochastic_sample: ids must be ascending and distinct (sort_and_merge_count_repeats)");
+    if (counts[i] < 1) return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_hci_pt2_stochastic_sample: a count below 1");
+  }
+  for (long long i = 0; i < m; i++) { h_ids[i] = (int)ids[i]; h_wop[i] = (double)counts[i] / p->prob[ids[i]]; }
+  const double *d_wop = (const double *)p->d_in; const int *d_ids = (const int *)(p->d_in + (size_t)p->n_mc * 8);
+  HIPCHK(hipMemcpyAsync(p->d_in, p->h_in, (size_t)p->n_mc * 8 + m * 4, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_pt2s_gather, dim3(nblk(m)), dim3(TPB), 0, st, d_ids, (const u64 *)p->vu, (const u64 *)p->vd, (const double *)p->vc, p->d_ru, p->d_rd, p->d_rc, m);
+  hipLaunchKernelGGL(k_hci_gen, dim3(nblk(m)), dim3(TPB), 0, st, c->dev, p->d_ru, p->d_rd, p->d_rc, p->eps_pt, 2, m, 0, p->d_cnt, p->d_off,
+                     (u64 *)nullptr, (u64 *)nullptr, (double *)nullptr, (double *)nullptr, 0ull, ~0ull, c->as);
+  ScanWork sw; sw.state = p->d_scan; sw.ticket = (u32 *)(p->d_scan + p->scan_tiles); sw.cap_tiles = p->scan_tiles; sw.self_clear = true;
+  device_excl_scan_u64(p->d_cnt, p->d_off, m, p->d_tot, sw, st);
+  HIPCHK(hipMemcpyAsync(p->h_out, p->d_tot, 8, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st));       // the one sync that sizes the fill
+  const u64 total = p->h_out[0];
+  if (total >= (1ull << 31)) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_hci_pt2_stochastic_sample: 2^31 or more raw connections in one sample (no slicing here: lower n_mc or raise eps_pt)");
+  const long long T = (long long)total;
+  p->last_raw = T; if (T > p->max_raw) p->max_raw = T;
+  *value = 0.0; *n_connected = 0;
+  if (T == 0) { p->n_samples++; return SQMC_OK; }
+  if (T > p->cap) { const int rc = pt2s_grow(p, T); if (rc != SQMC_OK) return rc; }
+  hipLaunchKernelGGL(k_hci_gen, dim3(nblk(m)), dim3(TPB), 0, st, c->dev, p->d_ru, p->d_rd, p->d_rc, p->eps_pt, 2, m, 1, p->d_cnt, p->d_off,
+                     p->du, p->dd, p->dx, p->dsrc, 0ull, ~0ull, c->as);
+  hipLaunchKernelGGL(k_main_keys, dim3(nblk(T)), dim3(TPB), 0, st, c->dev, p->du, p->dd, p->keys, p->vals, T, 0);
+  SortWork so; so.k_alt = p->kalt; so.v_alt = p->valt; so.hist = p->hist; so.rowtot = p->rowtot; so.cap = p->cap;
+  u64 *skey = p->keys; u32 *perm = p->vals;
+  device_radix_sort(skey, perm, T, c->key_bits, so, st);
+  const int nb = std::min(nblk(T), PT2S_MAXBLK);
+  hipLaunchKernelGGL(k_pt2s_terms, dim3(nb), dim3(TPB), 0, st, c->dev, (const u64 *)skey, (const u32 *)perm, (const u64 *)p->du, (const u64 *)p->dd,
+                     (const double *)p->dx, (const double *)p->dsrc, d_wop, T, (const u64 *)p->skey, p->n_var, p->e_var, p->eps_pt_big,
+                     (double)(p->n_mc - 1), p->d_part, p->d_pcnt);
+  hipLaunchKernelGGL(k_pt2s_final, dim3(1), dim3(64), 0, st, (const double *)p->d_part, (const u64 *)p->d_pcnt, nb, p->d_out);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(p->h_out + 2, p->d_out, 16, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st));
+  double sum; memcpy(&sum, &p->h_out[2], 8);
+  *value = sum / ((double)p->n_mc * (double)(p->n_mc - 1));
+  *n_connected = (int64_t)p->h_out[3];
+  p->n_samples++;
+  return SQMC_OK;
+}
+int sqmc_gpu_hci_pt2_stochastic_stats(sqmc_pt2s_plan *p, int64_t *n_alloc, int64_t *capacity, int64_t *last_raw, int64_t *n_samples) {
+  if (!p) return fail(SQMC_ERR_BAD_ARG, "null plan");
+  if (n_alloc) *n_alloc = p->n_alloc;
+  if (capacity) *capacity = p->cap;
+  if (last_raw) *last_raw = p->last_raw;
+  if (n_samples) *n_samples = p->n_samples;
+  return SQMC_OK;
+}
+
 // ----------------------------------------------------------------------- SpMV
 int sqmc_gpu_spmv_prepare(int64_t n, const int64_t *rc, const int64_t *idx, const double *val, sqmc_spmv_plan **plan) {
   if (!rc || !idx || !val || !plan || n <= 0) return fail(SQMC_ERR_BAD_ARG, "bad argument");

@@ -162,3 +162,68 @@ __global__ void __launch_bounds__(TPB) k_hci_dedup(const u64 *__restrict__ skey,
   const u64 o = pos[j];
   ou[o] = iu[t]; od[o] = id[t]; onum[o] = a; oden[o] = b;
 }
+
+// ================================================================ semistochastic PT2 (second_order_pt_alias, hci.f90:1314-1660)
+// the sampled determinants of one sample, gathered from the plan's resident variational list: the generator's input
+__global__ void __launch_bounds__(TPB) k_pt2s_gather(const int *__restrict__ ids, const u64 *__restrict__ vu, const u64 *__restrict__ vd,
+                                                     const double *__restrict__ vc, u64 *__restrict__ ru, u64 *__restrict__ rd, double *__restrict__ rc, long long n) {
+  long long i = (long long)blockIdx.x * TPB + threadIdx.x;
+  if (i < n) { const int s = ids[i]; ru[i] = vu[s]; rd[i] = vd[s]; rc[i] = vc[s]; }
+}
+// The weighted segmented sums of one sample and its finish in one pass over the sorted raw connections (hci.f90:1452-1640).
+// The thread that lands on the head of a run of equal keys owns the connected determinant k: it drops k if k is in the variational
+// space (binary search on the sorted ranks, as k_pt2_terms; this drops every source's own slot too), walks the run left to right --
+// the stable sort keeps generation order, so the additions have one fixed order -- forming from x = H_ki c_i and the source's
+// w/p (src: the raw mode's index of the source among the sampled determinants)
+//     term1 = sum x w/p                     term2 = sum x^2 ((n_mc-1) w/p - (w/p)^2)
+// and the same two over the connections with |x| > eps_pt_big, then H_kk and the term
+//     (term1^2 + term2 - term1_big^2 - term2_big) / (E_var - H_kk).
+// Runs are short (k is reached from a handful of the <= n_mc sources), hence one thread per run as k_hci_dedup; no head flags,
+// scan or compaction: nothing is copied out.  Grid-stride, one partial sum and one count per block (fixed tree, no atomics).
+__global__ void __launch_bounds__(TPB) k_pt2s_terms(ChemDev dev, const u64 *__restrict__ skey, const u32 *__restrict__ perm, const u64 *__restrict__ cu,
+                                                    const u64 *__restrict__ cd, const double *__restrict__ x, const double *__restrict__ src,
+                                                    const double *__restrict__ wop, long long n, const u64 *__restrict__ vkeys, long long nv, double e_var,
+                                                    double eps_big, double n_mc_m1, double *__restrict__ partial, u64 *__restrict__ pcount) {
+  __shared__ ChemTab t;
+  stage_tab(&t, dev.tab, dev.tab_words);
+  double acc = 0.0; u64 cnt = 0;
+  for (long long j = (long long)blockIdx.x * TPB + threadIdx.x; j < n; j += (long long)gridDim.x * TPB) {
+    const u64 key = skey[j];
+    if (j > 0 && skey[j - 1] == key) continue;         // not a head
+    long long lo = 0, hi = nv;                         // first variational rank >= key
+    while (lo < hi) { const long long mid = (lo + hi) >> 1; if (vkeys[mid] < key) lo = mid + 1; else hi = mid; }
+    if (lo < nv && vkeys[lo] == key) continue;         // inside the variational space
+    const u32 p0 = perm[j];
+    double t1 = 0.0, t2 = 0.0, t1b = 0.0, t2b = 0.0;
+    for (long long jj = j; jj < n && skey[jj] == key; jj++) {
+      const u32 p = (jj == j) ? p0 : perm[jj];
+      const double xv = x[p], w = wop[(int)src[p]];
+      const double a1 = xv * w, a2 = (xv * xv) * (n_mc_m1 * w - w * w);
+      const bool big = fabs(xv) > eps_big;
+      if (jj == j) { t1 = a1; t2 = a2; t1b = big ? a1 : 0.0; t2b = big ? a2 : 0.0; }
+      else { t1 = t1 + a1; t2 = t2 + a2; t1b = t1b + (big ? a1 : 0.0); t2b = t2b + (big ? a2 : 0.0); }
+    }
+    const u64 u = cu[p0], d = cd[p0];
+    const double hkk = h_any(t, dev.integrals, u, d, u, d);
+    acc += (t1 * t1 + t2 - t1b * t1b - t2b) / (e_var - hkk);
+    cnt++;
+  }
+  __shared__ double red[TPB / 64]; __shared__ u64 redc[TPB / 64];
+  for (int o = 32; o > 0; o >>= 1) { acc += __shfl_down(acc, o, 64); cnt += __shfl_down(cnt, o, 64); }
+  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = acc; redc[threadIdx.x >> 6] = cnt; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double v = 0.0; u64 k = 0;
+    for (int q = 0; q < TPB / 64; q++) { v += red[q]; k += redc[q]; }
+    partial[blockIdx.x] = v; pcount[blockIdx.x] = k;
+  }
+}
+// the block partials of k_pt2s_terms in block order: lane l of one wavefront adds its contiguous share left to right, then the
+// fixed shuffle tree; out[0] = the sum (a double), out[1] = the count -- the 16 bytes a sample sends back
+__global__ void __launch_bounds__(64) k_pt2s_final(const double *__restrict__ partial, const u64 *__restrict__ pcount, int nb, u64 *__restrict__ out) {
+  const int chunk = (nb + 63) / 64, lane = threadIdx.x;
+  double a = 0.0; u64 k = 0;
+  for (int q = lane * chunk; q < (lane + 1) * chunk && q < nb; q++) { a += partial[q]; k += pcount[q]; }
+  for (int o = 32; o > 0; o >>= 1) { a += __shfl_down(a, o, 64); k += __shfl_down(k, o, 64); }
+  if (lane == 0) { out[0] = (u64)__double_as_longlong(a); out[1] = k; }
+}

@@ -20,6 +20,7 @@ module sqmc_gpu_mod
   public :: sqmc_gpu_set_hf_to_psit, sqmc_gpu_setup_efficient_heatbath, sqmc_gpu_get_heatbath_tables
   public :: sqmc_gpu_set_hf_to_psit_shard, sqmc_gpu_shard_finish_psit
   public :: sqmc_gpu_setup_cauchy_schwarz, sqmc_gpu_propose_cauchy_schwarz_batch
+  public :: sqmc_gpu_hci_pt2_stochastic_prepare, sqmc_gpu_hci_pt2_stochastic_sample, sqmc_gpu_hci_pt2_stochastic_stats, sqmc_gpu_hci_pt2_stochastic_free
   public :: sqmc_gpu_check
 
   integer(c_int), parameter, public :: SQMC_RNG_REPLAY = 0, SQMC_RNG_COUNTER = 1
@@ -130,6 +131,26 @@ module sqmc_gpu_mod
       import; type(c_ptr), value :: ctx; integer(c_int64_t), value :: n_var; integer(c_int64_t), intent(in) :: var_up(*), var_dn(*)
       real(c_double), intent(in) :: coeffs(*); real(c_double), value :: e_var, eps_pt; integer(c_int32_t), value :: n_slices
       real(c_double), intent(out) :: delta_e; integer(c_int64_t), intent(out) :: n_connections
+    end function
+    ! second_order_pt_alias (hci.f90:1314-1660): the variational wavefunction and the work buffers stay on the device (prepare),
+    ! one call per sample with the merged draws (0-based ids, ascending, and their counts), free at the end
+    integer(c_int) function sqmc_gpu_hci_pt2_stochastic_prepare(ctx, n_var, var_up, var_dn, coeffs, e_var, eps_pt, eps_pt_big, n_mc, plan) &
+        bind(C, name='sqmc_gpu_hci_pt2_stochastic_prepare')
+      import; type(c_ptr), value :: ctx; integer(c_int64_t), value :: n_var; integer(c_int64_t), intent(in) :: var_up(*), var_dn(*)
+      real(c_double), intent(in) :: coeffs(*); real(c_double), value :: e_var, eps_pt, eps_pt_big; integer(c_int32_t), value :: n_mc
+      type(c_ptr), intent(out) :: plan
+    end function
+    integer(c_int) function sqmc_gpu_hci_pt2_stochastic_sample(plan, n_distinct, ids, counts, value, n_connected) &
+        bind(C, name='sqmc_gpu_hci_pt2_stochastic_sample')
+      import; type(c_ptr), value :: plan; integer(c_int64_t), value :: n_distinct; integer(c_int64_t), intent(in) :: ids(*), counts(*)
+      real(c_double), intent(out) :: value; integer(c_int64_t), intent(out) :: n_connected
+    end function
+    integer(c_int) function sqmc_gpu_hci_pt2_stochastic_stats(plan, n_alloc, capacity, last_raw, n_samples) &
+        bind(C, name='sqmc_gpu_hci_pt2_stochastic_stats')
+      import; type(c_ptr), value :: plan; integer(c_int64_t), intent(out) :: n_alloc, capacity, last_raw, n_samples
+    end function
+    integer(c_int) function sqmc_gpu_hci_pt2_stochastic_free(plan) bind(C, name='sqmc_gpu_hci_pt2_stochastic_free')
+      import; type(c_ptr), value :: plan
     end function
     integer(c_int) function sqmc_gpu_set_heatbath_tables(ctx, t) bind(C, name='sqmc_gpu_set_heatbath_tables')
       import; type(c_ptr), value :: ctx; type(sqmc_heatbath_tables), intent(in) :: t

@@ -1476,8 +1476,37 @@ def setup_alias(pdf):
     return J, q
 
 
+def pt2_stochastic_sample_host(g, up, dn, c, prob, ids, counts, e_var, eps_pt, eps_pt_big, n_mc, parts=None):
+    """One sample of second_order_pt_alias with the sums in numpy (the body of hci_pt2_stochastic's loop when on_device is off):
+    the raw connections of the sampled determinants come from the GPU, membership, lexsort and the four segmented sums are
+    numpy's, H_kk is one more GPU call.  ids are 1-based positions in the sorted list (up, dn, c), counts their multiplicities,
+    prob = |c| / sum|c|.  Returns (value, number of connected determinants outside the variational space); a dict passed as
+    parts receives the per-determinant arrays t1, t2, t1b, t2b, h_kk, the run starts and the raw connection count."""
+    ci, wop = c[ids - 1], counts / prob[ids - 1]
+    cu, cd, x, src = g.hci_connections(up[ids - 1], dn[ids - 1], ci, eps_pt, diag_mode=2)
+    src = src.astype(np.int64)
+    own = (cu == up[ids - 1][src]) & (cd == dn[ids - 1][src])           # the self slot of every reference determinant
+    keep = ~own & ~_dets_in(cu, cd, up, dn)                             # connected determinants outside the variational space
+    n_raw = len(cu)
+    cu, cd, x, src = cu[keep], cd[keep], x[keep], src[keep]
+    w1 = wop[src]
+    a1, a2 = x * w1, x * x * ((n_mc - 1) * w1 - w1 * w1)
+    big = np.abs(x) > eps_pt_big
+    o = np.lexsort((cd, cu))
+    cu, cd, a1, a2, big = cu[o], cd[o], a1[o], a2[o], big[o]
+    head = np.ones(len(cu), bool); head[1:] = (cu[1:] != cu[:-1]) | (cd[1:] != cd[:-1])
+    st = np.nonzero(head)[0]
+    t1, t2 = np.add.reduceat(a1, st), np.add.reduceat(a2, st)
+    t1b, t2b = np.add.reduceat(np.where(big, a1, 0.0), st), np.add.reduceat(np.where(big, a2, 0.0), st)
+    h_kk = g.hamiltonian_batch(cu[st], cd[st], cu[st], cd[st])
+    val = float(np.sum((t1 * t1 + t2 - t1b * t1b - t2b) / (e_var - h_kk))) / (n_mc * float(n_mc - 1))
+    if parts is not None:
+        parts.update(t1=t1, t2=t2, t1b=t1b, t2b=t2b, h_kk=h_kk, starts=st, n_kept=len(cu), n_raw=n_raw)
+    return val, len(st)
+
+
 def hci_pt2_stochastic(host, g, up, dn, coeffs, e_var, eps_pt, eps_pt_big, n_mc, target_error, seed=(2726, 5165, 6543, 6524),
-                       max_samples=10**6, log=None):
+                       max_samples=10**6, log=None, on_device=False):
     """second_order_pt_alias, hci.f90:1314-1660 (one rank): the PT correction at eps_pt as the
     deterministic correction at eps_pt_big (hci_pt2) plus a stochastic estimate of the difference.
     Each sample draws n_mc variational determinants with probability |c_i| / sum|c| (alias method,
@@ -1488,7 +1517,11 @@ def hci_pt2_stochastic(host, g, up, dn, coeffs, e_var, eps_pt, eps_pt_big, n_mc,
     is sum_k (term1^2 + term2 - term1_big^2 - term2_big) / (E_var - H_kk) / (n_mc (n_mc-1)).  Welford mean
     and variance; stops after >= 10 samples once the error bar is below target_error.
     The determinant list must be sorted by (up,dn) (hci.f90:1373-1380).
-    Returns dict(pt_big, pt_diff, pt_diff_std_dev, samples=[per-sample values], n_connected_big)."""
+    on_device: a sample is one call of the library (sqmc_gpu_hci_pt2_stochastic_sample: generation, sort, the weighted sums,
+    membership, H_kk and the reduction on the device; the merged draws go in, one double and one count come back) instead of
+    pt2_stochastic_sample_host.  Draws, merging, Welford and the stopping rule are the same code either way.
+    Returns dict(pt_big, pt_diff, pt_diff_std_dev, samples=[per-sample values], n_connected_big,
+    samples_connected=[connected determinants outside the variational space, per sample])."""
     up, dn, c = np.ascontiguousarray(up, np.uint64), np.ascontiguousarray(dn, np.uint64), np.asarray(coeffs, float)
     order = sort_dets(up, dn)
     up, dn, c = up[order], dn[order], c[order]
@@ -1498,31 +1531,26 @@ def hci_pt2_stochastic(host, g, up, dn, coeffs, e_var, eps_pt, eps_pt_big, n_mc,
     J, q = setup_alias(prob)
     rng = Rannyu(seed)
     mean = s_acc = var = 0.0
-    values = []
+    values, n_conn = [], []
+    plan = None
+    if on_device:
+        from ._lib import Pt2StochasticPlan
+        plan = Pt2StochasticPlan(g, up, dn, c, e_var, eps_pt, eps_pt_big, n_mc)
     for sample in range(1, max_samples + 1):
         draws = np.empty(n_mc, np.int64)
         for k in range(n_mc):
             i = rng.random_int(n)
             draws[k] = i if rng.rannyu() < q[i - 1] else J[i - 1]
         ids, counts = np.unique(draws, return_counts=True)                 # sort_and_merge_count_repeats, tools.f90:1574-1602
-        ci, wop = c[ids - 1], counts / prob[ids - 1]
-        cu, cd, x, src = g.hci_connections(up[ids - 1], dn[ids - 1], ci, eps_pt, diag_mode=2)
-        src = src.astype(np.int64)
-        own = (cu == up[ids - 1][src]) & (cd == dn[ids - 1][src])           # the self slot of every reference determinant
-        keep = ~own & ~_dets_in(cu, cd, up, dn)                             # connected determinants outside the variational space
-        cu, cd, x, src = cu[keep], cd[keep], x[keep], src[keep]
-        w1 = wop[src]
-        a1, a2 = x * w1, x * x * ((n_mc - 1) * w1 - w1 * w1)
-        big = np.abs(x) > eps_pt_big
-        o = np.lexsort((cd, cu))
-        cu, cd, a1, a2, big = cu[o], cd[o], a1[o], a2[o], big[o]
-        head = np.ones(len(cu), bool); head[1:] = (cu[1:] != cu[:-1]) | (cd[1:] != cd[:-1])
-        st = np.nonzero(head)[0]
-        t1, t2 = np.add.reduceat(a1, st), np.add.reduceat(a2, st)
-        t1b, t2b = np.add.reduceat(np.where(big, a1, 0.0), st), np.add.reduceat(np.where(big, a2, 0.0), st)
-        h_kk = g.hamiltonian_batch(cu[st], cd[st], cu[st], cd[st])
-        val = float(np.sum((t1 * t1 + t2 - t1b * t1b - t2b) / (e_var - h_kk))) / (n_mc * float(n_mc - 1))
-        values.append(val)
+        if plan is not None:
+            try:
+                val, nk = plan.sample(ids - 1, counts)
+            except BaseException:
+                plan.close()
+                raise
+        else:
+            val, nk = pt2_stochastic_sample_host(g, up, dn, c, prob, ids, counts, e_var, eps_pt, eps_pt_big, n_mc)
+        values.append(val); n_conn.append(nk)
         old = mean
         mean = mean + (val - mean) / sample                                 # welford, tools.f90:1761-1778
         s_acc = s_acc + (val - mean) * (val - old)
@@ -1531,4 +1559,6 @@ def hci_pt2_stochastic(host, g, up, dn, coeffs, e_var, eps_pt, eps_pt_big, n_mc,
             log("Sample, E_2pt_now, E_2pt estimate, total energy=%6d%15.9f%12.8f%15.8f +-%12.8f" % (sample, val, mean, e_var + pt_big + mean, np.sqrt(var) if sample > 1 else float("nan")))
         if sample >= 10 and var < target_error ** 2:
             break
-    return dict(pt_big=pt_big, pt_diff=mean, pt_diff_std_dev=float(np.sqrt(var)), samples=values, n_connected_big=n_big)
+    if plan is not None:
+        plan.close()
+    return dict(pt_big=pt_big, pt_diff=mean, pt_diff_std_dev=float(np.sqrt(var)), samples=values, n_connected_big=n_big, samples_connected=n_conn)

@@ -104,7 +104,7 @@ def parse_hci_deck(text):
     return deck
 
 
-def run_hci_heg(deck, out=sys.stdout):
+def run_hci_heg(deck, out=sys.stdout, pt_on_device=False):
     """HEG decks: no integral file; result lines as hci.f90 prints them for 'heg' (no state index in the
     older output format the e2e fixtures were produced with; Madelung total, correlation energy)."""
     import torch            # noqa: F401
@@ -128,7 +128,7 @@ def run_hci_heg(deck, out=sys.stdout):
     e0 = float(energy[0])
     if deck["n_mc"] > 0 and deck["eps_pt_big"] > deck["eps_pt"]:
         r = H.hci_pt2_stochastic(h, g, up, dn, wts[:, 0], e0, deck["eps_pt"], deck["eps_pt_big"], deck["n_mc"], deck["target_error"],
-                                 seed=deck["irand_seed"][0], log=lambda m: p("\n" + m))
+                                 seed=deck["irand_seed"][0], log=lambda m: p("\n" + m), on_device=pt_on_device)
         de, err = r["pt_big"] + r["pt_diff"], r["pt_diff_std_dev"]
         p("\nVariational energy=%s%15.9f" % (" " * 16, e0))
         p("Second-order PT energy lowering=%s%15.9f +-%12.9f (%13.9f%13.9f)" % (" " * 3, de, err, r["pt_big"], r["pt_diff"]))
@@ -149,9 +149,10 @@ def run_hci_heg(deck, out=sys.stdout):
     return res
 
 
-def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout):
+def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False):
+    """pt_on_device: the samples of the semistochastic PT are evaluated by the library (host.hci_pt2_stochastic on_device)"""
     if deck["hamiltonian_type"] == "heg":
-        return run_hci_heg(deck, out)
+        return run_hci_heg(deck, out, pt_on_device)
     import torch            # noqa: F401  one libamdhip64 per process
     import sqmc_amd
     from . import host as H
@@ -198,7 +199,7 @@ def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout):
             gp.set_hb_tables(*plain.hb_tables(gp))
             try:
                 r = H.hci_pt2_stochastic(plain, gp, du, dd, dc, float(energy[i]), deck["eps_pt"], deck["eps_pt_big"], deck["n_mc"], deck["target_error"],
-                                         seed=deck["irand_seed"][0], log=lambda m: p("\n" + m))
+                                         seed=deck["irand_seed"][0], log=lambda m: p("\n" + m), on_device=pt_on_device)
             finally:
                 gp.close()
             de, nconn = r["pt_big"] + r["pt_diff"], r["n_connected_big"]
@@ -235,6 +236,8 @@ def main(argv=None):
                        ("dtm-elems", "the deterministic space and its Hamiltonian (dtm_elems_in/out_file, do_walk.f90:898-1010)")):
         ap.add_argument("--%s-in" % name, default=None, help="walk decks: read %s from this file instead of building it" % what)
         ap.add_argument("--%s-out" % name, default=None, help="walk decks: write %s to this file" % what)
+    ap.add_argument("--pt-on-device", action="store_true", help="HCI decks with n_mc > 0: evaluate every sample of the semistochastic PT in the library "
+                    "(sqmc_gpu_hci_pt2_stochastic_sample) instead of numpy on the raw connection list")
     a = ap.parse_args(argv)
     text = open(a.input).read() if a.input else sys.stdin.read()
     lines = [l for l in text.splitlines() if l.strip() and not l.lstrip().startswith("!")]
@@ -244,7 +247,7 @@ def main(argv=None):
         return run_walk(parse_walk_deck(text), a.fcidump, walkalize=a.walkalize, psit_con_in=a.psit_con_in, psit_con_out=a.psit_con_out,
                         dtm_elems_in=a.dtm_elems_in, dtm_elems_out=a.dtm_elems_out)
     deck = parse_hci_deck(text)
-    return run_hci(deck, a.fcidump)
+    return run_hci(deck, a.fcidump, pt_on_device=a.pt_on_device)
 
 
 if __name__ == "__main__":
