@@ -410,6 +410,11 @@ class GpuChem:
         _chk(self.L.sqmc_gpu_get_rng(self.h, s))
         return list(s)
 
+    def set_rng(self, seed):
+        """re-seeds the context from four 12-bit limbs (setrn: the last one made odd), in either RNG discipline"""
+        s = (C.c_int32 * 4)(*[int(x) for x in seed])
+        _chk(self.L.sqmc_gpu_set_rng(self.h, s))
+
     def set_timing(self, level=2):
         _chk(self.L.sqmc_gpu_set_timing(self.h, int(level)))
 
