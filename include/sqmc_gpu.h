@@ -41,6 +41,7 @@ typedef struct sqmc_gpu_ctx sqmc_gpu_ctx;
 #define SQMC_ERR_BAD_ARG -1
 #define SQMC_ERR_HIP -2
 #define SQMC_ERR_UNSUPPORTED -3
+#define SQMC_ERR_BREAKDOWN -4     /* sqmc_gpu_davidson: the iteration ended on something that is no eigen-solution (see there) */
 
 /* RNG discipline.  REPLAY reproduces the reference's single rannyu stream draw for draw
  * (rannyu.f90:54-74 consumed in walker order, do_walk.f90:3577-3583, chemistry.f90:4391-4439,
@@ -372,7 +373,16 @@ int sqmc_gpu_spmv_free(sqmc_spmv_plan *plan);
  * preconditioner, as sqmc_gpu_build_spmv_plan returns it); v0: n x n_states start vectors, column-major (initial_vector), or NULL for
  * unit vectors on the first rows (more_tools.f90:3113-3114: the HF determinant when it is listed first); tol: the reference's
  * epsilon = 1e-10 on the eigenvalues.  Out: evals[n_states], evecs[n x n_states] column-major (largest component of the small
- * problem's eigenvector positive), *n_matvec (may be NULL) the products it took. */
+ * problem's eigenvector positive), *n_matvec (may be NULL) the products it took.
+ * Where this differs from the reference: the reference normalises every orthogonalised correction vector, also one that is zero or
+ * rounding noise (start vectors that span an invariant subspace already: a diagonal matrix, a decoupled block, an exact eigenvector),
+ * and never diagonalises the last vectors of a basis of min(n, 50 n_states) vectors when that is no multiple of n_states; it then
+ * returns non-finite or wrong numbers.  Here the iteration ends on the basis it has when a correction is below 64 m 2^-53 of
+ * max(its own norm in front of the m projections, 1), or when the basis holds n vectors; n_states == n is solved from the start
+ * vectors alone.  A result reached in one of these ways, or through the reference's criterion on the correction vectors (their summed
+ * squared norms below 1e-12), is returned only if every state's residual bears that criterion out,
+ * |H x - e x|^2 <= 2e-12 (|H x|^2 + max diag^2); otherwise the call fails with SQMC_ERR_BREAKDOWN and a message, evals and evecs
+ * undefined.  The iterates themselves are the reference's throughout. */
 int sqmc_gpu_davidson(sqmc_spmv_plan *plan, const double *diag, int32_t n_states, const double *v0, double tol, double *evals, double *evecs, int32_t *n_matvec);
 /* generate_sparse_ham_chem_upper_triangular (chemistry.f90:7639-8010) and the plan of the Davidson
  * matvec in one call, with the matrix never leaving the GPU: for a determinant list sorted by

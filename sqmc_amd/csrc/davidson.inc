@@ -11,6 +11,19 @@
 // eigenvalues move by less than tol (epsilon = 1e-10, more_tools.f90:73) or the summed squared correction norms fall below 1e-12;
 // the 50-vectors-per-state basis is recycled from the current best vectors (2107-2125).
 //
+// Where this leaves the reference.  The reference normalises every orthogonalised correction, also one that is zero or rounding
+// noise (a start that already spans an invariant subspace: 1/sqrt(0), or a unit vector of noise that is not orthogonal to the basis),
+// and it diagonalises only after every k additions, so with min(n, 50 k) not a multiple of k the last vectors are never used.  Here
+//   - a correction that vanishes under the orthogonalisation (dv_breakdown) ends the iteration: the basis built so far is
+//     diagonalised, and the result is returned only if its residuals say it is an eigen-solution, else SQMC_ERR_BREAKDOWN;
+//   - a basis of n vectors spans everything: it is diagonalised whatever n mod k is, and that result is final;
+//   - n_states == n is solved by the k x k matrix of the start vectors;
+//   - a result reached through the reference's own criterion, summed |t|^2 < 1e-12, is returned only if its residuals bear that
+//     criterion out, else SQMC_ERR_BREAKDOWN (the last correction was rounding noise above the level of dv_breakdown, and the last
+//     diagonalisation left the state that had converged for a lower one).
+// The iterates are the reference's, bit for bit what they were: the first three events end the iteration where the reference's next
+// step is undefined, and the residual test changes no number, it only refuses a result.
+//
 // Sums: a dot product is a fixed tree -- lanes of a block by shuffles, blocks in index order --, the same on every run.
 
 #define DV_TPB 256
@@ -90,6 +103,33 @@ __global__ void __launch_bounds__(DV_TPB) dv_combine(const double *__restrict__ 
     }
 }
 
+// part_r[b], part_h[b]: this block's share of |Hw - e w|^2 and of |Hw|^2
+__global__ void __launch_bounds__(DV_TPB) dv_residual(const double *__restrict__ Hw, const double *__restrict__ w, double e, long long n,
+                                                      double *__restrict__ part_r, double *__restrict__ part_h) {
+  double r = 0.0, h = 0.0;
+  for (long long i = (long long)blockIdx.x * DV_TPB + threadIdx.x; i < n; i += (long long)gridDim.x * DV_TPB) {
+    const double x = Hw[i] - e * w[i];
+    r += x * x; h += Hw[i] * Hw[i];
+  }
+  r = dv_block_sum(r); h = dv_block_sum(h);
+  if (threadIdx.x == 0) { part_r[blockIdx.x] = r; part_h[blockIdx.x] = h; }
+}
+
+// Has the correction vanished under the orthogonalisation against m basis vectors?  before2, after2: its squared norm in front of and
+// behind the m projections.  Each projection t -= (t.v_j) v_j rounds every element once in the product and once in the difference, and
+// its coefficient comes from a dot product whose fixed tree (a strided serial part of at most a few terms, 6 shuffles, 4 waves, up to
+// 1024 partials in 4 + 8 steps) commits fewer than 30 roundings on the way of a term: fewer than 32 units of u = 2^-53 per projection,
+// relative to |t|.  Doubled for the two norms compared: 64 m u |t|.  What is left below that is what the projections themselves made,
+// not a direction; zero and non-finite norms are below it by definition.
+// An assumption, not a derivation, is the floor of 1 under |t|: t = (H w - e w)/(e - H_ii) is itself computed from the unit vector w,
+// and the rounding it inherits is u |e| / |e - H_ii| per element, which is of the size of u only where the preconditioner's denominators
+// are not small against |e| (below 1e-8 they are replaced by -1, which makes |t| >= 1).  With the floor the level is absolute, 64 m u,
+// for |t| < 1: at most 1e-12 at m = 150, six orders under the |t| = 1e-6 at which the iteration stops anyway.
+static bool dv_breakdown(double before2, double after2, int m) {
+  const double level = 64.0 * (double)std::max(m, 1) * 1.1102230246251565e-16;
+  return !(after2 > level * level * std::max(before2, 1.0));
+}
+
 // cyclic Jacobi on a symmetric m x m matrix (row-major a, destroyed); eigenvalues ascending in ev, eigenvectors in the columns of y (y[j + m s])
 static void dv_small_eigh(int m, std::vector<double> &a, std::vector<double> &ev, std::vector<double> &y) {
   std::vector<double> V((size_t)m * m, 0.0);
@@ -155,7 +195,7 @@ int sqmc_gpu_davidson(sqmc_spmv_plan *p, const double *diag, int32_t n_states, c
     if (n_matvec) (*n_matvec)++;
   };
   // orthogonalise t against V[:, 0..j_end) one after the other (part_a holds dot(t, V_0) on entry when j_end > 0), normalise into `out`
-  auto mgs_into = [&](int j_end, double *out) {
+  auto mgs_into = [&](int j_end, double *out) -> const double * {
     double *pin = part_a, *pout = part_b;
     for (int j = 0; j < j_end; j++) {
       hipLaunchKernelGGL(dv_mgs_step, dim3(nb), dim3(DV_TPB), 0, st, t, V + (size_t)j * n, pin, n, (j + 1 < j_end) ? V + (size_t)(j + 1) * n : (const double *)nullptr, pout);
@@ -163,6 +203,7 @@ int sqmc_gpu_davidson(sqmc_spmv_plan *p, const double *diag, int32_t n_states, c
     }
     if (j_end == 0) hipLaunchKernelGGL(dv_self_dot, dim3(nb), dim3(DV_TPB), 0, st, t, n, pin);
     hipLaunchKernelGGL(dv_normalize, dim3(nb), dim3(DV_TPB), 0, st, t, pin, out, n);
+    return (const double *)pin;                  // the partial sums of |t|^2 that were normalised by
   };
   // host value of m dot products: partial rows part_cols[j][0..nb) summed in block order
   auto read_dots = [&](int m, std::vector<double> &out) -> int {
@@ -171,7 +212,7 @@ int sqmc_gpu_davidson(sqmc_spmv_plan *p, const double *diag, int32_t n_states, c
     for (int j = 0; j < m; j++) { double s = 0.0; for (int q = 0; q < nb; q++) s += hpart[(size_t)j * nb + q]; out[j] = s; }
     return SQMC_OK;
   };
-  std::vector<double> hk((size_t)m_max * m_max, 0.0), low(k, 0.0), low_prev(k, INFINITY), res(k, 1.0), col;
+  std::vector<double> hk((size_t)m_max * m_max, 0.0), low(k, 0.0), low_prev(k, INFINITY), res(k, 1.0), col, hnorm((size_t)nb);
   // ---- start vectors
   if (v0) {
     for (int i = 0; i < k; i++) {
@@ -195,40 +236,75 @@ int sqmc_gpu_davidson(sqmc_spmv_plan *p, const double *diag, int32_t n_states, c
   for (int i = 0; i < k; i++) matvec(V + (size_t)i * n, HV + (size_t)i * n);
   { int r = seed_block(); if (r) return r; }
   HIPCHK(hipMemcpyAsync(W, V, (size_t)n * k * 8, hipMemcpyDeviceToDevice, st)); HIPCHK(hipMemcpyAsync(HW, HV, (size_t)n * k * 8, hipMemcpyDeviceToDevice, st));
-  bool converged = false;
+  bool converged = false, check = false;
   std::vector<double> a, ev, y;
-  for (long long it = k + 1; it <= (long long)niter * 10; it++) {
+  int m_ritz = k;                                        // W, HW and low stand for this many basis vectors
+  // Rayleigh-Ritz on the first m basis vectors: low, W, HW
+  auto ritz = [&](int m) -> int {
+    a.assign((size_t)m * m, 0.0);
+    for (int r = 0; r < m; r++) for (int c2 = 0; c2 < m; c2++) a[(size_t)r * m + c2] = hk[(size_t)r * m_max + c2];
+    dv_small_eigh(m, a, ev, y);
+    for (int s = 0; s < k; s++) low[s] = ev[s];
+    HIPCHK(hipMemcpyAsync(dy, y.data(), (size_t)m * k * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(dv_combine, dim3(nb), dim3(DV_TPB), 0, st, V, n, m, dy, k, W);
+    hipLaunchKernelGGL(dv_combine, dim3(nb), dim3(DV_TPB), 0, st, HV, n, m, dy, k, HW);
+    HIPCHK(hipStreamSynchronize(st));            // y is reused by the next diagonalisation
+    m_ritz = m;
+    return SQMC_OK;
+  };
+  if (k == n) { int r = ritz(k); if (r) return r; check = true; }      // the start vectors span everything
+  for (long long it = k + 1; !check && it <= (long long)niter * 10; it++) {
     const int itc = (int)((it - 1) % niter) + 1;
     if (it > niter && itc == 1) {            // recycle the basis from the current best vectors
       HIPCHK(hipMemcpyAsync(V, W, (size_t)n * k * 8, hipMemcpyDeviceToDevice, st)); HIPCHK(hipMemcpyAsync(HV, HW, (size_t)n * k * 8, hipMemcpyDeviceToDevice, st));
       int r = seed_block(); if (r) return r;
+      m_ritz = k;
       continue;
     }
     const int i = (itc - 1) % k;
     hipLaunchKernelGGL(dv_correction, dim3(nb), dim3(DV_TPB), 0, st, HW + (size_t)i * n, W + (size_t)i * n, low[i], dd, t, n,
                        (itc - 1 > 0) ? V : (const double *)nullptr, part_cols, (itc - 1 > 0) ? part_a : (double *)nullptr);
     HIPCHK(hipMemcpyAsync(hpart.data(), part_cols, (size_t)nb * 8, hipMemcpyDeviceToHost, st));      // read below, behind the kernels that follow
-    mgs_into(itc - 1, V + (size_t)(itc - 1) * n);
+    const double *pnorm = mgs_into(itc - 1, V + (size_t)(itc - 1) * n);
+    HIPCHK(hipMemcpyAsync(hnorm.data(), pnorm, (size_t)nb * 8, hipMemcpyDeviceToHost, st));          // |t|^2 behind the projections
     matvec(V + (size_t)(itc - 1) * n, HV + (size_t)(itc - 1) * n);
     HIPCHK(hipStreamSynchronize(st));
     { double s = 0.0; for (int q = 0; q < nb; q++) s += hpart[q]; res[i] = s; }
     { double s = 0.0; for (int q = 0; q < k; q++) s += res[q]; if (s < 1.0e-12) converged = true; }
+    { double s = 0.0; for (int q = 0; q < nb; q++) s += hnorm[q];
+      if (dv_breakdown(res[i], s, itc - 1)) {          // nothing to add: what the basis in front of this vector gives is all there is
+        if (itc - 1 > m_ritz) { int r = ritz(itc - 1); if (r) return r; }
+        check = true; break;
+      } }
     hipLaunchKernelGGL(dv_dots, dim3(nb), dim3(DV_TPB), 0, st, V, n, itc, HV + (size_t)(itc - 1) * n, part_cols);
     { int r = read_dots(itc, col); if (r) return r; }
     for (int j = 0; j < itc; j++) hk[(size_t)j * m_max + (itc - 1)] = hk[(size_t)(itc - 1) * m_max + j] = col[j];
-    if (itc % k == 0) {
-      a.assign((size_t)itc * itc, 0.0);
-      for (int r = 0; r < itc; r++) for (int c2 = 0; c2 < itc; c2++) a[(size_t)r * itc + c2] = hk[(size_t)r * m_max + c2];
-      dv_small_eigh(itc, a, ev, y);
-      for (int s = 0; s < k; s++) low[s] = ev[s];
-      HIPCHK(hipMemcpyAsync(dy, y.data(), (size_t)itc * k * 8, hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(dv_combine, dim3(nb), dim3(DV_TPB), 0, st, V, n, itc, dy, k, W);
-      hipLaunchKernelGGL(dv_combine, dim3(nb), dim3(DV_TPB), 0, st, HV, n, itc, dy, k, HW);
-      HIPCHK(hipStreamSynchronize(st));            // y is reused by the next diagonalisation
+    if (itc % k == 0 || itc == n) {
+      { int r = ritz(itc); if (r) return r; }
+      if (itc == n) { check = true; break; }       // n orthonormal vectors: the Krylov matrix is the matrix, nothing is left to add
       double move = 0.0;
       for (int s = 0; s < k; s++) move = std::max(move, fabs(low[s] - low_prev[s]));
       if (move < tol || converged) break;
       low_prev = low;
+    }
+  }
+  if (check || converged) {
+    // Return what the iteration ended on only if it is an eigen-solution by the reference's own criterion, summed |t|^2 < 1e-12.  With
+    // t_i = r_i / (e - H_ii) that criterion says |r|^2 <= max_i (e - H_ii)^2 1e-12 <= 2 (e^2 + max H_ii^2) 1e-12, and e^2 <= |H w|^2 for
+    // a unit w: |r|^2 <= 2e-12 (|H w|^2 + max H_ii^2).  A run that converged had this in front of its last diagonalisation, which
+    // refines the state and does not enlarge its residual; a run that ended on an event above never got to ask.
+    double dmax = 0.0; for (long long i = 0; i < n; i++) dmax = std::max(dmax, fabs(diag[i]));
+    for (int s = 0; s < k; s++) {
+      hipLaunchKernelGGL(dv_residual, dim3(nb), dim3(DV_TPB), 0, st, HW + (size_t)s * n, W + (size_t)s * n, low[s], n, part_a, part_b);
+      HIPCHK(hipMemcpyAsync(hpart.data(), part_a, (size_t)2 * nb * 8, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st));
+      double r2 = 0.0, h2 = 0.0;
+      for (int q = 0; q < nb; q++) { r2 += hpart[q]; h2 += hpart[(size_t)nb + q]; }
+      const double allowed = 2.0e-12 * (h2 + dmax * dmax);
+      if (!(r2 <= allowed) || !std::isfinite(low[s])) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "Davidson: the iteration ended with state %d of %d not an eigen-solution (|Hx - ex|^2 = %.3g, allowed %.3g)", s + 1, k, r2, allowed);
+        return fail(SQMC_ERR_BREAKDOWN, msg);
+      }
     }
   }
   HIPCHK(hipGetLastError());
