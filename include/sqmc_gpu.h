@@ -423,8 +423,12 @@ int sqmc_gpu_propose_batch(sqmc_gpu_ctx *ctx, int64_t n, double tau, const uint6
 /* replaces: find_doubly_excited + find_important_connected_dets_chem + sort/dedup
  * (semistoch.f90:1750-2131, chemistry.f90:6819-7159, tools.f90:577-660) as used by
  * get_next_det_list (hci.f90:865) and generate_psi_t_connected_e_loc (semistoch.f90:27):
- * for n_ref reference dets with coefficients coeffs, all connections with
- * |H| >= eps/|c| (the reference det itself included), sorted by (up,dn), duplicates merged:
+ * for n_ref reference dets with coefficients coeffs, the connections that pass the screen at eps/|c|, per class as the
+ * reference has it: single excitations with |H| >= eps/|c| (chemistry.f90:6956, a tie is kept), chemistry doubles with
+ * |H| > eps/|c| (chemistry.f90:7042, a tie is dropped; none when eps/|c| > max_double, :6995), HEG doubles with |H| > eps/|c|
+ * (heg.f90:2608, 2629); H is the raw element, before the time-reversal factors.  The reference det itself is included, except
+ * that a det with c == 0 contributes nothing, its own slot included (the generator is not called for it, semistoch.f90:1762,
+ * 1798, 1854, 1891).  Sorted by (up,dn), duplicates merged:
  * e_mix_num = sum_j H_ij c_j, e_mix_den = c_i on the reference determinants, else 0
  * (semistoch.f90:2039-2063).  diag_mode 0: the self slot carries H=0 (HCI, chemistry.f90:6896);
  * 1: it carries H_ii (find_connected_dets_chem, chemistry.f90:6574-6576, for C(T));

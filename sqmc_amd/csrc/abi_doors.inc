@@ -392,8 +392,11 @@ static int hci_connections_impl(sqmc_gpu_ctx *c, int64_t n_ref, const uint64_t *
   device_excl_scan_u64(dcnt, doff, n_ref, dtot, sw, st);
   u64 total = 0;
   HIPCHK(hipMemcpyAsync(&total, dtot, 8, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st));
-  if (total >= (1ull << 31)) return fail(SQMC_ERR_UNSUPPORTED, "more than 2^31 connections in one call: use more slices (sqmc_gpu_hci_connections_slice)");
-  if (total == 0) { void *fz[] = {dru, drd, dco, dcnt, doff, dtot, dts}; for (void *q : fz) hipFree(q); return SQMC_OK; }
+  if (total >= (1ull << 31) || total == 0) {          // both early returns release what the count pass allocated
+    void *fz[] = {dru, drd, dco, dcnt, doff, dtot, dts}; for (void *q : fz) hipFree(q);
+    if (total == 0) return SQMC_OK;
+    return fail(SQMC_ERR_UNSUPPORTED, "more than 2^31 connections in one call: use more slices (sqmc_gpu_hci_connections_slice)");
+  }
   const long long T = (long long)total;
   u64 *du, *dd, *keys, *kalt, *flags, *pos, *ou, *od, *dts2, *dtot2; u32 *vals, *valt, *hist, *rowtot; double *dnum, *dden, *onum, *oden;
   HIPCHK(hipMalloc(&du, T * 8)); HIPCHK(hipMalloc(&dd, T * 8)); HIPCHK(hipMalloc(&dnum, T * 8)); HIPCHK(hipMalloc(&dden, T * 8));

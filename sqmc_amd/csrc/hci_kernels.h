@@ -7,6 +7,8 @@
 // find_important_connected_dets_chem, chemistry.f90:6819-7159: one thread per reference
 // determinant; pass 0 counts, pass 1 writes at the scanned offsets.  Emits (up, dn,
 // H_ij*c_j, e_mix_den) with the reference determinant itself in slot 0.
+// A reference determinant with c == 0 emits nothing, slot 0 included: find_doubly_excited does not call the generator for
+// it (semistoch.f90:1762, 1798, 1854, 1891).
 __global__ void __launch_bounds__(TPB) k_hci_gen(ChemDev dev, const u64 *__restrict__ rup, const u64 *__restrict__ rdn, const double *__restrict__ coef,
                                                  double eps_var, int diag_mode, long long n_ref, int pass, u64 *__restrict__ counts,
                                                  const u64 *__restrict__ offs, u64 *__restrict__ ou, u64 *__restrict__ od,

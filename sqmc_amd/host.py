@@ -707,7 +707,7 @@ def hci_variational(host, g, eps_var, eps_sched=(), n_states=1, max_iters=50, lo
         if it <= len(sched):
             eps = sched[it - 1]
         coeffs = np.abs(wts).max(axis=1) if it > 1 else wts[:, 0].copy()
-        cu, cd, _, _ = g.hci_connections(up, dn, coeffs, eps)              # sorted, unique, includes the old list
+        cu, cd, _, _ = g.hci_connections(up, dn, coeffs, eps)              # sorted, unique; holds every old determinant whose coefficient is not 0 (semistoch.f90:1762): only the new ones are taken
         # append the new determinants behind the old list in sorted order (hci.f90:979-991)
         is_new = ~_dets_in(cu, cd, up, dn)
         n_old, n_new = len(up), len(up) + int(is_new.sum())
