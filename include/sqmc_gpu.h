@@ -344,6 +344,12 @@ int sqmc_gpu_shard_time_split(sqmc_gpu_ctx *ctx, double us[4], int64_t *steps, i
 /* How many steps took the short-list tail (block-local partition + one annihilation kernel per key range, no global sort) and
  * how many of those had to be re-run through the radix tail because a key range outgrew its block (diagnostics, tests). */
 int sqmc_gpu_tail_stats(sqmc_gpu_ctx *ctx, int64_t *bucket_steps, int64_t *bucket_retries);
+/* Which tail the LAST step (sqmc_gpu_step, a step of sqmc_gpu_run, sqmc_gpu_annihilate, a sharded finish) took (diagnostics, tests):
+ * info[0] 0 = radix tail, 1 = short-list (bucket) tail, 2 = bucket tail that gave up and was re-run through the radix tail;
+ * info[1] sorted slots per thread of the annihilation kernel that produced the list (2, 3 or 4; 0 for the bucket kernel and for a
+ *         step that is not semistochastic);  info[2] 1 if only the spawns were sorted and merged into the ordered residents;
+ * info[3] 1 if sort keys and walker indices share one 64-bit word (keys of at most 32 bits), 0 for the two-array layout. */
+int sqmc_gpu_last_tail(sqmc_gpu_ctx *ctx, int32_t info[4]);
 /* A host that runs the walk in blocks (nstep steps, then its block statistics: do_walk.f90:2171 inside the iblk loop, 2086-3300)
  * calls sqmc_gpu_run once per block.  With chained runs on, the last step of a call enqueues the head (gate, child offsets, spawn)
  * of the first step of the NEXT call behind its own tail, as every other step of the call does for its successor, so the GPU keeps

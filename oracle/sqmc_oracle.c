@@ -1181,6 +1181,22 @@ static void search_list_and_update(orc_walk *w, int64_t n, double acc[7]) {
   }
 }
 
+/* the sums over the finished generation, do_walk.f90:2573-2598 and 2755-2759 (hf_to_psit = .false.): entries 0-6 and 8-13 of a
+ * step's out[16]; 7, 14 and 15 are the caller's (set to 0 here) */
+void orc_generation_sums(orc_walk *w, int64_t n, const orc_step_params *p, double out[16]) {
+  double w_gen = 0, w2 = 0, w_abs = 0, w_abs_imp = 0, w_perm = 0; int ip = 0;      /* 2573-2598 */
+  for (int64_t i = 0; i < n; i++) {
+    if (w->initiator[i] == 3) w_perm += w->wt[i] * w->sign_perm[ip++];
+    w_gen += w->wt[i]; w2 += w->wt[i] * w->wt[i]; w_abs += fabs(w->wt[i]);
+    if (w->imp_distance[i] == 0 || (w->imp_distance[i] == -2 && p->c_t_initiator)) w_abs_imp += fabs(w->wt[i]);
+  }
+  double acc[7] = {0, 0, 0, 0, 0, 0, 0};
+  search_list_and_update(w, n, acc);               /* 2755-2759 */
+  out[0] = w_gen; out[1] = w_abs; out[2] = acc[1]; out[3] = acc[0]; out[4] = w_perm; out[5] = (double)n;
+  out[6] = w_abs_imp; out[7] = 0; out[8] = w2; out[9] = acc[2]; out[10] = acc[3];
+  out[11] = acc[4]; out[12] = acc[5]; out[13] = acc[6]; out[14] = 0; out[15] = 0;
+}
+
 /* One MC step, do_walk.f90:2186-2790 for semistochastic chem, ncores=1, hf_to_psit=.false.,
  * run_type 'none'.  Population control (2880-2901) stays with the caller. */
 static int walk_step_sys(const orc_sys *s, orc_walk *w, const orc_step_params *p, double out[16]);
@@ -1245,17 +1261,8 @@ static int walk_step_sys(const orc_sys *s, orc_walk *w, const orc_step_params *p
   LAP(4);
   for (int64_t i = 0; i < n; i++) w->wt[i] = w->wt[i] * p->reweight_factor_inv;   /* 2487 */
   if (n == 0) return 4;
-  double w_gen = 0, w2 = 0, w_abs = 0, w_abs_imp = 0, w_perm = 0; int ip = 0;      /* 2573-2598 */
-  for (int64_t i = 0; i < n; i++) {
-    if (w->initiator[i] == 3) w_perm += w->wt[i] * w->sign_perm[ip++];
-    w_gen += w->wt[i]; w2 += w->wt[i] * w->wt[i]; w_abs += fabs(w->wt[i]);
-    if (w->imp_distance[i] == 0 || (w->imp_distance[i] == -2 && p->c_t_initiator)) w_abs_imp += fabs(w->wt[i]);
-  }
-  double acc[7] = {0, 0, 0, 0, 0, 0, 0};
-  search_list_and_update(w, n, acc);               /* 2755-2759 */
-  out[0] = w_gen; out[1] = w_abs; out[2] = acc[1]; out[3] = acc[0]; out[4] = w_perm; out[5] = (double)n;
-  out[6] = w_abs_imp; out[7] = (double)nbefore; out[8] = w2; out[9] = acc[2]; out[10] = acc[3];
-  out[11] = acc[4]; out[12] = acc[5]; out[13] = acc[6]; out[14] = wabs_before; out[15] = (double)attempts;
+  orc_generation_sums(w, n, p, out);               /* 2573-2598, 2755-2759 */
+  out[7] = (double)nbefore; out[14] = wabs_before; out[15] = (double)attempts;
   w->rng.step++;
   LAP(5);
 #undef LAP

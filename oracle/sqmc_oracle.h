@@ -173,6 +173,7 @@ void orc_djb_hash(uint64_t up_lo, uint64_t up_hi, uint64_t dn_lo, uint64_t dn_hi
 int  orc_get_det_owner(uint64_t up_lo, uint64_t up_hi, uint64_t dn_lo, uint64_t dn_hi, int ncores);
 int64_t orc_merge_original_with_spawned2(orc_walk *w, int64_t n, const orc_step_params *p); /* 5866-6083 */
 int64_t orc_reduce_my_walker(orc_walk *w, int64_t n, const orc_step_params *p);            /* 7196-7254 */
+void orc_generation_sums(orc_walk *w, int64_t n, const orc_step_params *p, double out[16]);     /* 2573-2598, 2755-2759 */
 int64_t orc_join_walker2(orc_walk *w, int64_t n, const orc_step_params *p);                /* 6990-7103 */
 
 #endif

@@ -226,6 +226,7 @@ struct sqmc_gpu_ctx {
   BucketArgs head_ba; long long last_nall;      // partition already done by the head's k_spawn (B > 0), and the length of the last sorted list (sizes the next one)
   int bk_holdoff;             // steps for which the bucket tail stays off (after a bucket overflowed or came close)
   long long bk_steps, bk_retries;
+  int lt_kind, lt_items, lt_merge, lt_pack;      // the tail the last step took (sqmc_gpu_last_tail)
   u32 *d_bpar; bool head_bpar_ok;      // parent of the first child of every block of 256 children, written beside the child offsets; valid for the head that follows
   AnnealStage stage; void *stage_mem; long long stage_cap;      // long lists: staging buffer of the two-kernel annihilation (k_anneal<., 0, 1> + k_anneal_place), allocated at first use
   double sh_us[4]; long long sh_steps;      // host wall clock of the in-library sharded steps: head, exchange, tail, of which waiting for the GPU's mail (sqmc_gpu_shard_time_split)
@@ -708,6 +709,11 @@ int sqmc_gpu_tail_stats(sqmc_gpu_ctx *c, int64_t *bucket_steps, int64_t *bucket_
   *bucket_steps = c->bk_steps; *bucket_retries = c->bk_retries;
   return SQMC_OK;
 }
+int sqmc_gpu_last_tail(sqmc_gpu_ctx *c, int32_t info[4]) {
+  if (!c || !info) return fail(SQMC_ERR_BAD_ARG, "null argument");
+  info[0] = c->lt_kind; info[1] = c->lt_items; info[2] = c->lt_merge; info[3] = c->lt_pack;
+  return SQMC_OK;
+}
 int sqmc_gpu_get_rng(sqmc_gpu_ctx *c, int32_t seed[4]) {
   if (!c) return SQMC_ERR_BAD_ARG;
   u64 x; HIPCHK(hipStreamSynchronize(c->st)); HIPCHK(hipMemcpy(&x, &c->d_sc->lcg, 8, hipMemcpyDeviceToHost));
@@ -1101,8 +1107,10 @@ static int step_tail_impl(sqmc_gpu_ctx *c, const StepP &p_in, long long n0, long
     c->side_pending = false;
     int rs = launch_side_kernels(c, p, n0, true); if (rs) return rs;
   }
+  c->lt_kind = bucket ? 1 : 0; c->lt_items = 0; c->lt_pack = c->pack; c->lt_merge = 0;
   if (bucket) {
   } else if (p.semi && c->residents_sorted && nall >= merge_min) {
+    c->lt_merge = (nall > n0) ? 1 : 0;
     // Large lists: the walkers [0, n0) are in order already (every step leaves them so), so only the spawns
     // [n0, nall) are sorted and one stable merge (walker before spawns on equal keys, spawns in creation order)
     // gives the order the full sort would.  The merged list lands in the flag arrays the fused tail does not use.
@@ -1140,6 +1148,7 @@ static int step_tail_impl(sqmc_gpu_ctx *c, const StepP &p_in, long long n0, long
     if (items < 3 && getenv("SQMC_ANNEAL_SPLIT_MIN") && nall >= atoll(getenv("SQMC_ANNEAL_SPLIT_MIN"))) items = 3;      // (tests: the two-kernel form exists for 3 and 4 slots per thread)
     if (c->psit_on) items = items <= 2 ? 2 : 3;          // the two shapes k_anneal<., 1> is instantiated with
     nb = n_ft = bucket ? ba.B : (int)((nall + (long long)TPB * items - 1) / ((long long)TPB * items));
+    if (!bucket) c->lt_items = items;
     // pipelined steps: the kernel also does the next step's gate (keys, child counts, child weights) as it places a walker
     static const bool no_fuse = getenv("SQMC_NO_GATE_FUSION") != nullptr;
     static const bool no_psit_fuse = getenv("SQMC_PSIT_NO_GATE_FUSION") != nullptr;
@@ -1354,7 +1363,7 @@ static int step_tail_impl(sqmc_gpu_ctx *c, const StepP &p_in, long long n0, long
 
 static int step_tail(sqmc_gpu_ctx *c, const StepP &p, long long n0, long long nall, bool join_side_stream, double out[16]) {
   int r = step_tail_impl(c, p, n0, nall, join_side_stream, out, true);
-  if (r == SQMC_INTERNAL_RETRY) r = step_tail_impl(c, p, n0, nall, false, out, false);
+  if (r == SQMC_INTERNAL_RETRY) { r = step_tail_impl(c, p, n0, nall, false, out, false); c->lt_kind = 2; }
   return r;
 }
 
