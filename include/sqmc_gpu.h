@@ -278,7 +278,22 @@ int sqmc_gpu_annihilate(sqmc_gpu_ctx *ctx, const sqmc_step_params *p, int64_t n_
  *   shard_finish  received records appended; sort, annihilation, rounding, estimator sums
  *     [host: all-reduce SUM of out_stats[0..6]]               (mpi_allred, do_walk.f90:2778)
  * set_projector takes the GLOBAL projector on every rank; shard_config gives, for the k-th
- * deterministic-space walker this rank owns (in its sorted order), its row in that matrix. */
+ * deterministic-space walker this rank owns (in its sorted order), its row in that matrix.
+ *
+ * Proposal: the sharded steps spawn with the context's proposal -- uniform, CauchySchwarz, or fast_heatbath once its tables are set
+ * (sqmc_gpu_set_heatbath_tables / sqmc_gpu_setup_efficient_heatbath, before or after sqmc_gpu_shard_config; COUNTER discipline only).
+ * A fast_heatbath child holds TWO walker slots, the single and the double excitation of one proposal (do_walk.f90:3604-3611), so a
+ * step of nch children has spc * nch spawn slots, spc = 2 (1 for every other proposal):
+ *   - capacity: nwalk + spc * nch > MWALK stops the step with SQMC_ERR_MWALK ("nwalk>MWALK"), as in sqmc_gpu_step, also for a
+ *     pipelined head of sqmc_gpu_shard_run; with a communicator the stop is collective;
+ *   - records: every slot that holds a walker becomes one 32-byte record, routed by the owner of ITS determinant (the two slots
+ *     of a child may go to different ranks); empty slots are neither counted in send_counts nor sent, so a step sends at most
+ *     spc * nch records.  Inside a destination the records keep slot order.  sqmc_gpu_shard_pack with cap_records smaller than
+ *     the records to send gives SQMC_ERR_SPAWN_OVERFLOW before anything is written.  The in-library step stages all slots, the
+ *     empty ones behind the last rank's, so its check is the conservative one: spc * nch slots against its staging buffer of
+ *     MWALK records (which the capacity rule above already guarantees);
+ *   - *n_children and out_stats[15] count children (proposals), not slots.
+ * fast_heatbath together with sqmc_gpu_set_hf_to_psit_shard is refused (SQMC_ERR_UNSUPPORTED), in either order of the calls. */
 int sqmc_gpu_det_owner(sqmc_gpu_ctx *ctx, int64_t n, const uint64_t *up, const uint64_t *dn, int32_t nranks, int32_t *owner);
 /* Which hash decides ownership.  0 (default): a mix of the determinant's sort key (cheapest).  1: the reference's own
  * get_det_owner -> hash -> djb_hash (mpi_routines.f90:419-445, 257-289, 354-379) bit for bit, so that ranks running the

@@ -223,10 +223,11 @@ int sqmc_gpu_propose_batch(sqmc_gpu_ctx *c, int64_t n, double tau, const uint64_
 }
 
 int sqmc_gpu_set_heatbath_tables(sqmc_gpu_ctx *c, const sqmc_heatbath_tables *t) {
-  abandon_head(c);          // a head enqueued with one walker slot per child must not meet a tail that counts two
+  abandon_head(c);          // a head enqueued with one walker slot per child must not meet a tail that counts two (a sharded run's pipelined head too)
   if (!c || !t) return fail(SQMC_ERR_BAD_ARG, "null argument");
   if (c->dev.cs.on) return fail(SQMC_ERR_BAD_ARG, "the context already proposes by Cauchy-Schwarz (sqmc_gpu_setup_cauchy_schwarz)");
   if (c->htab.sys_type != 0) return fail(SQMC_ERR_UNSUPPORTED, "the efficient heat-bath proposal is a 'chem' proposal");
+  if (c->psit_shard) return fail(SQMC_ERR_UNSUPPORTED, "hf_to_psit with proposal_method fast_heatbath is not built");      // as sqmc_gpu_set_hf_to_psit_shard refuses the other order
   if (t->norb != c->htab.norb) return fail(SQMC_ERR_BAD_ARG, "norb of the tables differs from the context's");
   const int n = t->norb; const long long npairs = ((long long)n * (n - 1)) / 2 + n;
   if (t->size_same != (npairs - 1) * n * n + (long long)(n - 1) * n + n || t->size_opposite != (long long)n * n * n * n)

@@ -60,12 +60,13 @@ __global__ void __launch_bounds__(TPB) k_prj_finish_rows(const double *__restric
   double y = yv[i];
   y = y + e_trial * tau * xg[row]; wt[loc[i]] = wt[loc[i]] + y;
 }
-// destination rank of every child (nranks = "no walker": weight 0), as an 8-bit sort key
+// destination rank of every spawn slot (nranks = "no walker": weight 0), as an 8-bit sort key; a slot is a child, or with
+// fast_heatbath one of a child's two walker slots (each routed by its own determinant: the two may go to different ranks)
 // (koff: hf_to_psit's offset of the sort keys outside C(T), taken off again -- the owner is the determinant's)
 __global__ void __launch_bounds__(TPB) k_child_owner(WalkArr w, const u64 *__restrict__ keys, u64 *__restrict__ okey, u32 *__restrict__ oval,
-                                                     long long n0, long long nch, u64 invalid_key, int nranks, int pack, int mode, u64 koff) {
+                                                     long long n0, long long nslot, u64 invalid_key, int nranks, int pack, int mode, u64 koff) {
   long long c = (long long)blockIdx.x * TPB + threadIdx.x;
-  if (c >= nch) return;
+  if (c >= nslot) return;
   u64 k = get_key(keys, n0 + c, pack);
   if (koff && k != invalid_key && k >= koff) k -= koff;
   u64 o = (u64)nranks;
@@ -254,11 +255,12 @@ static int shard_begin_impl(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double 
   if (wr == 0) nch = (long long)c->h_mail->n_children;
   else if (n0 > 0) { u64 v; HIPCHK(hipMemcpyAsync(&v, &c->d_sc->n_children, 8, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st)); nch = (long long)v; }
   if (full_sync) HIPCHK(hipStreamSynchronize(st));      // the caller's collective library reads x_global on its own stream
-  if (n0 + nch > M) {
+  const long long spc = c->dev.hb.on ? 2 : 1;          // walker slots per child (fast_heatbath: two), as in sqmc_gpu_step
+  if (n0 + spc * nch > M) {      // (k_spawn checked the same on the device and wrote nothing, a pipelined head's included)
     hipMemset(c->d_scan_state, 0, 3 * c->cap_tiles * 8); hipMemset(c->d_scan_ticket, 0, 3 * 4);
     return fail(SQMC_ERR_MWALK, "nwalk>MWALK");
   }
-  c->shard_n0 = n0; c->shard_nch = nch;
+  c->shard_n0 = n0; c->shard_nch = nch; c->shard_nslot = spc * nch;
   *n_children = nch;
   return SQMC_OK;
 }
@@ -268,15 +270,16 @@ int sqmc_gpu_shard_begin(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double *x_
 }
 
 // phase 2: apply the owned rows of the deterministic projection with the all-reduced x_global, then
-// bucket this step's children by owner rank (stable) into 32-byte records: send_counts[r] records
-// for rank r, contiguous in rank order in send_dev (capacity cap_records).
+// bucket this step's spawn slots by owner rank (stable) into 32-byte records: send_counts[r] records
+// for rank r, contiguous in rank order in send_dev (capacity cap_records).  A step has shard_nslot = spc * nch
+// slots: one per child, two with fast_heatbath (the single and the double excitation of a proposal).
 //
-// device part of phase 2; leaves the per-destination counts in d_rowtot[0..P) (valid when nch > 0)
-// and the permutation of the children by destination in *order.  Children that produced no
-// walker sort behind the last rank.
+// device part of phase 2; leaves the per-destination counts in d_rowtot[0..P) (valid when there are slots)
+// and the permutation of the slots by destination in *order.  Slots that hold no
+// walker sort behind the last rank: they are neither counted nor sent.
 static int shard_bucket(sqmc_gpu_ctx *c, const sqmc_step_params *sp, const double *x_global_dev, u32 **order, bool apply_rows = true) {
   hipStream_t st = c->st;
-  const long long n0 = c->shard_n0, nch = c->shard_nch; const int P = c->shard_n;
+  const long long n0 = c->shard_n0, nsl = c->shard_nslot; const int P = c->shard_n;
   if (apply_rows && c->psit_shard) { int r = psit_shard_project(c, sp, x_global_dev); if (r) return r; }
   else if (apply_rows && c->n_imp_local > 0 && c->shard_y_used)
     hipLaunchKernelGGL(k_prj_finish_rows, dim3(nblk(c->n_imp_local)), dim3(TPB), 0, st, (const double *)c->d_prj_y, x_global_dev, c->d_loc_imp, c->d_grow, c->w.wt, c->n_imp_local, sp->e_trial, sp->tau);
@@ -284,12 +287,12 @@ static int shard_bucket(sqmc_gpu_ctx *c, const sqmc_step_params *sp, const doubl
     hipLaunchKernelGGL(k_prj_apply_rows, dim3(nblk(c->n_imp_local, TPB / 64)), dim3(TPB), 0, st, c->d_prj_ptr, c->d_prj_col, c->d_prj_val, x_global_dev,
                        c->d_loc_imp, c->d_grow, c->w.wt, c->n_imp_local, sp->e_trial, sp->tau);
   *order = nullptr;
-  if (nch > 0) {
+  if (nsl > 0) {
     u64 *okey = c->d_flags, *okey_alt = c->d_pos; u32 *oval = (u32 *)c->d_flags2, *oval_alt = (u32 *)c->d_pos2;
-    if (!c->owner_ready) hipLaunchKernelGGL(k_child_owner, dim3(nblk(nch)), dim3(TPB), 0, st, c->w, c->d_keys, okey, oval, n0, nch, c->invalid_key, P, c->pack, c->owner_mode, c->dev.ps.koff);
+    if (!c->owner_ready) hipLaunchKernelGGL(k_child_owner, dim3(nblk(nsl)), dim3(TPB), 0, st, c->w, c->d_keys, okey, oval, n0, nsl, c->invalid_key, P, c->pack, c->owner_mode, c->dev.ps.koff);
     SortWork so; so.k_alt = okey_alt; so.v_alt = oval_alt; so.hist = c->d_hist; so.rowtot = c->d_rowtot; so.cap = c->mwalk;
     u64 *sk = okey; u32 *sv = oval;
-    device_radix_sort(sk, sv, nch, 8, so, st, 0, true);      // one stable 8-bit pass (also for a single child); rowtot[d] = children per destination
+    device_radix_sort(sk, sv, nsl, 8, so, st, 0, true);      // one stable 8-bit pass (also for a single slot); rowtot[d] = records per destination
     *order = sv;
   }
   c->owner_ready = false;
@@ -301,11 +304,11 @@ int sqmc_gpu_shard_pack(sqmc_gpu_ctx *c, const sqmc_step_params *sp, const doubl
                         int64_t *send_counts) {
   if (!c || !sp || !send_counts) return fail(SQMC_ERR_BAD_ARG, "null argument");
   hipStream_t st = c->st;
-  const long long n0 = c->shard_n0, nch = c->shard_nch; const int P = c->shard_n;
+  const long long n0 = c->shard_n0, nsl = c->shard_nslot; const int P = c->shard_n;
   u32 *order;
   int r = shard_bucket(c, sp, x_global_dev, &order); if (r) return r;
   for (int q = 0; q < P; q++) send_counts[q] = 0;
-  if (nch > 0) {
+  if (nsl > 0) {
     u32 cnt[256];
     HIPCHK(hipMemcpyAsync(cnt, c->d_rowtot, 256 * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -555,7 +558,7 @@ static int shard_step_impl(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double o
   int local = shard_begin_impl(c, sp, c->d_xg, &nch, false, side, diag_side);
   if (local < 0) return local;                     // argument / HIP failures are not walk statuses: nothing collective can be said about them
   const std::string local_msg = local ? g_err : std::string();
-  if (local) { c->shard_n0 = c->nwalk; c->shard_nch = 0; }
+  if (local) { c->shard_n0 = c->nwalk; c->shard_nch = 0; c->shard_nslot = 0; }
   t_us[1] = now_us();
   {   // deterministic projection: all-reduce of the weights, then the rows this rank owns
     hipStream_t sx = side ? c->st2 : st;
@@ -567,16 +570,18 @@ static int shard_step_impl(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double o
       HIPCHK(hipEventRecord(c->e_join, sx));
     }
   }
-  // bucket + pack without a host round trip: every child is packed in destination order (the
+  // bucket + pack without a host round trip: every spawn slot is packed in destination order (the
   // ones that made no walker sort last and are never sent), the counts stay on the device and go
   // straight into the all-gather that tells every rank who sends how much to whom
   u32 *order = nullptr;
   if (!local) { int r = shard_bucket(c, sp, c->d_xg, &order, !side); if (r) return r; }
-  const long long nch_l = c->shard_nch;
-  if (!local && nch_l > c->xch_cap) { local = fail(SQMC_ERR_SPAWN_OVERFLOW, "send buffer too small for this step's spawns"); }
+  // slots, not children (two per child with fast_heatbath), and slots, not records: the empty ones are packed behind the last rank's
+  // and never sent, so the staging buffer is checked against the slot count -- conservative, never a short write
+  const long long nsl_l = c->shard_nslot;
+  if (!local && nsl_l > c->xch_cap) { local = fail(SQMC_ERR_SPAWN_OVERFLOW, "send buffer too small for this step's spawns"); }
   // the per-destination counts are the digit totals the bucketing pass left in d_rowtot
   const u32 room = (u32)std::min<long long>(c->mwalk - c->shard_n0, 0x7FFFFFFFll);
-  if (!local && nch_l > 0) hipLaunchKernelGGL(k_pack_send, dim3(nblk(nch_l)), dim3(TPB), 0, st, c->w, order, c->d_send, c->shard_n0, nch_l, (const u32 *)c->d_rowtot, P, room, c->d_cnt_mine);
+  if (!local && nsl_l > 0) hipLaunchKernelGGL(k_pack_send, dim3(nblk(nsl_l)), dim3(TPB), 0, st, c->w, order, c->d_send, c->shard_n0, nsl_l, (const u32 *)c->d_rowtot, P, room, c->d_cnt_mine);
   else hipLaunchKernelGGL(k_fill_counts, dim3(1), dim3(256), 0, st, (const u32 *)nullptr, P, (u32)local, room, c->d_cnt_mine);
   NCCLCHK(g_rccl.AllGather(c->d_cnt_mine, c->d_cnt_all, (size_t)ROW, ncclUint32, c->comm, st));
   {

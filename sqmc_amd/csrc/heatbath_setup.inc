@@ -38,6 +38,7 @@ int sqmc_gpu_setup_efficient_heatbath(sqmc_gpu_ctx *c, int32_t *is_heatbath_unbi
   if (!c) return fail(SQMC_ERR_BAD_ARG, "null ctx");
   if (c->htab.sys_type != 0) return fail(SQMC_ERR_UNSUPPORTED, "the efficient heat-bath proposal is a 'chem' proposal");
   if (c->dev.cs.on) return fail(SQMC_ERR_BAD_ARG, "the context already proposes by Cauchy-Schwarz (sqmc_gpu_setup_cauchy_schwarz)");
+  if (c->psit_shard) return fail(SQMC_ERR_UNSUPPORTED, "hf_to_psit with proposal_method fast_heatbath is not built");
   const int n = c->htab.norb, nc = c->htab.ncore;
   const long long n2 = (long long)n * n, n3 = n2 * n;
   HbHost *H = new HbHost();

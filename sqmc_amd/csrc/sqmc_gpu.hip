@@ -181,7 +181,7 @@ struct sqmc_gpu_ctx {
   int key_bits; int pack; u64 invalid_key; u64 *d_binom;
   // multi-rank sharding (owner = hash(det) mod shard_n)
   int owner_mode;             // SQMC_OWNER_MIX (default) or SQMC_OWNER_DJB (the reference's get_det_owner, bit for bit)
-  int shard_rank, shard_n; int *d_grow; int *d_ginv; long long n_imp_local; long long shard_n0, shard_nch;
+  int shard_rank, shard_n; int *d_grow; int *d_ginv; long long n_imp_local; long long shard_n0, shard_nch, shard_nslot;      // shard_nslot: spawn slots of the step (children, or two per child with fast_heatbath)
   // in-library exchange over RCCL (sqmc_gpu_comm_init): communicator + device staging
   ncclComm_t comm, comm2; double *d_xg; u64 *d_send, *d_recv; long long xch_cap; u32 *d_cnt_mine, *d_cnt_all; u32 *h_cnt_all, *d_cnt_mail;
   u64 cntall_seq;      // comm2: second communicator (ncclCommSplit) for the all-reduce that runs on the side stream

@@ -795,24 +795,32 @@ class ShardedWalk:
     def __init__(self, host, w_target, rank, world, w_begin=None, mwalk=None, n_truncate_trial_wf=100, size_deterministic=1000,
                  tau_multiplier=0.1, e_trial=None, seed=(1346, 5634, 6635, 4361), min_wt=0.5, device_index=0, n_equil_steps=10**9, owner_hash=0,
                  semistochastic=True, hf_to_psit=False, sum_order=1, proposal="uniform"):
-        """proposal: "uniform" (the system's own) or "cauchyschwarz" (chem: proposal_method CauchySchwarz)"""
+        """proposal: "uniform" (the system's own), "cauchyschwarz" (chem: proposal_method CauchySchwarz) or "heatbath" (chem:
+        proposal_method fast_heatbath; every rank builds the tables, a child holds two walker slots)"""
         import torch
         self.rank, self.world, self.min_wt = rank, world, min_wt
         self.psit = bool(hf_to_psit)
-        if proposal not in ("uniform", "cauchyschwarz"):
-            raise ValueError("ShardedWalk: proposal %r (uniform or cauchyschwarz)" % (proposal,))
+        if proposal not in ("uniform", "cauchyschwarz", "heatbath"):
+            raise ValueError("ShardedWalk: proposal %r (uniform, cauchyschwarz or heatbath)" % (proposal,))
         if proposal == "cauchyschwarz" and self.psit:
             raise ValueError("proposal_method CauchySchwarz with hf_to_psit = t is not built")
-        pkw = {"proposal": proposal} if proposal != "uniform" else {}
+        if proposal == "heatbath" and self.psit:
+            raise ValueError("proposal_method fast_heatbath with hf_to_psit = t is not built")
+        pkw = {"proposal": proposal} if proposal == "cauchyschwarz" else {}
         if self.psit and not semistochastic:
             raise ValueError("hf_to_psit needs a semistochastic walk")
         self.semi = 1 if semistochastic else 0          # 0: semistochastic = f, no deterministic space; join_walker2 is local to a rank (do_walk.f90:2475)
         w_begin = w_begin if w_begin is not None else w_target
         per_rank = w_target / world
-        mwalk = mwalk or int(max(6 * (per_rank / min_wt + size_deterministic), 200000))
+        spc = 1.5 if proposal == "heatbath" else 1.0          # two walker slots per child: the spawn region (and send / recv, sized by MWALK) needs the room
+        mwalk = mwalk or int(max(6 * (per_rank / min_wt + size_deterministic), 200000) * spc)
         self.g = g = host.gpu(rng_mode=RNG_COUNTER, seed=rank_seed(seed, rank), mwalk=mwalk, **pkw)
         if owner_hash:
             g.set_owner_hash(owner_hash)       # 1: the reference's get_det_owner (djb_hash), mpi_routines.f90:354-445
+        if proposal == "heatbath":             # the library builds the tables and refuses what the reference refuses -- on every rank alike
+            if not g.setup_efficient_heatbath():
+                g.close()
+                raise ValueError("Heatbath may be biased for this system!")
         if self.psit:
             g, s, wk, mwalk = self._setup_psit(host, g, rank, world, w_begin, mwalk, per_rank, n_truncate_trial_wf, size_deterministic,
                                                tau_multiplier, seed, owner_hash, sum_order)
