@@ -474,6 +474,35 @@ int sqmc_gpu_hci_connections_slice(sqmc_gpu_ctx *ctx, int64_t n_ref, const uint6
  * orbital occupied, every virtual orbital empty); 2: only determinants outside it.  State of the context: applies to
  * sqmc_gpu_hci_connections(_slice) and sqmc_gpu_hci_pt2 until changed.  Chemistry only. */
 int sqmc_gpu_hci_set_active_space(sqmc_gpu_ctx *ctx, uint64_t core_up, uint64_t core_dn, uint64_t virt_up, uint64_t virt_dn, int32_t mode);
+/* replaces: get_new_diag_elem (chemistry.f90:9649-9739) and get_new_diag_elem_heg (heg.f90:3357-3453): H_aa of a determinant one
+ * double excitation away from a determinant whose diagonal element is known, in O(n_elec) instead of O(n_elec^2).  Record i is
+ * old_diag[i] = H of the source and pqrs[4i..4i+3] = p, q, r, s, the excitation p, q -> r, s in the reference's spin-orbital
+ * numbering (1..norb up, norb+1..2 norb dn; r of p's spin, s of q's); new_up/new_dn[i] is the determinant it leads to.
+ * form 0: one lane, the additions in the reference's statement order (bit for bit a left-to-right evaluation of them);
+ * form 1: the two O(n) loops summed by a group of 16 lanes (the same terms, another order).
+ * Every record is validated on the device before any table is read: orbitals in 1..2 norb, p != q, r != s, spins of p/r and q/s
+ * equal, r and s occupied in the new determinant, p and q empty in it, electron numbers of the context.  One bad record makes
+ * the call return SQMC_ERR_BAD_ARG with new_diag untouched.  chem and heg contexts; time_sym contexts (a determinant-basis
+ * formula) and hubbard2 return SQMC_ERR_UNSUPPORTED.  For the electron gas the statements run with the integrals of
+ * hamiltonian_heg (the reference's copy is never called and drops the kinetic part, see sqmc_amd/csrc/diag_update.h). */
+int sqmc_gpu_diag_update_batch(sqmc_gpu_ctx *ctx, int64_t n, const double *old_diag, const int32_t *pqrs, const uint64_t *new_up,
+                               const uint64_t *new_dn, int32_t form, double *new_diag);
+/* replaces: the ref_diag_elems / diag_elems_info branch of find_doubly_excited (semistoch.f90:2182-2196), which second_order_pt
+ * and second_order_pt_alias take.  mode 0 (default): H_aa of every connected determinant from scratch; 1: from the generator's
+ * record by the O(N) update, one lane per determinant; 2: the same by 16-lane groups.  Single excitations and self slots are
+ * recomputed from scratch in every mode, as the reference does (old_diag_elem = 1e51, chemistry.f90:6898, 6990).  State of the
+ * context: honoured by sqmc_gpu_hci_pt2 (any slice count) and by a plan from sqmc_gpu_hci_pt2_stochastic_prepare (the mode as it
+ * stands at prepare).  Modes 1 and 2 are refused (SQMC_ERR_UNSUPPORTED) on time_sym and hubbard2 contexts. */
+int sqmc_gpu_hci_set_diag_update(sqmc_gpu_ctx *ctx, int32_t mode);
+/* sqmc_gpu_hci_connections_slice with the record every connection carries for the update (diag_elems_info as
+ * find_important_connected_dets_chem fills it, chemistry.f90:7148-7152): out_old_diag = H_ii of the source the connection was
+ * generated from, out_pqrs = four int32 per connection, all 0 for a self slot or a single excitation.  Merged modes keep the record
+ * of the first entry of each run of equal determinants in the sorted (stable: generation) order; the reference keeps whichever its
+ * merge leaves, and any of them gives the same H_aa up to rounding.  The other outputs are those of the _slice entry bit for bit. */
+int sqmc_gpu_hci_connections_record(sqmc_gpu_ctx *ctx, int64_t n_ref, const uint64_t *ref_up, const uint64_t *ref_dn, const double *coeffs,
+                                    double eps, int diag_mode, int32_t slice, int32_t n_slices, int64_t *out_n, uint64_t **out_up,
+                                    uint64_t **out_dn, double **out_e_mix_num, double **out_e_mix_den, double **out_old_diag,
+                                    int32_t **out_pqrs);
 /* replaces: second_order_pt (hci.f90:1100-1182), the deterministic Epstein-Nesbet correction of a variational wavefunction:
  * delta_e = sum_a (sum_i H_ai c_i)^2 / (E_var - H_aa) over the connected determinants outside the variational space, the inner
  * sum screened by |H_ai c_i| >= eps_pt; n_connections = connected determinants visited (the reference prints it).  Everything

@@ -28,7 +28,7 @@ EXPORTS = [
     "sqmc_gpu_shard_begin", "sqmc_gpu_shard_pack", "sqmc_gpu_shard_finish", "sqmc_gpu_shard_finish_psit", "sqmc_gpu_comm_unique_id", "sqmc_gpu_comm_init", "sqmc_gpu_comm_size",
     "sqmc_gpu_shard_step", "sqmc_gpu_shard_run", "sqmc_gpu_shard_time_split", "sqmc_gpu_get_rng", "sqmc_gpu_set_rng", "sqmc_gpu_tail_stats", "sqmc_gpu_last_tail", "sqmc_gpu_slowest_steps", "sqmc_gpu_set_chained_runs", "sqmc_gpu_spmv_prepare", "sqmc_gpu_davidson",
     "sqmc_gpu_spmv_apply", "sqmc_gpu_spmv_free", "sqmc_gpu_build_spmv_plan", "sqmc_gpu_spmv_sym_upper", "sqmc_gpu_hamiltonian_batch",
-    "sqmc_gpu_propose_batch", "sqmc_gpu_hamiltonian_chem_batch", "sqmc_gpu_build_sparse_ham", "sqmc_gpu_hci_connections", "sqmc_gpu_hci_connections_slice", "sqmc_gpu_hci_pt2", "sqmc_gpu_hci_pt2_stochastic_prepare", "sqmc_gpu_hci_pt2_stochastic_sample", "sqmc_gpu_hci_pt2_stochastic_stats", "sqmc_gpu_hci_pt2_stochastic_free", "sqmc_gpu_hci_set_active_space", "sqmc_gpu_free", "sqmc_gpu_set_timing", "sqmc_gpu_get_timing",
+    "sqmc_gpu_propose_batch", "sqmc_gpu_hamiltonian_chem_batch", "sqmc_gpu_build_sparse_ham", "sqmc_gpu_hci_connections", "sqmc_gpu_hci_connections_slice", "sqmc_gpu_hci_pt2", "sqmc_gpu_hci_pt2_stochastic_prepare", "sqmc_gpu_hci_pt2_stochastic_sample", "sqmc_gpu_hci_pt2_stochastic_stats", "sqmc_gpu_hci_pt2_stochastic_free", "sqmc_gpu_hci_set_active_space", "sqmc_gpu_diag_update_batch", "sqmc_gpu_hci_set_diag_update", "sqmc_gpu_hci_connections_record", "sqmc_gpu_free", "sqmc_gpu_set_timing", "sqmc_gpu_get_timing",
 ]
 
 
@@ -563,6 +563,45 @@ def _gpuchem_hci_set_active_space(self, core_up, core_dn, virt_up, virt_dn, mode
     _chk(self.L.sqmc_gpu_hci_set_active_space(self.h, int(core_up), int(core_dn), int(virt_up), int(virt_dn), int(mode)))
 
 
+def _gpuchem_diag_update_batch(self, old_diag, pqrs, new_up, new_dn, form=0):
+    """sqmc_gpu_diag_update_batch (get_new_diag_elem): H_aa of new_up/new_dn[i] from old_diag[i] = H of its source and pqrs[i] = (p, q, r, s),
+    the excitation in the reference's 1..2 norb spin-orbital numbering.  form 0: one lane, reference order; 1: 16-lane groups."""
+    o, u, d = _f64(old_diag), _u64(new_up), _u64(new_dn)
+    q = np.ascontiguousarray(pqrs, np.int32).reshape(-1)
+    n = len(o)
+    if len(q) != 4 * n or len(u) != n or len(d) != n:
+        raise ValueError("old_diag, pqrs (4 per record), new_up and new_dn differ in length")
+    out = np.zeros(n)
+    self.L.sqmc_gpu_diag_update_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    _chk(self.L.sqmc_gpu_diag_update_batch(self.h, n, _p(o), _p(q), _p(u), _p(d), int(form), _p(out)))
+    return out
+
+
+def _gpuchem_hci_set_diag_update(self, mode):
+    """H_aa of the PT2 stages: 0 from scratch (default), 1 the O(N) update on one lane, 2 the same by 16-lane groups"""
+    self.L.sqmc_gpu_hci_set_diag_update.argtypes = [C.c_void_p, C.c_int32]
+    _chk(self.L.sqmc_gpu_hci_set_diag_update(self.h, int(mode)))
+
+
+def _gpuchem_hci_connections_record(self, ref_up, ref_dn, coeffs, eps, diag_mode=0, slice=0, n_slices=1):
+    """hci_connections with the update's record of every connection: (up, dn, num, den, old_diag, pqrs[n, 4])"""
+    u, d, c = _u64(ref_up), _u64(ref_dn), _f64(coeffs)
+    n = C.c_int64(); ptr = [C.c_void_p() for _ in range(6)]
+    self.L.sqmc_gpu_hci_connections_record.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int,
+                                                       C.c_int32, C.c_int32] + [C.c_void_p] * 7
+    _chk(self.L.sqmc_gpu_hci_connections_record(self.h, len(u), _p(u), _p(d), _p(c), float(eps), int(diag_mode), int(slice), int(n_slices),
+                                                C.byref(n), *[C.byref(x) for x in ptr]))
+    k = n.value
+    if k == 0:
+        return np.zeros(0, np.uint64), np.zeros(0, np.uint64), np.zeros(0), np.zeros(0), np.zeros(0), np.zeros((0, 4), np.int32)
+    def take(x, ct, dt, m):
+        a = np.ctypeslib.as_array(C.cast(x, C.POINTER(ct)), shape=(m,)).astype(dt, copy=True)
+        self.L.sqmc_gpu_free(x)
+        return a
+    return (take(ptr[0], C.c_uint64, np.uint64, k), take(ptr[1], C.c_uint64, np.uint64, k), take(ptr[2], C.c_double, np.float64, k),
+            take(ptr[3], C.c_double, np.float64, k), take(ptr[4], C.c_double, np.float64, k), take(ptr[5], C.c_int32, np.int32, 4 * k).reshape(k, 4))
+
+
 def _gpuchem_hci_pt2(self, up, dn, coeffs, e_var, eps_pt, n_slices=1):
     """sqmc_gpu_hci_pt2: (delta_E, number of connected determinants), everything on the device"""
     u, d, c = _u64(up), _u64(dn), _f64(coeffs)
@@ -673,3 +712,6 @@ class Pt2StochasticPlan:
 
 GpuChem.hci_pt2 = _gpuchem_hci_pt2
 GpuChem.hci_set_active_space = _gpuchem_hci_set_active_space
+GpuChem.diag_update_batch = _gpuchem_diag_update_batch
+GpuChem.hci_set_diag_update = _gpuchem_hci_set_diag_update
+GpuChem.hci_connections_record = _gpuchem_hci_connections_record

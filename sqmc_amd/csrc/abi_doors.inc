@@ -362,11 +362,17 @@ int sqmc_gpu_hci_connections(sqmc_gpu_ctx *c, int64_t n_ref, const uint64_t *ref
 
 // keep_dev != null: the deduplicated connections stay on the device (ou, od, onum, oden; the caller frees them) together with the
 // reference determinants (dru, drd), and nothing is copied to the host
-struct HciDevOut { u64 *ou, *od; double *onum, *oden; long long U; u64 *dru, *drd; };
+// rec: the generator carries the get_new_diag_elem record of every connection and the dedup keeps the first of each run (orold, orpk
+// of keep_dev; with host output: *out_old, *out_pqrs as four int32 per connection, zeros where there is no record)
+struct HciDevOut { u64 *ou, *od; double *onum, *oden; long long U; u64 *dru, *drd; double *orold; unsigned *orpk; };
+static void hci_unpack_records(const unsigned *pk, long long n, int32_t *pqrs) {
+  for (long long k = 0; k < n; k++) { pqrs[4 * k] = pk[k] & 255u; pqrs[4 * k + 1] = (pk[k] >> 8) & 255u; pqrs[4 * k + 2] = (pk[k] >> 16) & 255u; pqrs[4 * k + 3] = pk[k] >> 24; }
+}
 static int hci_connections_impl(sqmc_gpu_ctx *c, int64_t n_ref, const uint64_t *ref_up, const uint64_t *ref_dn, const double *coeffs, double eps,
                                 int diag_mode, int32_t slice, int32_t n_slices, int64_t *out_n, uint64_t **out_up, uint64_t **out_dn,
-                                double **out_num, double **out_den, HciDevOut *keep_dev) {
+                                double **out_num, double **out_den, HciDevOut *keep_dev, bool rec = false, double **out_old = nullptr, int32_t **out_pqrs = nullptr) {
   if (!c || !out_n) return fail(SQMC_ERR_BAD_ARG, "null argument");
+  if (rec && (c->htab.time_sym || c->htab.sys_type == 2)) return fail(SQMC_ERR_UNSUPPORTED, "the diagonal-update record is a determinant-basis formula for chem and heg contexts without time_sym");
   if (keep_dev) { memset(keep_dev, 0, sizeof(*keep_dev)); if (diag_mode == 2) return fail(SQMC_ERR_BAD_ARG, "raw mode has no device-resident form"); }
   if (n_slices < 1 || slice < 0 || slice >= n_slices) return fail(SQMC_ERR_BAD_ARG, "slice out of range");
   u64 key_lo = 0, key_hi = ~0ull;
@@ -387,8 +393,8 @@ static int hci_connections_impl(sqmc_gpu_ctx *c, int64_t n_ref, const uint64_t *
   HIPCHK(hipMalloc(&dts, (tiles + 1) * 8));
   HIPCHK(hipMemcpy(dru, ref_up, n_ref * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(drd, ref_dn, n_ref * 8, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(dco, coeffs, n_ref * 8, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_hci_gen, dim3(nblk(n_ref)), dim3(TPB), 0, st, c->dev, dru, drd, dco, eps, diag_mode, (long long)n_ref, 0, dcnt, doff,
-                     (u64 *)nullptr, (u64 *)nullptr, (double *)nullptr, (double *)nullptr, key_lo, key_hi, c->as);
+  hipLaunchKernelGGL(k_hci_gen<false>, dim3(nblk(n_ref)), dim3(TPB), 0, st, c->dev, dru, drd, dco, eps, diag_mode, (long long)n_ref, 0, dcnt, doff,
+                     (u64 *)nullptr, (u64 *)nullptr, (double *)nullptr, (double *)nullptr, key_lo, key_hi, c->as, (double *)nullptr, (unsigned *)nullptr);
   ScanWork sw; sw.state = dts; sw.ticket = (u32 *)(dts + tiles); sw.cap_tiles = tiles; sw.self_clear = true;
   device_excl_scan_u64(dcnt, doff, n_ref, dtot, sw, st);
   u64 total = 0;
@@ -401,10 +407,23 @@ static int hci_connections_impl(sqmc_gpu_ctx *c, int64_t n_ref, const uint64_t *
   const long long T = (long long)total;
   u64 *du, *dd, *keys, *kalt, *flags, *pos, *ou, *od, *dts2, *dtot2; u32 *vals, *valt, *hist, *rowtot; double *dnum, *dden, *onum, *oden;
   HIPCHK(hipMalloc(&du, T * 8)); HIPCHK(hipMalloc(&dd, T * 8)); HIPCHK(hipMalloc(&dnum, T * 8)); HIPCHK(hipMalloc(&dden, T * 8));
-  hipLaunchKernelGGL(k_hci_gen, dim3(nblk(n_ref)), dim3(TPB), 0, st, c->dev, dru, drd, dco, eps, diag_mode, (long long)n_ref, 1, dcnt, doff, du, dd, dnum, dden, key_lo, key_hi, c->as);
+  double *drold = nullptr, *orold = nullptr; unsigned *drpk = nullptr, *orpk = nullptr;
+  if (rec) {
+    HIPCHK(hipMalloc(&drold, T * 8)); HIPCHK(hipMalloc(&drpk, T * 4));
+    hipLaunchKernelGGL(k_hci_gen<true>, dim3(nblk(n_ref)), dim3(TPB), 0, st, c->dev, dru, drd, dco, eps, diag_mode, (long long)n_ref, 1, dcnt, doff, du, dd, dnum, dden, key_lo, key_hi, c->as, drold, drpk);
+  } else
+    hipLaunchKernelGGL(k_hci_gen<false>, dim3(nblk(n_ref)), dim3(TPB), 0, st, c->dev, dru, drd, dco, eps, diag_mode, (long long)n_ref, 1, dcnt, doff, du, dd, dnum, dden, key_lo, key_hi, c->as, (double *)nullptr, (unsigned *)nullptr);
   if (diag_mode == 2) {               // the unmerged list, in generation order
     HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(st));
     *out_n = T;
+    if (rec) {
+      double *ho = (double *)malloc(T * 8 + 8); int32_t *hp = (int32_t *)malloc(T * 16 + 16); std::vector<unsigned> pk(T);
+      HIPCHK(hipMemcpy(ho, drold, T * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(pk.data(), drpk, T * 4, hipMemcpyDeviceToHost));
+      hci_unpack_records(pk.data(), T, hp);
+      if (out_old) *out_old = ho; else free(ho);
+      if (out_pqrs) *out_pqrs = hp; else free(hp);
+      hipFree(drold); hipFree(drpk);
+    }
     uint64_t *hu = (uint64_t *)malloc(T * 8 + 8), *hd = (uint64_t *)malloc(T * 8 + 8);
     double *hn = (double *)malloc(T * 8 + 8), *hden = (double *)malloc(T * 8 + 8);
     HIPCHK(hipMemcpy(hu, du, T * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(hd, dd, T * 8, hipMemcpyDeviceToHost));
@@ -434,10 +453,26 @@ static int hci_connections_impl(sqmc_gpu_ctx *c, int64_t n_ref, const uint64_t *
   HIPCHK(hipMemcpyAsync(&nuniq, dtot2, 8, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st));
   const long long U = (long long)nuniq;
   HIPCHK(hipMalloc(&ou, U * 8)); HIPCHK(hipMalloc(&od, U * 8)); HIPCHK(hipMalloc(&onum, U * 8)); HIPCHK(hipMalloc(&oden, U * 8));
-  hipLaunchKernelGGL(k_hci_dedup, dim3(nblk(T)), dim3(TPB), 0, st, skey, perm, flags, pos, du, dd, dnum, dden, ou, od, onum, oden, T);
+  if (rec) {
+    HIPCHK(hipMalloc(&orold, U * 8)); HIPCHK(hipMalloc(&orpk, U * 4));
+    hipLaunchKernelGGL(k_hci_dedup<true>, dim3(nblk(T)), dim3(TPB), 0, st, skey, perm, flags, pos, du, dd, dnum, dden, ou, od, onum, oden, T,
+                       (const double *)drold, (const unsigned *)drpk, orold, orpk);
+  } else
+    hipLaunchKernelGGL(k_hci_dedup<false>, dim3(nblk(T)), dim3(TPB), 0, st, skey, perm, flags, pos, du, dd, dnum, dden, ou, od, onum, oden, T,
+                       (const double *)nullptr, (const unsigned *)nullptr, (double *)nullptr, (unsigned *)nullptr);
   HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(st));
   *out_n = U;
+  hipFree(drold); hipFree(drpk);
+  if (rec && !keep_dev) {
+    double *ho = (double *)malloc(U * 8 + 8); int32_t *hp = (int32_t *)malloc(U * 16 + 16); std::vector<unsigned> pk(U);
+    HIPCHK(hipMemcpy(ho, orold, U * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(pk.data(), orpk, U * 4, hipMemcpyDeviceToHost));
+    hci_unpack_records(pk.data(), U, hp);
+    if (out_old) *out_old = ho; else free(ho);
+    if (out_pqrs) *out_pqrs = hp; else free(hp);
+    hipFree(orold); hipFree(orpk);
+  }
   if (keep_dev) {
+    keep_dev->orold = orold; keep_dev->orpk = orpk;
     keep_dev->ou = ou; keep_dev->od = od; keep_dev->onum = onum; keep_dev->oden = oden; keep_dev->U = U; keep_dev->dru = dru; keep_dev->drd = drd;
     void *frk[] = {dco, dcnt, doff, dtot, dts, du, dd, dnum, dden, keys, kalt, vals, valt, hist, rowtot, flags, pos, dts2, dtot2};
     for (void *q : frk) hipFree(q);
@@ -470,6 +505,47 @@ int sqmc_gpu_hci_connections_slice(sqmc_gpu_ctx *c, int64_t n_ref, const uint64_
   return hci_connections_impl(c, n_ref, ref_up, ref_dn, coeffs, eps, diag_mode, slice, n_slices, out_n, out_up, out_dn, out_num, out_den, nullptr);
 }
 
+// ----------------------------------------------------------------------- the O(N) diagonal update (diag_update.h)
+int sqmc_gpu_diag_update_batch(sqmc_gpu_ctx *c, int64_t n, const double *old_diag, const int32_t *pqrs, const uint64_t *new_up, const uint64_t *new_dn,
+                               int32_t form, double *new_diag) {
+  if (!c) return fail(SQMC_ERR_BAD_ARG, "null ctx");
+  if (c->htab.sys_type == 2) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_diag_update_batch: hubbard2 has no heat-bath generator and no diagonal update");
+  if (c->htab.time_sym) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_diag_update_batch: a determinant-basis formula; run PT2 in the determinant basis on a context with time_sym = 0");
+  if (form != 0 && form != 1) return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_diag_update_batch: form must be 0 (one lane, reference order) or 1 (lane group)");
+  if (n <= 0) return SQMC_OK;
+  if (!old_diag || !pqrs || !new_up || !new_dn || !new_diag) return fail(SQMC_ERR_BAD_ARG, "null argument");
+  double *dold, *dout; int *dpq, *dbad; u64 *du, *dd;
+  HIPCHK(hipMalloc(&dold, n * 8)); HIPCHK(hipMalloc(&dout, n * 8)); HIPCHK(hipMalloc(&dpq, n * 16)); HIPCHK(hipMalloc(&du, n * 8)); HIPCHK(hipMalloc(&dd, n * 8));
+  HIPCHK(hipMalloc(&dbad, 4));
+  HIPCHK(hipMemcpy(dold, old_diag, n * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dpq, pqrs, n * 16, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(du, new_up, n * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dd, new_dn, n * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemsetAsync(dbad, 0, 4, c->st));
+  if (form == 0) hipLaunchKernelGGL(k_diag_update_batch<0>, dim3(nblk(n)), dim3(TPB), 0, c->st, c->dev, (const double *)dold, (const int *)dpq, (const u64 *)du, (const u64 *)dd, dout, (long long)n, dbad);
+  else hipLaunchKernelGGL(k_diag_update_batch<1>, dim3(nblk(n)), dim3(TPB), 0, c->st, c->dev, (const double *)dold, (const int *)dpq, (const u64 *)du, (const u64 *)dd, dout, (long long)n, dbad);
+  HIPCHK(hipGetLastError());
+  int bad = 0;
+  HIPCHK(hipMemcpyAsync(&bad, dbad, 4, hipMemcpyDeviceToHost, c->st)); HIPCHK(hipStreamSynchronize(c->st));      // the one status read
+  if (!bad) HIPCHK(hipMemcpy(new_diag, dout, n * 8, hipMemcpyDeviceToHost));
+  void *fr[] = {dold, dout, dpq, dbad, du, dd};
+  for (void *q : fr) hipFree(q);
+  if (bad) return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_diag_update_batch: a record does not describe a double excitation into its determinant (orbital out of 1..2 norb, "
+                                         "p or q still occupied, r or s empty, spins of p/r or q/s differ, or wrong electron numbers); nothing was evaluated for it");
+  return SQMC_OK;
+}
+int sqmc_gpu_hci_set_diag_update(sqmc_gpu_ctx *c, int32_t mode) {
+  if (!c || mode < 0 || mode > 2) return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_hci_set_diag_update: mode must be 0, 1 or 2");
+  if (mode && (c->htab.time_sym || c->htab.sys_type == 2)) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_hci_set_diag_update: chem and heg contexts without time_sym only");
+  c->du_mode = mode;
+  return SQMC_OK;
+}
+// milliseconds the term kernel of the last sqmc_gpu_hci_pt2 took, all slices (0 unless SQMC_PT2_TIME was set when the library loaded); not part of the ABI
+int sqmc_gpu_debug_pt2_terms_ms(sqmc_gpu_ctx *c, double *ms) { if (!c || !ms) return SQMC_ERR_BAD_ARG; *ms = c->pt2_terms_ms; return SQMC_OK; }
+int sqmc_gpu_hci_connections_record(sqmc_gpu_ctx *c, int64_t n_ref, const uint64_t *ref_up, const uint64_t *ref_dn, const double *coeffs, double eps,
+                                    int diag_mode, int32_t slice, int32_t n_slices, int64_t *out_n, uint64_t **out_up, uint64_t **out_dn,
+                                    double **out_num, double **out_den, double **out_old_diag, int32_t **out_pqrs) {
+  return hci_connections_impl(c, n_ref, ref_up, ref_dn, coeffs, eps, diag_mode, slice, n_slices, out_n, out_up, out_dn, out_num, out_den, nullptr, true, out_old_diag, out_pqrs);
+}
+
 // Deterministic Epstein-Nesbet second-order correction, second_order_pt (hci.f90:1100-1182):
 //   delta_E = sum over the determinants a connected to the variational wavefunction but outside it of
 //             (sum_i H_ai c_i)^2 / (E_var - H_aa),          the inner sum screened by |H_ai c_i| >= eps_pt,
@@ -481,6 +557,8 @@ int sqmc_gpu_hci_pt2(sqmc_gpu_ctx *c, int64_t n_var, const uint64_t *var_up, con
                      int32_t n_slices, double *delta_e, int64_t *n_connections) {
   if (!c || !delta_e || !n_connections || n_var <= 0 || n_slices < 1) return fail(SQMC_ERR_BAD_ARG, "bad argument");
   hipStream_t st = c->st;
+  static const bool timed = getenv("SQMC_PT2_TIME") != nullptr;      // tools/pt2_diag_time.py: HIP events around the term kernel (membership + H_aa + term)
+  c->pt2_terms_ms = 0.0;
   double total = 0.0; long long nconn = 0;
   // sorted ranks of the variational determinants
   u64 *vu, *vd, *vk, *vkalt; u32 *vv, *vvalt, *hist, *rowtot;
@@ -496,20 +574,31 @@ int sqmc_gpu_hci_pt2(sqmc_gpu_ctx *c, int64_t n_var, const uint64_t *var_up, con
   int rc = SQMC_OK;
   for (int sl = 0; sl < n_slices && rc == SQMC_OK; sl++) {
     HciDevOut d; int64_t U = 0;
-    rc = hci_connections_impl(c, n_var, var_up, var_dn, coeffs, eps_pt, 0, sl, n_slices, &U, nullptr, nullptr, nullptr, nullptr, &d);
+    rc = hci_connections_impl(c, n_var, var_up, var_dn, coeffs, eps_pt, 0, sl, n_slices, &U, nullptr, nullptr, nullptr, nullptr, &d, c->du_mode != 0);
     if (rc != SQMC_OK) break;
     if (U > 0 && d.ou) {
       const int nb = std::min(nblk(U), 4096);
       double *dpart; HIPCHK(hipMalloc(&dpart, nb * 8));
-      hipLaunchKernelGGL(k_pt2_terms, dim3(nb), dim3(TPB), 0, st, c->dev, (const u64 *)d.ou, (const u64 *)d.od, (const double *)d.onum, (long long)U,
-                         (const u64 *)skey, (long long)n_var, e_var, dpart);
+      hipEvent_t ev[2];
+      if (timed) { HIPCHK(hipEventCreate(&ev[0])); HIPCHK(hipEventCreate(&ev[1])); HIPCHK(hipEventRecord(ev[0], st)); }
+      if (c->du_mode == 1)
+        hipLaunchKernelGGL(k_pt2_terms_upd<0>, dim3(nb), dim3(TPB), 0, st, c->dev, (const u64 *)d.ou, (const u64 *)d.od, (const double *)d.onum, (const double *)d.orold,
+                           (const unsigned *)d.orpk, (long long)U, (const u64 *)skey, (long long)n_var, e_var, dpart);
+      else if (c->du_mode == 2)
+        hipLaunchKernelGGL(k_pt2_terms_upd<1>, dim3(nb), dim3(TPB), 0, st, c->dev, (const u64 *)d.ou, (const u64 *)d.od, (const double *)d.onum, (const double *)d.orold,
+                           (const unsigned *)d.orpk, (long long)U, (const u64 *)skey, (long long)n_var, e_var, dpart);
+      else
+        hipLaunchKernelGGL(k_pt2_terms, dim3(nb), dim3(TPB), 0, st, c->dev, (const u64 *)d.ou, (const u64 *)d.od, (const double *)d.onum, (long long)U,
+                           (const u64 *)skey, (long long)n_var, e_var, dpart);
+      if (timed) HIPCHK(hipEventRecord(ev[1], st));
       std::vector<double> part(nb);
       HIPCHK(hipMemcpyAsync(part.data(), dpart, nb * 8, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st));
+      if (timed) { float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1])); c->pt2_terms_ms += ms; hipEventDestroy(ev[0]); hipEventDestroy(ev[1]); }
       double ssum = 0.0; for (int q = 0; q < nb; q++) ssum += part[q];          // block partials in block order
       total += ssum; nconn += U;
       hipFree(dpart);
     }
-    void *fr[] = {d.ou, d.od, d.onum, d.oden, d.dru, d.drd};
+    void *fr[] = {d.ou, d.od, d.onum, d.oden, d.dru, d.drd, d.orold, d.orpk};
     for (void *q : fr) hipFree(q);
   }
   void *fv[] = {vu, vd, vk, vkalt, vv, vvalt, hist, rowtot};
@@ -532,6 +621,7 @@ struct sqmc_pt2s_plan {
   char *d_in; u64 *d_ru, *d_rd, *d_cnt, *d_off, *d_tot, *d_scan, *d_out; double *d_rc; long long scan_tiles;
   long long cap; u64 *du, *dd, *keys, *kalt; double *dx, *dsrc; u32 *vals, *valt, *hist, *rowtot;     // per connection, capacity cap
   double *d_part; u64 *d_pcnt;
+  int du_mode; double *drold; unsigned *drpk;                         // sqmc_gpu_hci_set_diag_update as it stood at prepare; the records, capacity cap (null in mode 0)
   long long n_alloc, n_samples, last_raw, max_raw;
 };
 // sum of n doubles in the blocked pairwise order (leaves of at most 128 summed in 8 interleaved accumulators, halves split on a
@@ -550,8 +640,9 @@ static double pt2s_pairwise_sum(const double *a, long long n) {
   return pt2s_pairwise_sum(a, n2) + pt2s_pairwise_sum(a + n2, n - n2);
 }
 static void pt2s_free_conn(sqmc_pt2s_plan *p) {
-  void *fr[] = {p->du, p->dd, p->keys, p->kalt, p->dx, p->dsrc, p->vals, p->valt, p->hist};
+  void *fr[] = {p->du, p->dd, p->keys, p->kalt, p->dx, p->dsrc, p->vals, p->valt, p->hist, p->drold, p->drpk};
   for (void *q : fr) hipFree(q);
+  p->drold = nullptr; p->drpk = nullptr;
   p->du = p->dd = p->keys = p->kalt = nullptr; p->dx = p->dsrc = nullptr; p->vals = p->valt = p->hist = nullptr; p->cap = 0;
 }
 static int pt2s_grow(sqmc_pt2s_plan *p, long long need) {
@@ -561,6 +652,7 @@ static int pt2s_grow(sqmc_pt2s_plan *p, long long need) {
   HIPCHK(hipMalloc(&p->du, cap * 8)); HIPCHK(hipMalloc(&p->dd, cap * 8)); HIPCHK(hipMalloc(&p->dx, cap * 8)); HIPCHK(hipMalloc(&p->dsrc, cap * 8));
   HIPCHK(hipMalloc(&p->keys, cap * 8)); HIPCHK(hipMalloc(&p->kalt, cap * 8)); HIPCHK(hipMalloc(&p->vals, cap * 4)); HIPCHK(hipMalloc(&p->valt, cap * 4));
   HIPCHK(hipMalloc(&p->hist, (size_t)RS_MAX_RADIX * ((cap + RS_TILE - 1) / RS_TILE + 1) * 4));
+  if (p->du_mode) { HIPCHK(hipMalloc(&p->drold, cap * 8)); HIPCHK(hipMalloc(&p->drpk, cap * 4)); }
   p->cap = cap; p->n_alloc++;
   return SQMC_OK;
 }
@@ -610,7 +702,7 @@ int sqmc_gpu_hci_pt2_stochastic_prepare(sqmc_gpu_ctx *c, int64_t n_var, const ui
     if (var_up[i - 1] > var_up[i] || (var_up[i - 1] == var_up[i] && var_dn[i - 1] >= var_dn[i]))
       return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_hci_pt2_stochastic_prepare: the variational determinants must be sorted by (up, dn) without repeats (hci.f90:1373-1380)");
   sqmc_pt2s_plan *p = new sqmc_pt2s_plan();       // value-initialised: every pointer null, every counter 0
-  p->c = c; p->n_var = n_var; p->n_mc = n_mc; p->e_var = e_var; p->eps_pt = eps_pt; p->eps_pt_big = eps_pt_big;
+  p->c = c; p->n_var = n_var; p->n_mc = n_mc; p->e_var = e_var; p->eps_pt = eps_pt; p->eps_pt_big = eps_pt_big; p->du_mode = c->du_mode;
   p->prob.resize(n_var);
   for (long long i = 0; i < n_var; i++) p->prob[i] = fabs(coeffs[i]);
   double norm = 0.0;                              // numpy adds the pairwise sums of consecutive 8192-element pieces left to right
@@ -636,8 +728,8 @@ int sqmc_gpu_hci_pt2_stochastic_sample(sqmc_pt2s_plan *p, int64_t n_distinct, co
   const double *d_wop = (const double *)p->d_in; const int *d_ids = (const int *)(p->d_in + (size_t)p->n_mc * 8);
   HIPCHK(hipMemcpyAsync(p->d_in, p->h_in, (size_t)p->n_mc * 8 + m * 4, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_pt2s_gather, dim3(nblk(m)), dim3(TPB), 0, st, d_ids, (const u64 *)p->vu, (const u64 *)p->vd, (const double *)p->vc, p->d_ru, p->d_rd, p->d_rc, m);
-  hipLaunchKernelGGL(k_hci_gen, dim3(nblk(m)), dim3(TPB), 0, st, c->dev, p->d_ru, p->d_rd, p->d_rc, p->eps_pt, 2, m, 0, p->d_cnt, p->d_off,
-                     (u64 *)nullptr, (u64 *)nullptr, (double *)nullptr, (double *)nullptr, 0ull, ~0ull, c->as);
+  hipLaunchKernelGGL(k_hci_gen<false>, dim3(nblk(m)), dim3(TPB), 0, st, c->dev, p->d_ru, p->d_rd, p->d_rc, p->eps_pt, 2, m, 0, p->d_cnt, p->d_off,
+                     (u64 *)nullptr, (u64 *)nullptr, (double *)nullptr, (double *)nullptr, 0ull, ~0ull, c->as, (double *)nullptr, (unsigned *)nullptr);
   ScanWork sw; sw.state = p->d_scan; sw.ticket = (u32 *)(p->d_scan + p->scan_tiles); sw.cap_tiles = p->scan_tiles; sw.self_clear = true;
   device_excl_scan_u64(p->d_cnt, p->d_off, m, p->d_tot, sw, st);
   HIPCHK(hipMemcpyAsync(p->h_out, p->d_tot, 8, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st));       // the one sync that sizes the fill
@@ -648,16 +740,29 @@ int sqmc_gpu_hci_pt2_stochastic_sample(sqmc_pt2s_plan *p, int64_t n_distinct, co
   *value = 0.0; *n_connected = 0;
   if (T == 0) { p->n_samples++; return SQMC_OK; }
   if (T > p->cap) { const int rc = pt2s_grow(p, T); if (rc != SQMC_OK) return rc; }
-  hipLaunchKernelGGL(k_hci_gen, dim3(nblk(m)), dim3(TPB), 0, st, c->dev, p->d_ru, p->d_rd, p->d_rc, p->eps_pt, 2, m, 1, p->d_cnt, p->d_off,
-                     p->du, p->dd, p->dx, p->dsrc, 0ull, ~0ull, c->as);
+  if (p->du_mode)
+    hipLaunchKernelGGL(k_hci_gen<true>, dim3(nblk(m)), dim3(TPB), 0, st, c->dev, p->d_ru, p->d_rd, p->d_rc, p->eps_pt, 2, m, 1, p->d_cnt, p->d_off,
+                       p->du, p->dd, p->dx, p->dsrc, 0ull, ~0ull, c->as, p->drold, p->drpk);
+  else
+    hipLaunchKernelGGL(k_hci_gen<false>, dim3(nblk(m)), dim3(TPB), 0, st, c->dev, p->d_ru, p->d_rd, p->d_rc, p->eps_pt, 2, m, 1, p->d_cnt, p->d_off,
+                       p->du, p->dd, p->dx, p->dsrc, 0ull, ~0ull, c->as, (double *)nullptr, (unsigned *)nullptr);
   hipLaunchKernelGGL(k_main_keys, dim3(nblk(T)), dim3(TPB), 0, st, c->dev, p->du, p->dd, p->keys, p->vals, T, 0);
   SortWork so; so.k_alt = p->kalt; so.v_alt = p->valt; so.hist = p->hist; so.rowtot = p->rowtot; so.cap = p->cap;
   u64 *skey = p->keys; u32 *perm = p->vals;
   device_radix_sort(skey, perm, T, c->key_bits, so, st);
   const int nb = std::min(nblk(T), PT2S_MAXBLK);
-  hipLaunchKernelGGL(k_pt2s_terms, dim3(nb), dim3(TPB), 0, st, c->dev, (const u64 *)skey, (const u32 *)perm, (const u64 *)p->du, (const u64 *)p->dd,
-                     (const double *)p->dx, (const double *)p->dsrc, d_wop, T, (const u64 *)p->skey, p->n_var, p->e_var, p->eps_pt_big,
-                     (double)(p->n_mc - 1), p->d_part, p->d_pcnt);
+  if (p->du_mode == 1)
+    hipLaunchKernelGGL(k_pt2s_terms_upd<0>, dim3(nb), dim3(TPB), 0, st, c->dev, (const u64 *)skey, (const u32 *)perm, (const u64 *)p->du, (const u64 *)p->dd,
+                       (const double *)p->dx, (const double *)p->dsrc, (const double *)p->drold, (const unsigned *)p->drpk, d_wop, T, (const u64 *)p->skey, p->n_var,
+                       p->e_var, p->eps_pt_big, (double)(p->n_mc - 1), p->d_part, p->d_pcnt);
+  else if (p->du_mode == 2)
+    hipLaunchKernelGGL(k_pt2s_terms_upd<1>, dim3(nb), dim3(TPB), 0, st, c->dev, (const u64 *)skey, (const u32 *)perm, (const u64 *)p->du, (const u64 *)p->dd,
+                       (const double *)p->dx, (const double *)p->dsrc, (const double *)p->drold, (const unsigned *)p->drpk, d_wop, T, (const u64 *)p->skey, p->n_var,
+                       p->e_var, p->eps_pt_big, (double)(p->n_mc - 1), p->d_part, p->d_pcnt);
+  else
+    hipLaunchKernelGGL(k_pt2s_terms, dim3(nb), dim3(TPB), 0, st, c->dev, (const u64 *)skey, (const u32 *)perm, (const u64 *)p->du, (const u64 *)p->dd,
+                       (const double *)p->dx, (const double *)p->dsrc, d_wop, T, (const u64 *)p->skey, p->n_var, p->e_var, p->eps_pt_big,
+                       (double)(p->n_mc - 1), p->d_part, p->d_pcnt);
   hipLaunchKernelGGL(k_pt2s_final, dim3(1), dim3(64), 0, st, (const double *)p->d_part, (const u64 *)p->d_pcnt, nb, p->d_out);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(p->h_out + 2, p->d_out, 16, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st));

@@ -9,10 +9,16 @@
 // H_ij*c_j, e_mix_den) with the reference determinant itself in slot 0.
 // A reference determinant with c == 0 emits nothing, slot 0 included: find_doubly_excited does not call the generator for
 // it (semistoch.f90:1762, 1798, 1854, 1891).
+// REC: every connection also carries the record get_new_diag_elem works from (diag_update.h; diag_elems_info of the reference,
+// chemistry.f90:7148-7152): the source's H_ii, computed once per source before generation, and the packed p, q -> r, s of a double
+// excitation; DU_NONE for the self slot and for single excitations (old_diag_elem = 1e51 there, :6898, :6990).  REC = false is
+// the kernel as it always was: nothing extra is computed or written, orec_old / orec_pk are not touched.
+template <bool REC>
 __global__ void __launch_bounds__(TPB) k_hci_gen(ChemDev dev, const u64 *__restrict__ rup, const u64 *__restrict__ rdn, const double *__restrict__ coef,
                                                  double eps_var, int diag_mode, long long n_ref, int pass, u64 *__restrict__ counts,
                                                  const u64 *__restrict__ offs, u64 *__restrict__ ou, u64 *__restrict__ od,
-                                                 double *__restrict__ onum, double *__restrict__ oden, u64 key_lo, u64 key_hi, ActiveSpace as) {
+                                                 double *__restrict__ onum, double *__restrict__ oden, u64 key_lo, u64 key_hi, ActiveSpace as,
+                                                 double *__restrict__ orec_old, unsigned *__restrict__ orec_pk) {
   __shared__ ChemTab t;
   __shared__ unsigned char s_lut[HEG_LUT_MAX];        // plane wave (kx,ky,kz) -> orbital id, 0 = not in the basis (find_orb_id, heg.f90:752-771)
   stage_tab(&t, dev.tab, dev.tab_words);
@@ -38,9 +44,12 @@ __global__ void __launch_bounds__(TPB) k_hci_gen(ChemDev dev, const u64 *__restr
   // of a large space is done in slices of the connected space, each with exact sums (the role of
   // n_energy_batch, hci.f90:642); the full range keeps everything without computing keys
   const bool sliced = !(key_lo == 0 && key_hi == ~0ull);
-#define EMIT(U, D, M, DEN) do { bool in_ = true; if (sliced) { const u64 kk_ = det_key(dev, (U), (D)); in_ = (kk_ >= key_lo && kk_ < key_hi); } \
-    if (in_) { if (pass) { ou[base + cnt] = (U); od[base + cnt] = (D); onum[base + cnt] = (M) * c; oden[base + cnt] = (diag_mode == 2) ? (double)i : (DEN); } cnt++; } } while (0)
-  { double hd = (diag_mode == 1) ? h_any(t, dev.integrals, up, dn, up, dn) : 0.0; EMIT(up, dn, hd, c); }
+  double hii = 0.0;
+  if constexpr (REC) { if (pass) hii = h_any(t, dev.integrals, up, dn, up, dn); }
+#define EMIT(U, D, M, DEN, PK) do { bool in_ = true; if (sliced) { const u64 kk_ = det_key(dev, (U), (D)); in_ = (kk_ >= key_lo && kk_ < key_hi); } \
+    if (in_) { if (pass) { ou[base + cnt] = (U); od[base + cnt] = (D); onum[base + cnt] = (M) * c; oden[base + cnt] = (diag_mode == 2) ? (double)i : (DEN); \
+      if constexpr (REC) { orec_old[base + cnt] = hii; orec_pk[base + cnt] = (PK); } } cnt++; } } while (0)
+  { double hd = (diag_mode == 1) ? h_any(t, dev.integrals, up, dn, up, dn) : 0.0; EMIT(up, dn, hd, c, DU_NONE); }
   if (t.sys_type == 1) {
     // find_important_connected_dets_heg, heg.f90:2475-2727: no single excitations (momentum); every
     // double p,q -> r,s with k_p + k_q = k_r + k_s whose |H| exceeds eps/|c|.  The reference walks
@@ -69,7 +78,7 @@ __global__ void __launch_bounds__(TPB) k_hci_gen(ChemDev dev, const u64 *__restr
             else { nu = (up & ~bit64(pa - 1)) | bit64(r - 1); nd = (dn & ~bit64(qb - 1)) | bit64(s_ - 1); }
             const double mel = h_heg(t, up, dn, nu, nd);
             if (!(fabs(mel) > eps)) continue;
-            EMIT(nu, nd, mel, 0.0);
+            EMIT(nu, nd, mel, 0.0, du_pack(pa + (cls == 1 ? n : 0), qb + (cls == 0 ? 0 : n), r + (cls == 1 ? n : 0), s_ + (cls == 0 ? 0 : n)));
           }
         }
       }
@@ -95,7 +104,7 @@ __global__ void __launch_bounds__(TPB) k_hci_gen(ChemDev dev, const u64 *__restr
           if (nu == nd && up != dn) mel = sqrt2 * mel;
           if (nu > nd) { u64 x = nu; nu = nd; nd = x; mel = t.z * mel; }
         }
-        EMIT(nu, nd, mel, 0.0);
+        EMIT(nu, nd, mel, 0.0, DU_NONE);
       }
     }
   }
@@ -137,7 +146,7 @@ __global__ void __launch_bounds__(TPB) k_hci_gen(ChemDev dev, const u64 *__restr
               }
             }
             if (t.time_sym && nu > nd) { u64 x = nu; nu = nd; nd = x; mel = t.z * mel; }
-            EMIT(nu, nd, mel, 0.0);
+            EMIT(nu, nd, mel, 0.0, du_pack(p, q, r, s));
           }
         }
       }
@@ -147,15 +156,21 @@ __global__ void __launch_bounds__(TPB) k_hci_gen(ChemDev dev, const u64 *__restr
   if (!pass) counts[i] = cnt;
 }
 // dedup of the sorted connection list: sums e_mix_num / e_mix_den of equal determinants
-// left to right (merge_original_with_spawned3, tools.f90:577-660)
+// left to right (merge_original_with_spawned3, tools.f90:577-660).
+// REC: the merged determinant keeps the record of the FIRST entry of its run in the sorted order (the sort is stable: the first in
+// generation order).  The reference keeps whichever its merge leaves; every record of a run leads to the same H_aa up to rounding,
+// so no parity with the reference's choice is claimed.
 __global__ void __launch_bounds__(TPB) k_hci_heads(const u64 *__restrict__ skey, u64 *__restrict__ flags, long long n) {
   long long j = (long long)blockIdx.x * TPB + threadIdx.x;
   if (j < n) flags[j] = (j == 0 || skey[j] != skey[j - 1]) ? 1ull : 0ull;
 }
+template <bool REC>
 __global__ void __launch_bounds__(TPB) k_hci_dedup(const u64 *__restrict__ skey, const u32 *__restrict__ perm, const u64 *__restrict__ flags,
                                                    const u64 *__restrict__ pos, const u64 *__restrict__ iu, const u64 *__restrict__ id,
                                                    const double *__restrict__ inum, const double *__restrict__ iden,
-                                                   u64 *__restrict__ ou, u64 *__restrict__ od, double *__restrict__ onum, double *__restrict__ oden, long long n) {
+                                                   u64 *__restrict__ ou, u64 *__restrict__ od, double *__restrict__ onum, double *__restrict__ oden, long long n,
+                                                   const double *__restrict__ irec_old, const unsigned *__restrict__ irec_pk,
+                                                   double *__restrict__ orec_old, unsigned *__restrict__ orec_pk) {
   long long j = (long long)blockIdx.x * TPB + threadIdx.x;
   if (j >= n || !flags[j]) return;
   const u64 key = skey[j]; u32 t = perm[j];
@@ -163,6 +178,7 @@ __global__ void __launch_bounds__(TPB) k_hci_dedup(const u64 *__restrict__ skey,
   for (long long jj = j + 1; jj < n && skey[jj] == key; jj++) { a = a + inum[perm[jj]]; b = b + iden[perm[jj]]; }
   const u64 o = pos[j];
   ou[o] = iu[t]; od[o] = id[t]; onum[o] = a; oden[o] = b;
+  if constexpr (REC) { orec_old[o] = irec_old[t]; orec_pk[o] = irec_pk[t]; }
 }
 
 // ================================================================ semistochastic PT2 (second_order_pt_alias, hci.f90:1314-1660)

@@ -217,6 +217,8 @@ struct sqmc_gpu_ctx {
   bool side_pending;          // death/clone and the projection of this step have not been launched as kernels: the bucket tail does them itself, any other tail must launch them first
   double slow_us[4]; long long slow_step[4];      // the slowest steps of the last run_steps call (wall clock; host jitter shows up here)
   ActiveSpace as;             // masks of the HCI generator (sqmc_gpu_hci_set_active_space); mode 0 = none
+  double pt2_terms_ms;        // HIP-event time of the last sqmc_gpu_hci_pt2's term kernel (sqmc_gpu_debug_pt2_terms_ms)
+  int du_mode;                // H_aa of the PT2 stages (sqmc_gpu_hci_set_diag_update): 0 from scratch, 1 / 2 get_new_diag_elem on one lane / 16 lanes
   bool tail_fills_hii;        // the tail that enqueues the next head is a bucket tail: it computes the H_ii of the determinants it creates itself
   bool fork_valid;            // e_fork was recorded behind the last tail (a head behind a bucket tail forks nothing and skips it)
   bool head_hii, head_hii_joined;     // the pipelined head fills the missing H_ii of this step's walkers (joined: inside k_spawn itself, nothing to wait for)
@@ -263,6 +265,7 @@ static inline int spawn_kind(const sqmc_gpu_ctx *c) {
   else if (FUSE_) hipExtLaunchKernelGGL((k_spawn<SPAWN_UNIFORM, 1>), __VA_ARGS__); else hipExtLaunchKernelGGL((k_spawn<SPAWN_UNIFORM, 0>), __VA_ARGS__); } while (0)
 #include "bucket_kernels.h"
 #include "door_kernels.h"
+#include "diag_update.h"
 #include "hci_kernels.h"
 #include "hbuild_kernels.h"
 #include "spmv_kernels.h"

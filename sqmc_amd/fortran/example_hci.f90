@@ -3,8 +3,9 @@
 !> sqmc_gpu_mod -- sqmc_gpu_hci_connections for find_doubly_excited + dedup (hci.f90:905-931),
 !> sqmc_gpu_build_spmv_plan for generate_sparse_ham_chem_upper_triangular, sqmc_gpu_davidson for
 !> davidson_sparse (more_tools.f90:2018-2244) -- and the host logic (the list bookkeeping of get_next_det_list) written here.  Tables come from a deck written by sqmc_amd.host.dump_hci_deck.
-!>   usage: example_hci <deck> [eps_pt]      with eps_pt: the Epstein-Nesbet correction of state 1 (second_order_pt,
-!>   hci.f90:1100-1182) in one call, sqmc_gpu_hci_pt2, on the basis the deck's context works in
+!>   usage: example_hci <deck> [eps_pt [diag_update]]      with eps_pt: the Epstein-Nesbet correction of state 1 (second_order_pt,
+!>   hci.f90:1100-1182) in one call, sqmc_gpu_hci_pt2, on the basis the deck's context works in; diag_update 0 (default), 1 or 2:
+!>   H_aa from scratch or by get_new_diag_elem's O(N) update (sqmc_gpu_hci_set_diag_update; contexts without time_sym)
 module hci_host_tools
   use iso_c_binding
   implicit none
@@ -79,16 +80,20 @@ program example_hci
   real(c_double), allocatable :: wts(:,:), coeffs(:), energy(:), old_energy(:), diag(:)
   real(c_double), allocatable, target :: start(:,:)
   real(c_double), allocatable :: w(:,:), low(:)
-  integer(c_int32_t) :: n_mv
+  integer(c_int32_t) :: n_mv, du_mode
   integer(c_int64_t), pointer :: p_up(:), p_dn(:)
   type(c_ptr) :: gpu, plan, c_up, c_dn, c_num, c_den
   type(sqmc_chem_cfg) :: cfg
 
-  if (command_argument_count() < 1) stop 'usage: example_hci <deck> [eps_pt]'
+  if (command_argument_count() < 1) stop 'usage: example_hci <deck> [eps_pt [diag_update]]'
   call get_command_argument(1, deck)
   eps_pt = 0
   if (command_argument_count() >= 2) then
     call get_command_argument(2, arg2); read(arg2, *) eps_pt
+  endif
+  du_mode = 0
+  if (command_argument_count() >= 3) then
+    call get_command_argument(3, arg2); read(arg2, *) du_mode
   endif
   open(newunit=u, file=trim(deck), access='stream', form='unformatted', status='old')
   read(u) hdr
@@ -181,6 +186,7 @@ program example_hci
   write(6, '(a,i10,10es26.17)') 'fortran hci:', n, energy
   if (eps_pt > 0) then
     allocate(coeffs(n)); coeffs = wts(:, 1)
+    if (du_mode /= 0) call sqmc_gpu_check(sqmc_gpu_hci_set_diag_update(gpu, du_mode), 'hci_set_diag_update')
     call sqmc_gpu_check(sqmc_gpu_hci_pt2(gpu, n, up, dn, coeffs, energy(1), eps_pt, 1_c_int32_t, delta_e, n_conn), 'hci_pt2')
     write(6, '(a,i12,2es26.17)') 'fortran pt2:', n_conn, delta_e, energy(1) + delta_e
     deallocate(coeffs)

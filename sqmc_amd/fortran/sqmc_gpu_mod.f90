@@ -20,6 +20,7 @@ module sqmc_gpu_mod
   public :: sqmc_gpu_set_hf_to_psit, sqmc_gpu_setup_efficient_heatbath, sqmc_gpu_get_heatbath_tables
   public :: sqmc_gpu_set_hf_to_psit_shard, sqmc_gpu_shard_finish_psit
   public :: sqmc_gpu_setup_cauchy_schwarz, sqmc_gpu_propose_cauchy_schwarz_batch
+  public :: sqmc_gpu_diag_update_batch, sqmc_gpu_hci_set_diag_update, sqmc_gpu_hci_connections_record
   public :: sqmc_gpu_hci_pt2_stochastic_prepare, sqmc_gpu_hci_pt2_stochastic_sample, sqmc_gpu_hci_pt2_stochastic_stats, sqmc_gpu_hci_pt2_stochastic_free
   public :: sqmc_gpu_check
 
@@ -128,6 +129,24 @@ module sqmc_gpu_mod
     end function
     integer(c_int) function sqmc_gpu_hci_set_active_space(ctx, core_up, core_dn, virt_up, virt_dn, mode) bind(C, name='sqmc_gpu_hci_set_active_space')
       import; type(c_ptr), value :: ctx; integer(c_int64_t), value :: core_up, core_dn, virt_up, virt_dn; integer(c_int32_t), value :: mode
+    end function
+    ! get_new_diag_elem (chemistry.f90:9649-9739): H_aa from the source's H_ii and the excitation p, q -> r, s (pqrs(4, n), the
+    ! reference's 1..2 norb numbering); form 0 one lane in the reference's order, 1 lane groups
+    integer(c_int) function sqmc_gpu_diag_update_batch(ctx, n, old_diag, pqrs, new_up, new_dn, form, new_diag) bind(C, name='sqmc_gpu_diag_update_batch')
+      import; type(c_ptr), value :: ctx; integer(c_int64_t), value :: n; real(c_double), intent(in) :: old_diag(*)
+      integer(c_int32_t), intent(in) :: pqrs(*); integer(c_int64_t), intent(in) :: new_up(*), new_dn(*); integer(c_int32_t), value :: form
+      real(c_double), intent(out) :: new_diag(*)
+    end function
+    ! H_aa of the PT2 stages: 0 from scratch (default), 1 / 2 the O(N) update on one lane / by lane groups
+    integer(c_int) function sqmc_gpu_hci_set_diag_update(ctx, mode) bind(C, name='sqmc_gpu_hci_set_diag_update')
+      import; type(c_ptr), value :: ctx; integer(c_int32_t), value :: mode
+    end function
+    integer(c_int) function sqmc_gpu_hci_connections_record(ctx, n_ref, ref_up, ref_dn, coeffs, eps, diag_mode, slice, n_slices, out_n, out_up, out_dn, &
+        out_num, out_den, out_old_diag, out_pqrs) bind(C, name='sqmc_gpu_hci_connections_record')
+      import; type(c_ptr), value :: ctx; integer(c_int64_t), value :: n_ref; integer(c_int64_t), intent(in) :: ref_up(*), ref_dn(*)
+      real(c_double), intent(in) :: coeffs(*); real(c_double), value :: eps; integer(c_int), value :: diag_mode
+      integer(c_int32_t), value :: slice, n_slices
+      integer(c_int64_t), intent(out) :: out_n; type(c_ptr), intent(out) :: out_up, out_dn, out_num, out_den, out_old_diag, out_pqrs
     end function
     integer(c_int) function sqmc_gpu_hci_pt2(ctx, n_var, var_up, var_dn, coeffs, e_var, eps_pt, n_slices, delta_e, n_connections) &
         bind(C, name='sqmc_gpu_hci_pt2')

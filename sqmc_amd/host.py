@@ -1201,7 +1201,7 @@ def sum_left(it):
     return t
 
 
-def hci_pt2(host, g, up, dn, coeffs, e_var, eps_pt, n_slices=1):
+def hci_pt2(host, g, up, dn, coeffs, e_var, eps_pt, n_slices=1, diag_update=0):
     """Deterministic Epstein-Nesbet second-order correction, second_order_pt (hci.f90:1100-1182):
     delta_E = sum over determinants a outside the variational space of
     (sum_i H_ai c_i)^2 / (E_var - H_aa), the inner sum screened by |H_ai c_i| >= eps_pt.
@@ -1209,8 +1209,17 @@ def hci_pt2(host, g, up, dn, coeffs, e_var, eps_pt, n_slices=1):
     diagonal elements and the reduction all stay on the device.  n_slices > 1 does the connected
     space in that many slices of the determinant-key range (exact: every connected determinant
     lives in one slice), for spaces whose connections do not fit one call.
+    diag_update: how H_aa is formed -- 0 from scratch (the default), 1 by get_new_diag_elem's O(N) update from the generator's
+    record (chemistry.f90:9649-9739) on one lane per determinant, 2 the same by 16-lane groups.  The context's setting is
+    restored afterwards.
     Returns (delta_E, number of connected determinants)."""
-    return g.hci_pt2(up, dn, coeffs, e_var, eps_pt, n_slices)
+    if not diag_update:
+        return g.hci_pt2(up, dn, coeffs, e_var, eps_pt, n_slices)
+    g.hci_set_diag_update(diag_update)
+    try:
+        return g.hci_pt2(up, dn, coeffs, e_var, eps_pt, n_slices)
+    finally:
+        g.hci_set_diag_update(0)
 
 
 def hci_pt2_by_doors(host, g, up, dn, coeffs, e_var, eps_pt, n_slices=1):
@@ -1243,7 +1252,7 @@ def time_symmetrized_to_dets(up, dn, coeffs, z=1):
     return ou[order], od[order], oc[order]
 
 
-def hci_pt2_determinant_basis(host, up, dn, coeffs, e_var, eps_pt, n_slices=1):
+def hci_pt2_determinant_basis(host, up, dn, coeffs, e_var, eps_pt, n_slices=1, diag_update=0):
     """do_pt as the reference runs it for a time-symmetric variational stage: back to the
     determinant basis, time_sym off from then on (hci.f90:648-659), then second_order_pt."""
     import copy
@@ -1251,7 +1260,7 @@ def hci_pt2_determinant_basis(host, up, dn, coeffs, e_var, eps_pt, n_slices=1):
         g = host.gpu()
         g.set_hb_tables(*host.hb_tables(g))
         try:
-            return hci_pt2(host, g, up, dn, coeffs, e_var, eps_pt, n_slices)
+            return hci_pt2(host, g, up, dn, coeffs, e_var, eps_pt, n_slices, diag_update)
         finally:
             g.close()
     plain = copy.copy(host)
@@ -1260,7 +1269,7 @@ def hci_pt2_determinant_basis(host, up, dn, coeffs, e_var, eps_pt, n_slices=1):
     g = plain.gpu()
     try:
         g.set_hb_tables(*plain.hb_tables(g))
-        return hci_pt2(plain, g, du, dd, dc, e_var, eps_pt, n_slices)
+        return hci_pt2(plain, g, du, dd, dc, e_var, eps_pt, n_slices, diag_update)
     finally:
         g.close()
 
@@ -1514,7 +1523,7 @@ def pt2_stochastic_sample_host(g, up, dn, c, prob, ids, counts, e_var, eps_pt, e
 
 
 def hci_pt2_stochastic(host, g, up, dn, coeffs, e_var, eps_pt, eps_pt_big, n_mc, target_error, seed=(2726, 5165, 6543, 6524),
-                       max_samples=10**6, log=None, on_device=False):
+                       max_samples=10**6, log=None, on_device=False, diag_update=0):
     """second_order_pt_alias, hci.f90:1314-1660 (one rank): the PT correction at eps_pt as the
     deterministic correction at eps_pt_big (hci_pt2) plus a stochastic estimate of the difference.
     Each sample draws n_mc variational determinants with probability |c_i| / sum|c| (alias method,
@@ -1528,13 +1537,16 @@ def hci_pt2_stochastic(host, g, up, dn, coeffs, e_var, eps_pt, eps_pt_big, n_mc,
     on_device: a sample is one call of the library (sqmc_gpu_hci_pt2_stochastic_sample: generation, sort, the weighted sums,
     membership, H_kk and the reduction on the device; the merged draws go in, one double and one count come back) instead of
     pt2_stochastic_sample_host.  Draws, merging, Welford and the stopping rule are the same code either way.
+    diag_update (on_device only): 0 / 1 / 2 as hci_pt2, for the deterministic part and for the plan's samples.
     Returns dict(pt_big, pt_diff, pt_diff_std_dev, samples=[per-sample values], n_connected_big,
     samples_connected=[connected determinants outside the variational space, per sample])."""
     up, dn, c = np.ascontiguousarray(up, np.uint64), np.ascontiguousarray(dn, np.uint64), np.asarray(coeffs, float)
     order = sort_dets(up, dn)
     up, dn, c = up[order], dn[order], c[order]
     n = len(up)
-    pt_big, n_big = hci_pt2(host, g, up, dn, c, e_var, eps_pt_big)
+    if diag_update and not on_device:
+        raise ValueError("diag_update needs on_device=True: the host path takes H_kk from hamiltonian_batch")
+    pt_big, n_big = hci_pt2(host, g, up, dn, c, e_var, eps_pt_big, diag_update=diag_update)
     prob = np.abs(c) / np.abs(c).sum()
     J, q = setup_alias(prob)
     rng = Rannyu(seed)
@@ -1543,7 +1555,11 @@ def hci_pt2_stochastic(host, g, up, dn, coeffs, e_var, eps_pt, eps_pt_big, n_mc,
     plan = None
     if on_device:
         from ._lib import Pt2StochasticPlan
-        plan = Pt2StochasticPlan(g, up, dn, c, e_var, eps_pt, eps_pt_big, n_mc)
+        g.hci_set_diag_update(diag_update)              # the plan takes the mode as it stands when it is prepared
+        try:
+            plan = Pt2StochasticPlan(g, up, dn, c, e_var, eps_pt, eps_pt_big, n_mc)
+        finally:
+            g.hci_set_diag_update(0)
     for sample in range(1, max_samples + 1):
         draws = np.empty(n_mc, np.int64)
         for k in range(n_mc):

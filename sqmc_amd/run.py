@@ -104,7 +104,7 @@ def parse_hci_deck(text):
     return deck
 
 
-def run_hci_heg(deck, out=sys.stdout, pt_on_device=False):
+def run_hci_heg(deck, out=sys.stdout, pt_on_device=False, pt_diag_update=0):
     """HEG decks: no integral file; result lines as hci.f90 prints them for 'heg' (no state index in the
     older output format the e2e fixtures were produced with; Madelung total, correlation energy)."""
     import torch            # noqa: F401
@@ -128,7 +128,7 @@ def run_hci_heg(deck, out=sys.stdout, pt_on_device=False):
     e0 = float(energy[0])
     if deck["n_mc"] > 0 and deck["eps_pt_big"] > deck["eps_pt"]:
         r = H.hci_pt2_stochastic(h, g, up, dn, wts[:, 0], e0, deck["eps_pt"], deck["eps_pt_big"], deck["n_mc"], deck["target_error"],
-                                 seed=deck["irand_seed"][0], log=lambda m: p("\n" + m), on_device=pt_on_device)
+                                 seed=deck["irand_seed"][0], log=lambda m: p("\n" + m), on_device=pt_on_device, diag_update=pt_diag_update)
         de, err = r["pt_big"] + r["pt_diff"], r["pt_diff_std_dev"]
         p("\nVariational energy=%s%15.9f" % (" " * 16, e0))
         p("Second-order PT energy lowering=%s%15.9f +-%12.9f (%13.9f%13.9f)" % (" " * 3, de, err, r["pt_big"], r["pt_diff"]))
@@ -136,7 +136,7 @@ def run_hci_heg(deck, out=sys.stdout, pt_on_device=False):
         p("Total energy (includ. Madelung)=%s%15.9f +-%12.9f" % (" " * 3, e0 + de + mad, err))
         res.update(pt=de, pt_err=err, pt_big=r["pt_big"], pt_diff=r["pt_diff"], n_samples=len(r["samples"]))
     else:
-        de, nconn = H.hci_pt2(h, g, up, dn, wts[:, 0], e0, deck["eps_pt"])
+        de, nconn = H.hci_pt2(h, g, up, dn, wts[:, 0], e0, deck["eps_pt"], diag_update=pt_diag_update)
         p("\nPT_correction, eps_pt, ndets_connected for fully deterministic run=%15.9f%12.4E%12d" % (de, deck["eps_pt"], nconn))
         p("\nVariational energy=%s%15.9f" % (" " * 16, e0))
         p("Second-order PT energy lowering=%s%15.9f" % (" " * 3, de))
@@ -149,10 +149,11 @@ def run_hci_heg(deck, out=sys.stdout, pt_on_device=False):
     return res
 
 
-def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False):
-    """pt_on_device: the samples of the semistochastic PT are evaluated by the library (host.hci_pt2_stochastic on_device)"""
+def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False, pt_diag_update=0):
+    """pt_on_device: the samples of the semistochastic PT are evaluated by the library (host.hci_pt2_stochastic on_device);
+    pt_diag_update: 0 / 1 / 2, how the PT stage forms H_aa (host.hci_pt2)"""
     if deck["hamiltonian_type"] == "heg":
-        return run_hci_heg(deck, out, pt_on_device)
+        return run_hci_heg(deck, out, pt_on_device, pt_diag_update)
     import torch            # noqa: F401  one libamdhip64 per process
     import sqmc_amd
     from . import host as H
@@ -199,7 +200,7 @@ def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False):
             gp.set_hb_tables(*plain.hb_tables(gp))
             try:
                 r = H.hci_pt2_stochastic(plain, gp, du, dd, dc, float(energy[i]), deck["eps_pt"], deck["eps_pt_big"], deck["n_mc"], deck["target_error"],
-                                         seed=deck["irand_seed"][0], log=lambda m: p("\n" + m), on_device=pt_on_device)
+                                         seed=deck["irand_seed"][0], log=lambda m: p("\n" + m), on_device=pt_on_device, diag_update=pt_diag_update)
             finally:
                 gp.close()
             de, nconn = r["pt_big"] + r["pt_diff"], r["n_connected_big"]
@@ -209,7 +210,7 @@ def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False):
             p("Total energy(%d)=%s%15.9f +-%12.9f" % (i + 1, " " * 18, energy[i] + de, r["pt_diff_std_dev"]))
             results.append((float(energy[i]), float(de), int(nconn)))
             continue
-        de, nconn = H.hci_pt2_determinant_basis(h, up, dn, wts[:, i], float(energy[i]), deck["eps_pt"])
+        de, nconn = H.hci_pt2_determinant_basis(h, up, dn, wts[:, i], float(energy[i]), deck["eps_pt"], diag_update=pt_diag_update)
         p("\nState%4d:" % (i + 1))
         p("Variational energy(%d)=%s%15.9f" % (i + 1, " " * 12, energy[i]))
         p("2nd-order PT energy lowering(%d)=%s%15.9f" % (i + 1, " " * 2, de))
@@ -238,6 +239,8 @@ def main(argv=None):
         ap.add_argument("--%s-out" % name, default=None, help="walk decks: write %s to this file" % what)
     ap.add_argument("--pt-on-device", action="store_true", help="HCI decks with n_mc > 0: evaluate every sample of the semistochastic PT in the library "
                     "(sqmc_gpu_hci_pt2_stochastic_sample) instead of numpy on the raw connection list")
+    ap.add_argument("--pt-diag-update", type=int, choices=(0, 1, 2), default=0, help="HCI decks: H_aa of the PT stage from scratch (0, default), by the O(N) update "
+                    "of get_new_diag_elem on one lane (1) or by 16-lane groups (2); with n_mc > 0 it needs --pt-on-device")
     a = ap.parse_args(argv)
     text = open(a.input).read() if a.input else sys.stdin.read()
     lines = [l for l in text.splitlines() if l.strip() and not l.lstrip().startswith("!")]
@@ -247,7 +250,7 @@ def main(argv=None):
         return run_walk(parse_walk_deck(text), a.fcidump, walkalize=a.walkalize, psit_con_in=a.psit_con_in, psit_con_out=a.psit_con_out,
                         dtm_elems_in=a.dtm_elems_in, dtm_elems_out=a.dtm_elems_out)
     deck = parse_hci_deck(text)
-    return run_hci(deck, a.fcidump, pt_on_device=a.pt_on_device)
+    return run_hci(deck, a.fcidump, pt_on_device=a.pt_on_device, pt_diag_update=a.pt_diag_update)
 
 
 if __name__ == "__main__":
