@@ -107,6 +107,30 @@ typedef struct {
   int64_t mwalk;
 } sqmc_hubbard_cfg;
 int sqmc_gpu_init_hubbard(const sqmc_hubbard_cfg *cfg, sqmc_gpu_ctx **out);
+/* Hubbard model in its plane-wave basis on a periodic l_x by l_y lattice (hamiltonian_type 'hubbardk', space_sym = .false.):
+ * hubbard.f90:2179-2324 (generate_k_vectors), 2866-2924 (hamiltonian_hubbard_k), 3649-3848 (off_diagonal_move_hubbard_k),
+ * 5462 (find_connected_dets_hubbard_k).  The orbital table arrives as data in the reference's orbital order, as
+ * sqmc_gpu_init_heg takes its plane waves: k_vectors is the reference's k_vectors(2, nsites) (int32, two per orbital, units of
+ * pi / L), k_energies its k_energies(nsites).  The library builds the momentum -> orbital lookup itself (nsites entries; the
+ * reference's kmap).  sys_type 3: H_ii = U/nsites * nup * ndn + the occupied orbitals' energies; every off-diagonal element is
+ * +-U/nsites between determinants one up and one dn electron apart with the total momentum conserved modulo (2 l_x, 2 l_y);
+ * the proposal draws random_int(nup), random_int(ndn), random_int(nsites - nup) in that order.
+ * The connection generator (sqmc_gpu_hci_connections, _slice, sqmc_gpu_hci_pt2) loops up electrons x dn electrons x empty up
+ * orbitals, ascending, and keeps a connection when |H c| > eps: every |H| is U/nsites, so the screen selects on |c| alone.
+ * Refused: l_x * l_y > 64; a length of 2 (the double bond sqmc_gpu_init_hubbard refuses); both lengths 1; nup or ndn outside
+ * 1 .. nsites - 1 (the move needs one electron of each spin and a hole); a k table that is not exactly one orbital per lattice
+ * momentum modulo (2 l_x, 2 l_y).  Chains (one length 1, the other >= 3) are supported.  On such a context the diagonal-update
+ * modes, the active-space masks, the stochastic-PT plan and hf_to_psit return SQMC_ERR_UNSUPPORTED, as for hubbard2. */
+typedef struct {
+  int32_t l_x, l_y, nup, ndn;
+  double t, U;
+  const int32_t *k_vectors;         /* [2 * nsites] */
+  const double *k_energies;         /* [nsites] */
+  int32_t rng_mode;
+  int32_t irand_seed[4];
+  int64_t mwalk;
+} sqmc_hubbardk_cfg;
+int sqmc_gpu_init_hubbardk(const sqmc_hubbardk_cfg *cfg, sqmc_gpu_ctx **out);
 int sqmc_gpu_finalize(sqmc_gpu_ctx *ctx);
 const char *sqmc_gpu_last_error(void);
 

@@ -22,7 +22,7 @@ RNG_REPLAY, RNG_COUNTER = 0, 1
 _LIB = None
 
 EXPORTS = [
-    "sqmc_gpu_set_device", "sqmc_gpu_init_chem", "sqmc_gpu_init_heg", "sqmc_gpu_init_hubbard", "sqmc_gpu_finalize", "sqmc_gpu_last_error", "sqmc_gpu_set_hb_tables", "sqmc_gpu_set_heatbath_tables", "sqmc_gpu_setup_efficient_heatbath", "sqmc_gpu_get_heatbath_tables", "sqmc_gpu_propose_heatbath_batch", "sqmc_gpu_setup_cauchy_schwarz", "sqmc_gpu_propose_cauchy_schwarz_batch", "sqmc_gpu_set_projector",
+    "sqmc_gpu_set_device", "sqmc_gpu_init_chem", "sqmc_gpu_init_heg", "sqmc_gpu_init_hubbard", "sqmc_gpu_init_hubbardk", "sqmc_gpu_finalize", "sqmc_gpu_last_error", "sqmc_gpu_set_hb_tables", "sqmc_gpu_set_heatbath_tables", "sqmc_gpu_setup_efficient_heatbath", "sqmc_gpu_get_heatbath_tables", "sqmc_gpu_propose_heatbath_batch", "sqmc_gpu_setup_cauchy_schwarz", "sqmc_gpu_propose_cauchy_schwarz_batch", "sqmc_gpu_set_projector",
     "sqmc_gpu_scale_projector", "sqmc_gpu_set_ct_table", "sqmc_gpu_set_hf_to_psit", "sqmc_gpu_set_hf_to_psit_shard", "sqmc_gpu_upload_walkers", "sqmc_gpu_num_walkers",
     "sqmc_gpu_download_walkers", "sqmc_gpu_step", "sqmc_gpu_run", "sqmc_gpu_annihilate", "sqmc_gpu_det_owner", "sqmc_gpu_set_owner_hash", "sqmc_gpu_shard_config",
     "sqmc_gpu_shard_begin", "sqmc_gpu_shard_pack", "sqmc_gpu_shard_finish", "sqmc_gpu_shard_finish_psit", "sqmc_gpu_comm_unique_id", "sqmc_gpu_comm_init", "sqmc_gpu_comm_size",
@@ -72,6 +72,11 @@ class HegCfg(C.Structure):
 class HubbardCfg(C.Structure):
     _fields_ = [("l_x", C.c_int32), ("l_y", C.c_int32), ("pbc", C.c_int32), ("nup", C.c_int32), ("ndn", C.c_int32),
                 ("t", C.c_double), ("U", C.c_double), ("rng_mode", C.c_int32), ("irand_seed", C.c_int32 * 4), ("mwalk", C.c_int64)]
+
+
+class HubbardKCfg(C.Structure):
+    _fields_ = [("l_x", C.c_int32), ("l_y", C.c_int32), ("nup", C.c_int32), ("ndn", C.c_int32), ("t", C.c_double), ("U", C.c_double),
+                ("k_vectors", C.c_void_p), ("k_energies", C.c_void_p), ("rng_mode", C.c_int32), ("irand_seed", C.c_int32 * 4), ("mwalk", C.c_int64)]
 
 
 class StepParams(C.Structure):
@@ -208,6 +213,26 @@ class GpuChem:
             cfg.irand_seed[i] = seed[i]
         h = C.c_void_p()
         _chk(L.sqmc_gpu_init_hubbard(C.byref(cfg), C.byref(h)))
+        self.h, self.norb, self.mwalk = h, l_x * l_y, mwalk
+        return self
+
+    @classmethod
+    def hubbardk(cls, l_x, l_y, nup, ndn, t, U, k_vectors, k_energies, rng_mode=RNG_COUNTER, seed=(1346, 5634, 6635, 4361), mwalk=0):
+        """context for the Hubbard model in plane waves ('hubbardk'): k_vectors[nsites, 2] in units of pi / L and k_energies[nsites],
+        both in the reference's orbital order (HubbardKHost builds them)"""
+        self = cls.__new__(cls)
+        self.L = L = load_library()
+        kv, ke = np.ascontiguousarray(k_vectors, np.int32).reshape(-1), _f64(k_energies)
+        if len(kv) != 2 * l_x * l_y or len(ke) != l_x * l_y:
+            raise ValueError("k_vectors / k_energies do not hold l_x * l_y orbitals")
+        self._tabs = [kv, ke]
+        cfg = HubbardKCfg()
+        cfg.l_x, cfg.l_y, cfg.nup, cfg.ndn, cfg.t, cfg.U = l_x, l_y, nup, ndn, float(t), float(U)
+        cfg.k_vectors, cfg.k_energies, cfg.rng_mode, cfg.mwalk = kv.ctypes.data, ke.ctypes.data, rng_mode, mwalk
+        for i in range(4):
+            cfg.irand_seed[i] = seed[i]
+        h = C.c_void_p()
+        _chk(L.sqmc_gpu_init_hubbardk(C.byref(cfg), C.byref(h)))
         self.h, self.norb, self.mwalk = h, l_x * l_y, mwalk
         return self
 

@@ -372,7 +372,7 @@ static int hci_connections_impl(sqmc_gpu_ctx *c, int64_t n_ref, const uint64_t *
                                 int diag_mode, int32_t slice, int32_t n_slices, int64_t *out_n, uint64_t **out_up, uint64_t **out_dn,
                                 double **out_num, double **out_den, HciDevOut *keep_dev, bool rec = false, double **out_old = nullptr, int32_t **out_pqrs = nullptr) {
   if (!c || !out_n) return fail(SQMC_ERR_BAD_ARG, "null argument");
-  if (rec && (c->htab.time_sym || c->htab.sys_type == 2)) return fail(SQMC_ERR_UNSUPPORTED, "the diagonal-update record is a determinant-basis formula for chem and heg contexts without time_sym");
+  if (rec && (c->htab.time_sym || c->htab.sys_type >= 2)) return fail(SQMC_ERR_UNSUPPORTED, "the diagonal-update record is a determinant-basis formula for chem and heg contexts without time_sym");
   if (keep_dev) { memset(keep_dev, 0, sizeof(*keep_dev)); if (diag_mode == 2) return fail(SQMC_ERR_BAD_ARG, "raw mode has no device-resident form"); }
   if (n_slices < 1 || slice < 0 || slice >= n_slices) return fail(SQMC_ERR_BAD_ARG, "slice out of range");
   u64 key_lo = 0, key_hi = ~0ull;
@@ -510,6 +510,7 @@ int sqmc_gpu_diag_update_batch(sqmc_gpu_ctx *c, int64_t n, const double *old_dia
                                int32_t form, double *new_diag) {
   if (!c) return fail(SQMC_ERR_BAD_ARG, "null ctx");
   if (c->htab.sys_type == 2) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_diag_update_batch: hubbard2 has no heat-bath generator and no diagonal update");
+  if (c->htab.sys_type == 3) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_diag_update_batch: hubbardk has no diagonal update (its H_ii is a sum of nup + ndn orbital energies)");
   if (c->htab.time_sym) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_diag_update_batch: a determinant-basis formula; run PT2 in the determinant basis on a context with time_sym = 0");
   if (form != 0 && form != 1) return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_diag_update_batch: form must be 0 (one lane, reference order) or 1 (lane group)");
   if (n <= 0) return SQMC_OK;
@@ -534,7 +535,7 @@ int sqmc_gpu_diag_update_batch(sqmc_gpu_ctx *c, int64_t n, const double *old_dia
 }
 int sqmc_gpu_hci_set_diag_update(sqmc_gpu_ctx *c, int32_t mode) {
   if (!c || mode < 0 || mode > 2) return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_hci_set_diag_update: mode must be 0, 1 or 2");
-  if (mode && (c->htab.time_sym || c->htab.sys_type == 2)) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_hci_set_diag_update: chem and heg contexts without time_sym only");
+  if (mode && (c->htab.time_sym || c->htab.sys_type >= 2)) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_hci_set_diag_update: chem and heg contexts without time_sym only");
   c->du_mode = mode;
   return SQMC_OK;
 }
@@ -696,6 +697,7 @@ int sqmc_gpu_hci_pt2_stochastic_prepare(sqmc_gpu_ctx *c, int64_t n_var, const ui
   if (n_mc < 2) return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_hci_pt2_stochastic_prepare: n_mc must be at least 2 (the estimator divides by n_mc (n_mc - 1))");
   if (n_var >= (1ll << 31)) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_hci_pt2_stochastic_prepare: more than 2^31 variational determinants");
   if (c->htab.sys_type == 2) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_hci_pt2_stochastic_prepare: hubbard2 has no heat-bath connection generator (find_connected_dets_hubbard is the host's)");
+  if (c->htab.sys_type == 3) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_hci_pt2_stochastic_prepare: the stochastic PT plan is not built for hubbardk");
   if (c->htab.sys_type == 0 && !c->dev.hb_r) return fail(SQMC_ERR_BAD_ARG, "heat-bath tables not set (sqmc_gpu_set_hb_tables)");
   if (c->htab.sys_type == 1 && c->htab.heg_nmax > 4) return fail(SQMC_ERR_UNSUPPORTED, "HEG connections: plane-wave index beyond +-4");
   for (long long i = 1; i < n_var; i++)

@@ -637,6 +637,7 @@ int sqmc_gpu_set_hf_to_psit_shard(sqmc_gpu_ctx *c, int64_t n_ct_local, const int
   abandon_head(c);
   if (!c || n_ct_local < 0 || n_psit_local < 0 || n_psit < 1 || !cdet_psi_t || (n_ct_local > 0 && (!ct_index || !diag_elems)) ||
       (n_psit_local > 0 && (!psit_slot || !psit_mask))) return fail(SQMC_ERR_BAD_ARG, "bad argument");
+  if (c->htab.sys_type == 3) return fail(SQMC_ERR_UNSUPPORTED, "hf_to_psit is not built for the Hubbard model in plane waves (hubbardk)");
   if (c->mwalk <= 0) return fail(SQMC_ERR_BAD_ARG, "context has no walker arrays (mwalk=0)");
   if (c->shard_n < 1 || !c->d_grow) return fail(SQMC_ERR_BAD_ARG, "call sqmc_gpu_shard_config before sqmc_gpu_set_hf_to_psit_shard");
   if (c->dev.hb.on) return fail(SQMC_ERR_UNSUPPORTED, "hf_to_psit with proposal_method fast_heatbath is not built");

@@ -29,19 +29,28 @@ struct ChemTab {
   unsigned char orbsym[SQ_MAXORB + 1]; // 1-based
   double nuclear;
   // homogeneous electron gas (sys_type 1): plane-wave orbitals k_vectors(:, i), heg.f90:643-749
-  int sys_type, n_dim;                 // 0 = 'chem', 1 = 'heg', 2 = 'hubbard2' (real-space Hubbard, hubbard.f90)
+  int sys_type, n_dim;                 // 0 = 'chem', 1 = 'heg', 2 = 'hubbard2' (real-space Hubbard, hubbard.f90), 3 = 'hubbardk' (the same in plane waves)
   double length_cell;
   double hub_t, hub_U;                 // hubbard2: hopping and on-site repulsion
   union {
     double kvec[SQ_MAXORB + 1][3];     // heg, 1-based
     unsigned char hub_nbr[SQ_MAXORB + 1][4];   // hubbard2: get_nbr(site, LEFT/RIGHT/UP/DOWN), 0 = not allowed (more_tools.f90:223-355)
+    struct {                           // hubbardk: k_energies(i), 1-based, in the reference's orbital order (hubbard.f90:2249-2281); ubyn = U / nsites (:2224)
+      double hk_energies[SQ_MAXORB + 1];
+      double hk_ubyn;
+      int hk_lx, hk_ly;
+    };
   };
-  signed char krel[SQ_MAXORB + 1][3];  // the same in units of 2 pi / L (k_vectors_rel): exact momentum bookkeeping
+  signed char krel[SQ_MAXORB + 1][3];  // the same in units of 2 pi / L (k_vectors_rel): exact momentum bookkeeping.  hubbardk: the lattice momentum
+                                       // of orbital i as (k_x / 2 mod l_x, k_y / 2 mod l_y), k in the reference's units of pi / L (every component is even)
   int heg_nmax;                        // max |krel component|
   int c2_stride, c2_pad;               // combine_2 is stored packed: c2[i*c2_stride + j], 1-based.  heg: c2_pad = 1 when the bytes of c2 hold the
                                        // plane-wave lookup (krel + heg_nmax, base 2 heg_nmax + 1) -> orbital, 0 = no such plane wave (heg_lut)
+                                       // hubbardk: the bytes of c2 hold momentum -> orbital, nsites entries at [m_x * l_y + m_y] (the reference's
+                                       // kmap(nsites, 2 l_x - 1, 2 l_y - 1), hubbard.f90:2297-2324, folded into the one table it is)
   unsigned short c2[(SQ_MAXORB + 2) * (SQ_MAXORB + 2)];   // only the first c2_stride^2 entries are used/staged
 };
+static_assert(sizeof(ChemTab) == 10784, "ChemTab is staged into LDS by every kernel: new fields go into the union, the size stays");
 
 // efficient heat-bath proposal tables on the device (heatbath_device.h): 0-based, last index fastest
 struct HbDev {
@@ -380,9 +389,35 @@ __device__ __forceinline__ double h_hubbard(const ChemTab &t, u64 iu, u64 id, u6
   return -t.hub_t * phase;
 }
 
+// ---- Hubbard model in plane waves, hamiltonian_hubbard_k (hubbard.f90:2866-2924) without space_sym.  Diagonal: ubyn*nup*ndn left to
+// right, then k_energies over the up string's bits ascending, then the dn string's (:2893-2907).  Off-diagonal: ubyn times the two
+// strings' permutation factors when exactly one up and one dn electron have moved and the total momentum is conserved modulo the
+// reciprocal lattice (is_connected_hubbard_fast), exactly 0.0 for every other pair: the all-pairs matrix builder calls it on anything.
+// Kept out of line: the kernels of the other three operators then hold a call on a branch they never take, not its code.
+__device__ __forceinline__ int hk_orbital(const ChemTab &t, int mx, int my) {      // momentum a + b - c of three orbitals (each in [0, l)) -> orbital, 1-based
+  const int lx = t.hk_lx, ly = t.hk_ly;
+  if (mx < 0) mx += lx; else if (mx >= lx) mx -= lx;
+  if (my < 0) my += ly; else if (my >= ly) my -= ly;
+  return (int)reinterpret_cast<const unsigned char *>(t.c2)[mx * ly + my];
+}
+__device__ __noinline__ double h_hubbardk(const ChemTab &t, u64 iu, u64 id, u64 ju, u64 jd) {
+  if (iu == ju && id == jd) {
+    double me = t.hk_ubyn * t.nup * t.ndn;
+    for (u64 d = iu; d; d &= d - 1) me = me + t.hk_energies[ctz64(d) + 1];
+    for (u64 d = id; d; d &= d - 1) me = me + t.hk_energies[ctz64(d) + 1];
+    return me;
+  }
+  const u64 au = iu & ~ju, bu = ju & ~iu, ad = id & ~jd, bd = jd & ~id;
+  if (popc64(au) != 1 || popc64(bu) != 1 || popc64(ad) != 1 || popc64(bd) != 1) return 0.0;
+  const int p = ctz64(au) + 1, r = ctz64(bu) + 1, q = ctz64(ad) + 1, s = ctz64(bd) + 1;
+  if (hk_orbital(t, t.krel[p][0] + t.krel[q][0] - t.krel[r][0], t.krel[p][1] + t.krel[q][1] - t.krel[r][1]) != s) return 0.0;
+  return t.hk_ubyn * permutation_factor(iu, ju) * permutation_factor(id, jd);
+}
+
 __device__ inline double h_any(const ChemTab &t, const double *__restrict__ ints, u64 iu, u64 id, u64 ju, u64 jd) {
   if (t.sys_type == 1) return h_heg(t, iu, id, ju, jd);
   if (t.sys_type == 2) return h_hubbard(t, iu, id, ju, jd);
+  if (t.sys_type == 3) return h_hubbardk(t, iu, id, ju, jd);
   if (t.time_sym) return h_time_sym(t, ints, iu, id, ju, jd);
   int lev = excitation_level(iu, id, ju, jd);
   return lev < 0 ? 0.0 : h_level(t, ints, iu, id, ju, jd, lev);
@@ -537,6 +572,11 @@ __device__ inline double proposal_weight(const ChemTab &t, const double *__restr
     const double acc = fabs(me) * tau * prob;
     return acc * copysign(1.0, -me);
   }
+  if (t.sys_type == 3) {                 // hubbard.f90:3820, 3843-3845; prob holds proposal_prob_inv = nup * ndn * (nsites - nup)
+    const double me = h_hubbardk(t, iu, id, ju, jd);
+    const double acc = fabs(me) * tau * prob;
+    return acc * copysign(1.0, -me);
+  }
   if (!t.time_sym) return -tau * h_level(t, ints, iu, id, ju, jd, level) / prob;
   const double sqrt2 = sqrt(2.0);
   const double norm_i = (iu == id) ? sqrt2 : 1.0;
@@ -661,10 +701,37 @@ __device__ inline int propose_hubbard(const ChemTab &t, Rng &g, u64 iu, u64 id, 
   prob = (double)(t.nelec * ctr);
   return 1;
 }
+// off_diagonal_move_hubbard_k, hubbard.f90:3738-3767 (space_sym and importance sampling off): random_int(nup), random_int(ndn) and
+// random_int(nsites - nup), in that order: the chosen up and dn electrons (k-th set bits, ascending), the up hole (k-th empty orbital,
+// ascending); the dn electron goes to the orbital that takes the momentum the up electron gained.  Returns 2 with prob = the INVERSE
+// proposal probability real(nup * ndn * (nsites - nup)), or 0 when that orbital is occupied -- all three draws consumed either way.
+// Out of line, with everything passed and returned in registers (no reference to a caller's local: that would give every spawn kernel a stack).
+struct HkMove { u64 ju, jd, x; int level; };
+__device__ __noinline__ HkMove propose_hubbardk_call(const ChemTab &t, int mode, u64 x, u64 iu, u64 id) {
+  Rng g; g.mode = mode; g.x = x;
+  HkMove m; m.ju = iu; m.jd = id; m.level = 0;
+  const int cu = kth_set_wide(iu, rng_int(g, t.nup));
+  const int cd = kth_set_wide(id, rng_int(g, t.ndn));
+  const int tu = kth_set_wide(t.orb_mask & ~iu, rng_int(g, t.norb - t.nup));
+  m.x = g.x;
+  const int td = hk_orbital(t, t.krel[cd][0] - (t.krel[tu][0] - t.krel[cu][0]), t.krel[cd][1] - (t.krel[tu][1] - t.krel[cu][1]));
+  if (td == 0 || ((id >> (td - 1)) & 1)) return m;
+  m.ju = (iu & ~bit64(cu - 1)) | bit64(tu - 1);
+  m.jd = (id & ~bit64(cd - 1)) | bit64(td - 1);
+  m.level = 2;
+  return m;
+}
+__device__ __forceinline__ int propose_hubbardk(const ChemTab &t, Rng &g, u64 iu, u64 id, u64 &ju, u64 &jd, double &prob) {
+  const HkMove m = propose_hubbardk_call(t, g.mode, g.x, iu, id);
+  g.x = m.x; ju = m.ju; jd = m.jd;
+  if (m.level) prob = (double)(t.nup * t.ndn * (t.norb - t.nup));
+  return m.level;
+}
 // proposal of the system at hand (the procedure pointer `move`, do_walk.f90:126-134, 3599-3633)
 __device__ __forceinline__ int propose_any(const ChemTab &t, Rng &g, u64 iu, u64 id, u64 &ju, u64 &jd, double &prob) {
   if (t.sys_type == 1) return propose_heg(t, g, iu, id, ju, jd, prob);
   if (t.sys_type == 2) return propose_hubbard(t, g, iu, id, ju, jd, prob);
+  if (t.sys_type == 3) return propose_hubbardk(t, g, iu, id, ju, jd, prob);
   return propose_uniform(t, g, iu, id, ju, jd, prob);
 }
 

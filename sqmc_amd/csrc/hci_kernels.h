@@ -13,6 +13,53 @@
 // chemistry.f90:7148-7152): the source's H_ii, computed once per source before generation, and the packed p, q -> r, s of a double
 // excitation; DU_NONE for the self slot and for single excitations (old_diag_elem = 1e51 there, :6898, :6990).  REC = false is
 // the kernel as it always was: nothing extra is computed or written, orec_old / orec_pk are not touched.
+// hubbardk (find_connected_dets_hubbard_k, hubbard.f90:5462): up electrons x dn electrons x empty up orbitals, all ascending -- the
+// "generation order" of diag_mode 2 --, the dn electron to the orbital that conserves the total momentum, if it is empty.  A connection
+// is kept when |H c| > eps (strict; the product itself is compared, not |H| with eps / |c|, so that a tie is a tie).  Every |H| is U / nsites, so the screen selects on |c| alone: a reference determinant keeps all
+// of its connections or none.  No diagonal-update record exists for this system (the REC instantiation never gets here).  Out of line:
+// k_hci_gen holds a call on this branch, and the code of the other systems' branches is what it was.
+// Two calls, each with everything passed in registers and few enough of them that neither climbs past the kernel's own register count (a
+// reference to a caller's local would give k_hci_gen a stack): hci_gen_hubbardk counts the connections and, given ou / od, writes the
+// determinants; hci_fill_hubbardk then writes H c and e_mix_den for them (den: the source's index in raw mode, else 0).
+__device__ __noinline__ u64 hci_gen_hubbardk(const ChemTab &t, const u64 *binom, u64 n_dn_strings, u64 up, u64 dn, u64 *ou, u64 *od, u64 key_lo, u64 key_hi) {
+  const bool sliced = !(key_lo == 0 && key_hi == ~0ull);
+  u64 cnt = 0;
+#pragma nounroll
+  for (u64 eu = up; eu; eu &= eu - 1) {
+    const int p = ctz64(eu) + 1;
+#pragma nounroll
+    for (u64 ed = dn; ed; ed &= ed - 1) {
+      const int q = ctz64(ed) + 1;
+#pragma nounroll
+      for (u64 hr = t.orb_mask & ~up; hr; hr &= hr - 1) {
+        const int r = ctz64(hr) + 1;
+        const int s_ = hk_orbital(t, t.krel[q][0] - (t.krel[r][0] - t.krel[p][0]), t.krel[q][1] - (t.krel[r][1] - t.krel[p][1]));
+        if (!s_ || ((dn >> (s_ - 1)) & 1)) continue;
+        const u64 nu = (up & ~bit64(p - 1)) | bit64(r - 1), nd = (dn & ~bit64(q - 1)) | bit64(s_ - 1);
+        if (sliced) {                     // det_key, one electron at a time: few registers matter more here than loads in flight
+          u64 ru = 0, rd = 0; int k = 1;
+#pragma nounroll
+          for (u64 d = nu; d; d &= d - 1, k++) ru += binom[ctz64(d) * SQ_BINOM_STRIDE + k];
+          k = 1;
+#pragma nounroll
+          for (u64 d = nd; d; d &= d - 1, k++) rd += binom[ctz64(d) * SQ_BINOM_STRIDE + k];
+          const u64 kk = ru * n_dn_strings + rd;
+          if (!(kk >= key_lo && kk < key_hi)) continue;
+        }
+        if (ou) { ou[cnt] = nu; od[cnt] = nd; }      // null in the counting pass
+        cnt++;
+      }
+    }
+  }
+  return cnt;
+}
+__device__ __noinline__ void hci_fill_hubbardk(const ChemTab &t, u64 up, u64 dn, double c, double den, const u64 *ou, const u64 *od, double *onum, double *oden, u64 cnt) {
+#pragma nounroll
+  for (u64 k = 0; k < cnt; k++) {
+    const double mel = t.hk_ubyn * permutation_factor(up, ou[k]) * permutation_factor(dn, od[k]);
+    onum[k] = mel * c; oden[k] = den;
+  }
+}
 template <bool REC>
 __global__ void __launch_bounds__(TPB) k_hci_gen(ChemDev dev, const u64 *__restrict__ rup, const u64 *__restrict__ rdn, const double *__restrict__ coef,
                                                  double eps_var, int diag_mode, long long n_ref, int pass, u64 *__restrict__ counts,
@@ -82,6 +129,16 @@ __global__ void __launch_bounds__(TPB) k_hci_gen(ChemDev dev, const u64 *__restr
           }
         }
       }
+    }
+    if (!pass) counts[i] = cnt;
+    return;
+  }
+  if (t.sys_type == 3) {
+    if (fabs(t.hk_ubyn * c) > eps_var) {      // |H c| > eps, with the one |H| there is
+      const u64 at = base + cnt;
+      const u64 m = hci_gen_hubbardk(t, dev.binom, dev.n_dn_strings, up, dn, pass ? ou + at : nullptr, pass ? od + at : nullptr, key_lo, key_hi);
+      if (pass) hci_fill_hubbardk(t, up, dn, c, (diag_mode == 2) ? (double)i : 0.0, ou + at, od + at, onum + at, oden + at, m);
+      cnt += m;
     }
     if (!pass) counts[i] = cnt;
     return;

@@ -468,6 +468,45 @@ int sqmc_gpu_init_hubbard(const sqmc_hubbard_cfg *cfg, sqmc_gpu_ctx **out) {
   return init_common(c, (int)ns, cfg->nup, cfg->ndn, cfg->rng_mode, cfg->irand_seed, cfg->mwalk, out);
 }
 
+// Hubbard model in its plane-wave basis (hamiltonian_type 'hubbardk', space_sym off): generate_k_vectors' table (hubbard.f90:2179-2324)
+// arrives as data in the reference's orbital order; the momentum -> orbital lookup (the reference's kmap) is built here, in the bytes
+// of combine_2 this system has no use for.  Every k component is even in the reference's units of pi / L, so k / 2 mod l is the
+// lattice momentum.
+int sqmc_gpu_init_hubbardk(const sqmc_hubbardk_cfg *cfg, sqmc_gpu_ctx **out) {
+  if (!cfg || !out || !cfg->k_vectors || !cfg->k_energies) return fail(SQMC_ERR_BAD_ARG, "null argument");
+  if (cfg->l_x < 1 || cfg->l_y < 1) return fail(SQMC_ERR_BAD_ARG, "l_x and l_y must be positive");
+  const long long ns = (long long)cfg->l_x * cfg->l_y;
+  if (ns > SQ_MAXORB) return fail(SQMC_ERR_UNSUPPORTED, "l_x*l_y must be <= 64 (one 64-bit word per spin)");
+  if (cfg->l_x == 2 || cfg->l_y == 2)
+    return fail(SQMC_ERR_UNSUPPORTED, "a periodic direction of length 2 doubles a bond (the ambiguity sqmc_gpu_init_hubbard refuses): the plane-wave and the real-space model then differ");
+  if (cfg->l_x == 1 && cfg->l_y == 1) return fail(SQMC_ERR_BAD_ARG, "l_x and l_y cannot both be 1");
+  if (cfg->nup < 1 || cfg->ndn < 1 || cfg->nup > ns - 1 || cfg->ndn > ns - 1)
+    return fail(SQMC_ERR_BAD_ARG, "nup and ndn must be in 1 .. nsites-1: off_diagonal_move_hubbard_k moves one electron of each spin into a hole");
+  unsigned char lut[SQ_MAXORB]; signed char kr[SQ_MAXORB + 1][2];
+  memset(lut, 0, sizeof(lut));
+  for (int i = 1; i <= (int)ns; i++) {
+    const int kx = cfg->k_vectors[2 * (i - 1)], ky = cfg->k_vectors[2 * (i - 1) + 1];
+    if ((kx & 1) || (ky & 1)) return fail(SQMC_ERR_BAD_ARG, "k_vectors: a component is odd in units of pi/L: not a momentum of the periodic lattice");
+    const int mx = (((kx / 2) % cfg->l_x) + cfg->l_x) % cfg->l_x, my = (((ky / 2) % cfg->l_y) + cfg->l_y) % cfg->l_y;
+    if (lut[mx * cfg->l_y + my]) return fail(SQMC_ERR_BAD_ARG, "k_vectors: two orbitals share a lattice momentum modulo (2 l_x, 2 l_y); the table must hold each momentum once");
+    lut[mx * cfg->l_y + my] = (unsigned char)i; kr[i][0] = (signed char)mx; kr[i][1] = (signed char)my;
+  }                                     // nsites distinct momenta out of nsites: every one is present
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SQMC_ERR_HIP, "no HIP device: libsqmc_gpu has no CPU fallback");
+  sqmc_gpu_ctx *c = new sqmc_gpu_ctx();
+  memset((void *)c, 0, sizeof(*c));
+  HIPCHK(hipStreamCreate(&c->st));
+  ChemTab &t = c->htab;
+  t.sys_type = 3; t.n_dim = 2; t.hub_t = cfg->t; t.hub_U = cfg->U;
+  t.norb = (int)ns; t.nup = cfg->nup; t.ndn = cfg->ndn; t.ncore = 0; t.nelec = cfg->nup + cfg->ndn; t.time_sym = 0; t.z = 1; t.ngroup = 1;
+  t.orb_mask = (ns >= 64) ? ~0ull : ((1ull << ns) - 1ull);
+  t.hk_lx = cfg->l_x; t.hk_ly = cfg->l_y; t.hk_ubyn = cfg->U / (double)ns;      // ubyn = U/real(nsites), hubbard.f90:2224
+  for (int i = 1; i <= (int)ns; i++) { t.hk_energies[i] = cfg->k_energies[i - 1]; t.krel[i][0] = kr[i][0]; t.krel[i][1] = kr[i][1]; t.krel[i][2] = 0; }
+  memcpy(t.c2, lut, sizeof(lut));
+  t.c2_stride = 6; t.c2_pad = 1;        // (c2_stride only sizes the staging of the table: 6 * 6 shorts hold the 64 bytes)
+  return init_common(c, (int)ns, cfg->nup, cfg->ndn, cfg->rng_mode, cfg->irand_seed, cfg->mwalk, out);
+}
+
 static void comm_release(sqmc_gpu_ctx *c);
 static void hb_host_release(sqmc_gpu_ctx *c);
 int sqmc_gpu_finalize(sqmc_gpu_ctx *c) {
@@ -583,6 +622,7 @@ static void psit_off(sqmc_gpu_ctx *c) {
 int sqmc_gpu_set_hf_to_psit(sqmc_gpu_ctx *c, int64_t n_psit, const int64_t *psit_ct_index, const double *cdet_psi_t, const double *diag_elems, int32_t sum_order) {
   abandon_head(c);
   if (!c || n_psit < 1 || !psit_ct_index || !cdet_psi_t || !diag_elems) return fail(SQMC_ERR_BAD_ARG, "bad argument");
+  if (c->htab.sys_type == 3) return fail(SQMC_ERR_UNSUPPORTED, "hf_to_psit is not built for the Hubbard model in plane waves (hubbardk)");
   if (c->mwalk <= 0) return fail(SQMC_ERR_BAD_ARG, "context has no walker arrays (mwalk=0)");
   if (c->d_grow || c->comm) return fail(SQMC_ERR_UNSUPPORTED, "hf_to_psit is built for one rank only");
   if (!c->d_ct_up || c->n_ct < 1) return fail(SQMC_ERR_BAD_ARG, "set the C(T) table first");

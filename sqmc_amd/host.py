@@ -1193,6 +1193,114 @@ class HubbardHost:
         return s
 
 
+class HubbardKHost:
+    """Hubbard model in its plane-wave basis on a periodic l_x by l_y lattice (hamiltonian_type 'hubbardk', space_sym = .false.):
+    the orbital table of generate_k_vectors (hubbard.f90:2237-2281), the start determinant of k_hf_up / k_hf_dn (the first nup / ndn
+    orbitals of that order) and the walk set-up with a determinant-list trial wavefunction.  Connections come from the device
+    generator (find_connected_dets_hubbard_k); the z / p symmetries and the Gutzwiller trial functions are outside this path."""
+
+    def __init__(self, l_x, l_y, nup, ndn, t=1.0, U=4.0):
+        self.l_x, self.l_y, self.nup, self.ndn, self.t, self.U = int(l_x), int(l_y), int(nup), int(ndn), float(t), float(U)
+        self.norb, self.nelec = self.l_x * self.l_y, self.nup + self.ndn
+        if not abs(self.U) / self.norb > 1e-290:
+            raise ValueError("HubbardKHost needs U != 0: every connection is an element +-U/nsites, and the set-up finds them by screening on it")
+        self.k_vectors, self.k_energies = self._k_table()
+        self.hf_up, self.hf_dn = (1 << self.nup) - 1, (1 << self.ndn) - 1
+
+    def _k_table(self):
+        """k_vectors[nsites, 2] (units of pi / L) and k_energies[nsites], sorted as the reference sorts them: repeatedly the first
+        index that holds the minimum of the computed doubles"""
+        import math
+        lx, ly, n = self.l_x, self.l_y, self.l_x * self.l_y
+        kv = np.zeros((n, 2), np.int32)
+        for i in range(1, lx + 1):
+            for j in range(1, ly + 1):
+                kv[ly * (i - 1) + j - 1] = (-lx + 2 * i - (lx % 2), -ly + 2 * j - (ly % 2))
+        e = []
+        for kx, ky in kv.tolist():
+            if ly == 1:
+                e.append(-2.0 * self.t * (math.cos(math.pi * kx / float(lx))))
+            elif lx == 1:
+                e.append(-2.0 * self.t * (math.cos(math.pi * ky / float(ly))))
+            else:
+                e.append(-2.0 * self.t * (math.cos(math.pi * kx / float(lx)) + math.cos(math.pi * ky / float(ly))))
+        tmp, order = list(e), []
+        for _ in range(n):
+            lo = min(tmp)
+            j = tmp.index(lo)
+            tmp[j] = max(tmp) + 1.0
+            order.append(j)
+        return kv[order].copy(), np.array([e[j] for j in order])
+
+    def gpu(self, proposal="uniform", **kw):
+        if proposal != "uniform":
+            raise ValueError("the hubbardk context has the one proposal of its system (off_diagonal_move_hubbard_k)")
+        return GpuChem.hubbardk(self.l_x, self.l_y, self.nup, self.ndn, self.t, self.U, self.k_vectors, self.k_energies, **kw)
+
+    def _with_ctx(self, g, fn):
+        if g is not None:
+            return fn(g)
+        g = self.gpu()
+        try:
+            return fn(g)
+        finally:
+            g.close()
+
+    def connected(self, up, dn, g=None):
+        """the determinant and everything one up and one dn electron away at conserved momentum, from the device generator
+        (find_connected_dets_hubbard_k), unique, sorted.  g: a context to use; without one a context is opened for the call."""
+        def run(g):
+            cu, cd, _, _ = g.hci_connections([up], [dn], [1.0], 1e-300)
+            return cu, cd
+        return self._with_ctx(g, run)
+
+    def first_order_space(self, n_levels=1, g=None):
+        """the start determinant and everything within n_levels applications of the generator, unique, sorted"""
+        def run(g):
+            up, dn = np.array([self.hf_up], np.uint64), np.array([self.hf_dn], np.uint64)
+            fu, fd = up, dn
+            for _ in range(n_levels):
+                cu, cd, _, _ = g.hci_connections(fu, fd, np.ones(len(fu)), 1e-300)
+                new = ~_dets_in(cu, cd, up, dn)
+                if not np.any(new):
+                    break
+                fu, fd = cu[new], cd[new]
+                up, dn = np.concatenate((up, fu)), np.concatenate((dn, fd))
+                o = sort_dets(up, dn)
+                up, dn = up[o], dn[o]
+            return up, dn
+        return self._with_ctx(g, run)
+
+    def spectral_range_bound(self):
+        """(the nup + ndn highest orbital energies) - (the lowest) + U min(nup, ndn): the interaction's spectrum lies in
+        [0, U min(nup, ndn)] (it is U times the number of doubly occupied sites)"""
+        e = np.sort(self.k_energies)
+        hi = float(e[len(e) - self.nup:].sum() + e[len(e) - self.ndn:].sum())
+        lo = float(e[:self.nup].sum() + e[:self.ndn].sum())
+        return hi - lo + self.U * min(self.nup, self.ndn)
+
+    def setup_walk(self, g, n_truncate_trial_wf=20, size_deterministic=500, tau_multiplier=0.5, n_levels=1):
+        s = WalkSetup()
+        up, dn = self.first_order_space(n_levels, g)
+        w, X, _ = lowest_state(g, up, dn)
+        c = X[:, 0]
+        if c[np.argmax(np.abs(c))] < 0:
+            c = -c
+        by = np.argsort(-np.abs(c), kind="stable")
+        up_s, dn_s, c_s = up[by], dn[by], c[by]
+        n_t, n_i = _truncate_at_csf(c_s, n_truncate_trial_wf), _truncate_at_csf(c_s, size_deterministic)
+        s.psi_up, s.psi_dn = up_s[:n_t].copy(), dn_s[:n_t].copy()
+        s.psi_c = c_s[:n_t] / np.sqrt(np.dot(c_s[:n_t], c_s[:n_t]))
+        o = sort_dets(up_s[:n_i], dn_s[:n_i])
+        s.imp_up, s.imp_dn = up_s[:n_i][o].copy(), dn_s[:n_i][o].copy()
+        s.tau, s.e_var = tau_multiplier / self.spectral_range_bound(), float(w[0])
+        pc, pi_, pv = g.build_sparse_ham(s.imp_up, s.imp_dn)
+        s.prj_counts, s.prj_indices, s.prj_values = pc, pi_, -s.tau * pv
+        s.ct_up, s.ct_dn, s.ct_num, s.ct_den = g.hci_connections(s.psi_up, s.psi_dn, s.psi_c, 1e-300, diag_mode=1)
+        s.e_trial0 = float(np.dot(s.ct_num, s.ct_den) / np.dot(s.ct_den, s.ct_den))
+        return s
+
+
 def sum_left(it):
     """left-to-right floating sum (Fortran SUM over a tiny array)"""
     t = 0.0

@@ -1,6 +1,6 @@
 """Walk decks (run_type `none`): the reference's input grammar for a projector Monte Carlo walk
 (read_input, do_walk.f90:222-404; read_chem, chemistry.f90:119-245; read_heg, heg.f90:102-170;
-read_hubbard's lattice scalars) driven on the GPU path, with the host-side control plane the
+read_hubbard's lattice scalars for hubbard2 and hubbardk) driven on the GPU path, with the host-side control plane the
 reference keeps on the host: equilibration in units of nblk_eq blocks until population, permanent
 initiator weight and block energy have each gone up-down-up (do_walk.f90:3109-3159), the
 generation and block estimators with their first-order bias correction and error bars
@@ -79,10 +79,21 @@ def parse_walk_deck(text):
         d["pbc"] = _logical(nxt().split()[0])
         a = _numbers(nxt(), 2); d.update(t=a[0], U=a[1])
         a = _numbers(nxt(), 2); d.update(nup=int(a[0]), ndn=int(a[1]))
+    elif d["hamiltonian_type"] == "hubbardk":
+        # read_hubbard (hubbard.f90:153-208): l_x l_y / pbc neel_up_only / t U / nup ndn / space_sym; its trial-wavefunction block is not read
+        a = _numbers(nxt(), 2); d.update(l_x=int(a[0]), l_y=int(a[1]))
+        d["pbc"] = _logical(nxt().split()[0])
+        if not d["pbc"]:
+            raise SystemExit("sqmc_amd.walk_run: hubbardk needs pbc = t (plane waves are the orbitals of the periodic lattice)")
+        a = _numbers(nxt(), 2); d.update(t=a[0], U=a[1])
+        a = _numbers(nxt(), 2); d.update(nup=int(a[0]), ndn=int(a[1]))
+        d["space_sym"] = _logical(nxt().split()[0])
+        if d["space_sym"]:
+            raise SystemExit("sqmc_amd.walk_run: space_sym = t (the z / p symmetries of hubbardk) is not on the GPU path; use space_sym = f")
     else:
-        raise SystemExit("sqmc_amd.walk_run: hamiltonian_type %r has no GPU operator (chem, heg, hubbard2)" % d["hamiltonian_type"])
+        raise SystemExit("sqmc_amd.walk_run: hamiltonian_type %r has no GPU operator (chem, heg, hubbard2, hubbardk)" % d["hamiltonian_type"])
     if d["proposal_method"] not in ("uniform2", "uniform") and not (d["proposal_method"] in ("fast_heatbath", "cauchyschwarz") and d["hamiltonian_type"] == "chem"):
-        raise SystemExit("sqmc_amd.walk_run: proposal_method %r is not on the GPU path (uniform2: off_diagonal_move_chem / _heg / _hubbard; "
+        raise SystemExit("sqmc_amd.walk_run: proposal_method %r is not on the GPU path (uniform2: off_diagonal_move_chem / _heg / _hubbard / _hubbard_k; "
                          "fast_heatbath, CauchySchwarz: chem)" % d["proposal_method"])
     if d["proposal_method"] == "fast_heatbath" and d["hf_to_psit"]:
         raise SystemExit("sqmc_amd.walk_run: proposal_method fast_heatbath with hf_to_psit = t is not built")
@@ -90,7 +101,7 @@ def parse_walk_deck(text):
         raise SystemExit("sqmc_amd.walk_run: proposal_method CauchySchwarz with hf_to_psit = t is not built")
     if d["importance_sampling"] != 0:
         raise SystemExit("sqmc_amd.walk_run: importance_sampling must be 0")
-    if d["hf_to_psit"] and d["hamiltonian_type"] == "hubbard2":
+    if d["hf_to_psit"] and d["hamiltonian_type"] in ("hubbard2", "hubbardk"):
         raise SystemExit("sqmc_amd.walk_run: hf_to_psit = t needs the first determinant of Psi_T to be the first determinant of C(T) (chem, heg)")
     if d["use_exponential_projector"]:
         raise SystemExit("sqmc_amd.walk_run: use_exponential_projector = t is not on the GPU path (linear projector)")
@@ -208,6 +219,9 @@ def run_walk(deck, fcidump="FCIDUMP", out=sys.stdout, walkalize=None, max_equil_
     elif d["hamiltonian_type"] == "heg":
         hst = H.HegHost(d["n_dim"], d["r_s"], d["nelec"], d["nup"], d["cutoff_radius"])
         skw = dict(n_truncate_trial_wf=1, size_deterministic=max(d["size_deterministic"], 1), tau_multiplier=d["tau_multiplier"])
+    elif d["hamiltonian_type"] == "hubbardk":
+        hst = H.HubbardKHost(d["l_x"], d["l_y"], d["nup"], d["ndn"], d["t"], d["U"])
+        skw = dict(n_truncate_trial_wf=20, size_deterministic=max(d["size_deterministic"], 1), tau_multiplier=d["tau_multiplier"])
     else:
         hst = H.HubbardHost(d["l_x"], d["l_y"], d["pbc"], d["nup"], d["ndn"], d["t"], d["U"])
         skw = dict(n_truncate_trial_wf=20, size_deterministic=max(d["size_deterministic"], 1), tau_multiplier=d["tau_multiplier"])
@@ -235,7 +249,7 @@ def run_walk(deck, fcidump="FCIDUMP", out=sys.stdout, walkalize=None, max_equil_
     g = hst.gpu(rng_mode=H.RNG_COUNTER, seed=tuple(d["irand_seed"][1]), mwalk=mwalk, **gkw)
     t0 = time.perf_counter()
     # the trial wave function is rediagonalised among its own determinants, as generate_space_iterate leaves it (semistoch.f90:575, 706-712)
-    s = hst.setup_walk(g, rediagonalize=True, **skw) if d["hamiltonian_type"] != "hubbard2" else hst.setup_walk(g, **skw)
+    s = hst.setup_walk(g, rediagonalize=True, **skw) if d["hamiltonian_type"] not in ("hubbard2", "hubbardk") else hst.setup_walk(g, **skw)
     if d["tau"] != 0:                                         # an explicit tau overrides tau_multiplier (do_walk.f90:1396-1412)
         s.prj_values = s.prj_values * (d["tau"] / s.tau); s.tau = d["tau"]
     n_core = d.get("n_core_orb", 0)
