@@ -568,6 +568,28 @@ int sqmc_gpu_hci_pt2_stochastic_sample(sqmc_pt2s_plan *plan, int64_t n_distinct,
 int sqmc_gpu_hci_pt2_stochastic_stats(sqmc_pt2s_plan *plan, int64_t *n_alloc, int64_t *capacity, int64_t *last_raw, int64_t *n_samples);
 /* replaces: the deallocations at the end of second_order_pt_alias (hci.f90:1642-1660) */
 int sqmc_gpu_hci_pt2_stochastic_free(sqmc_pt2s_plan *plan);
+/* replaces: the off-diagonal histograms and weight ratios every walk of the reference keeps (off_diag_histograms = .true.,
+ * do_walk.f90:104; gen_hist at 1420-1429; filled at 3619-3640 and in add_walker, 7603-7636; max_wt_ratio / min_wt_ratio at 3649-3661,
+ * 7610-7622).  Context state, off by default: with it off a step launches exactly the kernels it launches without this entry.  On,
+ * every step's spawn kernel also bins x = abs(weight_j)/tau = |H_ij| / p(i -> j) of each off-diagonal proposal with add_to_hist's
+ * statements (more_tools.f90:5472-5495: 10001 unit-wide bins from 0, the last one open) and keeps the largest x per excitation
+ * level and the smallest x over the proposals with x > 1e-9.  Walker lists and the 16 sums are bit-identical either way; steps run
+ * un-pipelined while it is on, so the totals after N returned steps hold exactly the proposals of those N steps.
+ * on != 0 allocates and zeroes at first use (64 sets of the counters, 20 MB: blocks add to different sets, get folds them); on = 0 keeps
+ * the counts. */
+int sqmc_gpu_set_spawn_diagnostics(sqmc_gpu_ctx *ctx, int32_t on);
+/* zeroes counts, ratios and the NaN count (the reference does this once, before the run: do_walk.f90:1420-1429, 3432-3433) */
+int sqmc_gpu_reset_spawn_diagnostics(sqmc_gpu_ctx *ctx);
+/* replaces: the tables of do_walk.f90:3295-3311 and the ratios of 3313-3322, as data.  Waits for the context's streams.  Any pointer
+ * may be NULL.  nbins = 10001; bins (any walker), bins_hf (proposals of iwalk == 1, slot 0 of the resident list), bins_single and
+ * bins_double (chemistry only, proposals with weight_j != 0 by excitation_level, chemistry.f90:7162-7227): nbins counts each.
+ * max_ratio_by_level[l]: largest x among proposals of excitation level l (count_excitations on both spin strings, the smaller of the
+ * straight and the spin-swapped count with time_sym: 3654-3658; levels above 7 count as 7), -1e99 where none; max_ratio = the
+ * largest of them, max_ratio_level = the lowest level that attains it (-1: none); min_ratio = 1e99 when nothing qualified (the
+ * reference's initial values); n_nan = proposals whose x was a NaN (add_to_hist stops the run there: the caller should). */
+int sqmc_gpu_get_spawn_diagnostics(sqmc_gpu_ctx *ctx, int32_t *nbins, int64_t *bins, int64_t *bins_hf, int64_t *bins_single,
+                                   int64_t *bins_double, double max_ratio_by_level[8], double *max_ratio, int32_t *max_ratio_level,
+                                   double *min_ratio, int64_t *n_nan);
 void sqmc_gpu_free(void *p);
 
 /* HIP-event timing on the library's streams.  level 0 off; 1 = only the longest kernel on the

@@ -29,6 +29,7 @@ EXPORTS = [
     "sqmc_gpu_shard_step", "sqmc_gpu_shard_run", "sqmc_gpu_shard_time_split", "sqmc_gpu_get_rng", "sqmc_gpu_set_rng", "sqmc_gpu_tail_stats", "sqmc_gpu_last_tail", "sqmc_gpu_slowest_steps", "sqmc_gpu_set_chained_runs", "sqmc_gpu_spmv_prepare", "sqmc_gpu_davidson",
     "sqmc_gpu_spmv_apply", "sqmc_gpu_spmv_free", "sqmc_gpu_build_spmv_plan", "sqmc_gpu_spmv_sym_upper", "sqmc_gpu_hamiltonian_batch",
     "sqmc_gpu_propose_batch", "sqmc_gpu_hamiltonian_chem_batch", "sqmc_gpu_build_sparse_ham", "sqmc_gpu_hci_connections", "sqmc_gpu_hci_connections_slice", "sqmc_gpu_hci_pt2", "sqmc_gpu_hci_pt2_stochastic_prepare", "sqmc_gpu_hci_pt2_stochastic_sample", "sqmc_gpu_hci_pt2_stochastic_stats", "sqmc_gpu_hci_pt2_stochastic_free", "sqmc_gpu_hci_set_active_space", "sqmc_gpu_diag_update_batch", "sqmc_gpu_hci_set_diag_update", "sqmc_gpu_hci_connections_record", "sqmc_gpu_free", "sqmc_gpu_set_timing", "sqmc_gpu_get_timing",
+    "sqmc_gpu_set_spawn_diagnostics", "sqmc_gpu_reset_spawn_diagnostics", "sqmc_gpu_get_spawn_diagnostics",
 ]
 
 
@@ -735,6 +736,39 @@ class Pt2StochasticPlan:
         self.close()
 
 
+def _gpuchem_set_spawn_diagnostics(self, on=True):
+    """sqmc_gpu_set_spawn_diagnostics: histograms of abs(weight_j)/tau and max / min weight ratios of every step from here on
+    (off keeps the counts).  Walker lists and sums do not change; steps run un-pipelined while it is on."""
+    self.L.sqmc_gpu_set_spawn_diagnostics.argtypes = [C.c_void_p, C.c_int32]
+    _chk(self.L.sqmc_gpu_set_spawn_diagnostics(self.h, 1 if on else 0))
+
+
+def _gpuchem_reset_spawn_diagnostics(self):
+    self.L.sqmc_gpu_reset_spawn_diagnostics.argtypes = [C.c_void_p]
+    _chk(self.L.sqmc_gpu_reset_spawn_diagnostics(self.h))
+
+
+SPAWN_HIST_NBINS = 10001
+
+
+def _gpuchem_spawn_diagnostics(self):
+    """sqmc_gpu_get_spawn_diagnostics as a dict: nbins, bins / bins_hf / bins_single / bins_double (int64[nbins]; bin b of the
+    reference is index b - 1, lower bound b - 1), max_ratio_by_level (float64[8], -1e99 where no proposal), max_ratio,
+    max_ratio_level (-1: none), min_ratio (1e99: none), n_nan"""
+    nb = C.c_int32()
+    h = [np.zeros(SPAWN_HIST_NBINS, np.int64) for _ in range(4)]
+    lv = np.zeros(8); mx, mn, ml, nn = C.c_double(), C.c_double(), C.c_int32(), C.c_int64()
+    self.L.sqmc_gpu_get_spawn_diagnostics.argtypes = [C.c_void_p] * 11
+    _chk(self.L.sqmc_gpu_get_spawn_diagnostics(self.h, C.byref(nb), _p(h[0]), _p(h[1]), _p(h[2]), _p(h[3]), _p(lv), C.byref(mx), C.byref(ml),
+                                               C.byref(mn), C.byref(nn)))
+    assert nb.value == SPAWN_HIST_NBINS
+    return dict(nbins=nb.value, bins=h[0], bins_hf=h[1], bins_single=h[2], bins_double=h[3], max_ratio_by_level=lv, max_ratio=mx.value,
+                max_ratio_level=ml.value, min_ratio=mn.value, n_nan=nn.value)
+
+
+GpuChem.set_spawn_diagnostics = _gpuchem_set_spawn_diagnostics
+GpuChem.reset_spawn_diagnostics = _gpuchem_reset_spawn_diagnostics
+GpuChem.spawn_diagnostics = _gpuchem_spawn_diagnostics
 GpuChem.hci_pt2 = _gpuchem_hci_pt2
 GpuChem.hci_set_active_space = _gpuchem_hci_set_active_space
 GpuChem.diag_update_batch = _gpuchem_diag_update_batch

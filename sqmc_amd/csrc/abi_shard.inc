@@ -208,7 +208,7 @@ static int shard_begin_impl(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double 
     if (n0 > 0) {
       TBEG(spawn, st);
       if (M > n0)      // first: it posts the child count to the host mailbox as soon as it starts
-        SPAWN_LAUNCH(spawn_kind(c), 0, dim3(nblk(M - n0)), dim3(TPB), 0, st, c->dev, c->w, c->d_child_off, c->d_wchild, c->d_child_state, c->d_keys, c->d_vals,
+        SPAWN_LAUNCH(spawn_kind(c), 0, spawn_diag(c), dim3(nblk(M - n0)), dim3(TPB), 0, st, c->dev, c->w, c->d_child_off, c->d_wchild, c->d_child_state, c->d_keys, c->d_vals,
                            n0, M, p, c->rng_mode, c->seed64, c->step_no, c->invalid_key, (const DevScalars *)c->d_sc, c->d_mail, cseq, c->pack, 0, shard_owner_out(c), BucketArgs{}, FinArgs{}, PrjPre{}, 0);
       TEND(spawn, st);
     }

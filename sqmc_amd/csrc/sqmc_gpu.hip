@@ -218,6 +218,7 @@ struct sqmc_gpu_ctx {
   double slow_us[4]; long long slow_step[4];      // the slowest steps of the last run_steps call (wall clock; host jitter shows up here)
   ActiveSpace as;             // masks of the HCI generator (sqmc_gpu_hci_set_active_space); mode 0 = none
   double pt2_terms_ms;        // HIP-event time of the last sqmc_gpu_hci_pt2's term kernel (sqmc_gpu_debug_pt2_terms_ms)
+  u64 *d_sdiag; bool sdiag_on;      // spawn diagnostics (sqmc_gpu_set_spawn_diagnostics): SDIAG_REPL + 1 sets of SDIAG_WORDS words, allocated at first use; on: steps launch k_spawn's diagnostic form and enqueue no head ahead
   int du_mode;                // H_aa of the PT2 stages (sqmc_gpu_hci_set_diag_update): 0 from scratch, 1 / 2 get_new_diag_elem on one lane / 16 lanes
   bool tail_fills_hii;        // the tail that enqueues the next head is a bucket tail: it computes the H_ii of the determinants it creates itself
   bool fork_valid;            // e_fork was recorded behind the last tail (a head behind a bucket tail forks nothing and skips it)
@@ -255,14 +256,16 @@ static int psit_shard_tinv(sqmc_gpu_ctx *c, const double *ps_raw);              
 static inline int spawn_kind(const sqmc_gpu_ctx *c) {
   return c->dev.hb.on ? SPAWN_HEATBATH : (c->dev.cs.on ? (c->htab.time_sym ? SPAWN_CAUCHY_TS : SPAWN_CAUCHY) : SPAWN_UNIFORM);
 }
-#define SPAWN_LAUNCH(PK_, FUSE_, ...) do { const int pk_ = (PK_); if (pk_ == SPAWN_HEATBATH) hipLaunchKernelGGL((k_spawn<SPAWN_HEATBATH, 1>), __VA_ARGS__); \
-  else if (pk_ == SPAWN_CAUCHY) hipLaunchKernelGGL((k_spawn<SPAWN_CAUCHY, 1>), __VA_ARGS__); \
-  else if (pk_ == SPAWN_CAUCHY_TS) hipLaunchKernelGGL((k_spawn<SPAWN_CAUCHY_TS, 1>), __VA_ARGS__); \
-  else if (FUSE_) hipLaunchKernelGGL((k_spawn<SPAWN_UNIFORM, 1>), __VA_ARGS__); else hipLaunchKernelGGL((k_spawn<SPAWN_UNIFORM, 0>), __VA_ARGS__); } while (0)
-#define SPAWN_LAUNCH_EXT(PK_, FUSE_, ...) do { const int pk_ = (PK_); if (pk_ == SPAWN_HEATBATH) hipExtLaunchKernelGGL((k_spawn<SPAWN_HEATBATH, 1>), __VA_ARGS__); \
-  else if (pk_ == SPAWN_CAUCHY) hipExtLaunchKernelGGL((k_spawn<SPAWN_CAUCHY, 1>), __VA_ARGS__); \
-  else if (pk_ == SPAWN_CAUCHY_TS) hipExtLaunchKernelGGL((k_spawn<SPAWN_CAUCHY_TS, 1>), __VA_ARGS__); \
-  else if (FUSE_) hipExtLaunchKernelGGL((k_spawn<SPAWN_UNIFORM, 1>), __VA_ARGS__); else hipExtLaunchKernelGGL((k_spawn<SPAWN_UNIFORM, 0>), __VA_ARGS__); } while (0)
+// SD_: spawn_diag(c), the diagnostics' words or null; it picks the DIAG form and is passed on as the kernel's last argument
+static inline u64 *spawn_diag(const sqmc_gpu_ctx *c) { return c->sdiag_on ? c->d_sdiag : (u64 *)nullptr; }
+#define SPAWN_LAUNCH_K(L_, PK_, FUSE_, DG_, ...) do { const int pk_ = (PK_); if (pk_ == SPAWN_HEATBATH) L_((k_spawn<SPAWN_HEATBATH, 1, DG_>), __VA_ARGS__); \
+  else if (pk_ == SPAWN_CAUCHY) L_((k_spawn<SPAWN_CAUCHY, 1, DG_>), __VA_ARGS__); \
+  else if (pk_ == SPAWN_CAUCHY_TS) L_((k_spawn<SPAWN_CAUCHY_TS, 1, DG_>), __VA_ARGS__); \
+  else if (FUSE_) L_((k_spawn<SPAWN_UNIFORM, 1, DG_>), __VA_ARGS__); else L_((k_spawn<SPAWN_UNIFORM, 0, DG_>), __VA_ARGS__); } while (0)
+#define SPAWN_LAUNCH(PK_, FUSE_, SD_, ...) do { u64 *sd_ = (SD_); if (sd_) SPAWN_LAUNCH_K(hipLaunchKernelGGL, PK_, FUSE_, 1, __VA_ARGS__, sd_); \
+  else SPAWN_LAUNCH_K(hipLaunchKernelGGL, PK_, FUSE_, 0, __VA_ARGS__, sd_); } while (0)
+#define SPAWN_LAUNCH_EXT(PK_, FUSE_, SD_, ...) do { u64 *sd_ = (SD_); if (sd_) SPAWN_LAUNCH_K(hipExtLaunchKernelGGL, PK_, FUSE_, 1, __VA_ARGS__, sd_); \
+  else SPAWN_LAUNCH_K(hipExtLaunchKernelGGL, PK_, FUSE_, 0, __VA_ARGS__, sd_); } while (0)
 #include "bucket_kernels.h"
 #include "door_kernels.h"
 #include "diag_update.h"
@@ -530,6 +533,7 @@ int sqmc_gpu_finalize(sqmc_gpu_ctx *c) {
   hipFree(c->d_ps_loc); hipFree(c->d_ps_of); hipFree(c->d_ps_impof); hipFree(c->d_ps_c); hipFree(c->d_ps_diag); hipFree(c->d_ps_dwct); hipFree(c->d_ps_dwps);
   hipFree(c->d_ps_dwimp); hipFree(c->d_ps_p2); hipFree(c->d_ps_part); hipFree(c->d_ps_raw); hipFree(c->stage_mem); hipFree(c->d_bpar);
   hipFree(c->d_ps_num); hipFree(c->d_ps_den); hipFree(c->d_ps_tx);
+  hipFree(c->d_sdiag);
   hipFree(c->d_sc); hipHostFree(c->h_sc); if (c->h_mail) hipHostFree((void *)c->h_mail);
   for (int i = 0; i < NTIMERS; i++) { hipEventDestroy(c->ev0[i]); hipEventDestroy(c->ev1[i]); }
   hipEventDestroy(c->e_fork); hipEventDestroy(c->e_join); hipEventDestroy(c->e_cnt); hipEventDestroy(c->e_spawned);
@@ -997,10 +1001,10 @@ static int enqueue_head(sqmc_gpu_ctx *c, const StepP &p, u64 step, long long n0,
   const size_t spawn_lds = std::max<size_t>(hb.B > 0 ? (size_t)BK_PART_LDS(hb.B) : 0, hq_blk > 0 ? (size_t)(TPB / 16) * bk_hii_terms_of(c->htab.nup, c->htab.ndn) * 8 : 0);
   if (nfree > 0) {
     if (s0)
-      SPAWN_LAUNCH_EXT(spawn_kind(c), spawn_fuse, dim3(nblk(nfree) + (spawn_fin.on ? 1 : 0) + hq_blk + (pp.n_imp > 0 ? nblk(pp.n_imp, TPB / 64) : 0) + ((hb.kb || hb.kb_out) ? 1 : 0)), dim3(TPB), spawn_lds, st, s0, s1, 0, c->dev, c->w, c->d_child_off, c->d_wchild,
+      SPAWN_LAUNCH_EXT(spawn_kind(c), spawn_fuse, spawn_diag(c), dim3(nblk(nfree) + (spawn_fin.on ? 1 : 0) + hq_blk + (pp.n_imp > 0 ? nblk(pp.n_imp, TPB / 64) : 0) + ((hb.kb || hb.kb_out) ? 1 : 0)), dim3(TPB), spawn_lds, st, s0, s1, 0, c->dev, c->w, c->d_child_off, c->d_wchild,
                             c->d_child_state, c->d_keys, c->d_vals, n0, M, p, c->rng_mode, c->seed64, step, c->invalid_key, (const DevScalars *)c->d_sc, c->d_mail, *cseq, c->pack, dev_n ? 1 : 0, oo, hb, spawn_fin, pp, (spawn_fin.on ? 1 : 0) + hq_blk + (pp.n_imp > 0 ? nblk(pp.n_imp, TPB / 64) : 0) + ((hb.kb || hb.kb_out) ? 1 : 0));
     else
-      SPAWN_LAUNCH(spawn_kind(c), spawn_fuse, dim3(nblk(nfree) + (spawn_fin.on ? 1 : 0) + hq_blk + (pp.n_imp > 0 ? nblk(pp.n_imp, TPB / 64) : 0) + ((hb.kb || hb.kb_out) ? 1 : 0)), dim3(TPB), spawn_lds, st, c->dev, c->w, c->d_child_off, c->d_wchild, c->d_child_state, c->d_keys, c->d_vals,
+      SPAWN_LAUNCH(spawn_kind(c), spawn_fuse, spawn_diag(c), dim3(nblk(nfree) + (spawn_fin.on ? 1 : 0) + hq_blk + (pp.n_imp > 0 ? nblk(pp.n_imp, TPB / 64) : 0) + ((hb.kb || hb.kb_out) ? 1 : 0)), dim3(TPB), spawn_lds, st, c->dev, c->w, c->d_child_off, c->d_wchild, c->d_child_state, c->d_keys, c->d_vals,
                          n0, M, p, c->rng_mode, c->seed64, step, c->invalid_key, (const DevScalars *)c->d_sc, c->d_mail, *cseq, c->pack, dev_n ? 1 : 0, oo, hb, spawn_fin, pp, (spawn_fin.on ? 1 : 0) + hq_blk + (pp.n_imp > 0 ? nblk(pp.n_imp, TPB / 64) : 0) + ((hb.kb || hb.kb_out) ? 1 : 0));
   } else if (s0) { hipEventRecord(s0, st); hipEventRecord(s1, st); }
   HIPCHK(hipEventRecord(c->e_spawned, st)); c->spawned_valid = true;
@@ -1434,6 +1438,7 @@ int sqmc_gpu_step(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double out[16]) {
   if (!c->in_run) c->pipeline_next = c->chained_runs && sp->reached_w_abs_gen == 2 && mode != SQMC_RNG_REPLAY && !getenv("SQMC_NO_PIPELINE");
   { static const bool psit_no_pipe = getenv("SQMC_PSIT_NO_PIPELINE") != nullptr;      // hf_to_psit: the head (gate, scan, spawn) behind the tail like any other step's; the gate stays a kernel of its own
     if (c->psit_on && psit_no_pipe) c->pipeline_next = false; }
+  if (c->sdiag_on) c->pipeline_next = false;      // spawn diagnostics: a head enqueued ahead would count proposals of a step that may never be returned
   collect_timers(c);
   c->nt = 0;
   hipStream_t st2 = c->st2;
@@ -1468,10 +1473,10 @@ int sqmc_gpu_step(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double out[16]) {
     cseq = ++c->cnt_seq;
     if (M > n0) {
       if (t_spawn >= 0)
-        SPAWN_LAUNCH_EXT(spawn_kind(c), 0, dim3(nblk(M - n0)), dim3(TPB), 0, st, c->ev0[t_spawn], c->ev1[t_spawn], 0, c->dev, c->w, c->d_child_off, c->d_wchild,
+        SPAWN_LAUNCH_EXT(spawn_kind(c), 0, spawn_diag(c), dim3(nblk(M - n0)), dim3(TPB), 0, st, c->ev0[t_spawn], c->ev1[t_spawn], 0, c->dev, c->w, c->d_child_off, c->d_wchild,
                               c->d_child_state, c->d_keys, c->d_vals, n0, M, p, mode, seed, step, c->invalid_key, (const DevScalars *)c->d_sc, c->d_mail, cseq, c->pack, 0, OwnerOut{nullptr, nullptr, 0, 0}, BucketArgs{}, FinArgs{}, PrjPre{}, 0);
       else
-        SPAWN_LAUNCH(spawn_kind(c), 0, dim3(nblk(M - n0)), dim3(TPB), 0, st, c->dev, c->w, c->d_child_off, c->d_wchild, c->d_child_state, c->d_keys, c->d_vals,
+        SPAWN_LAUNCH(spawn_kind(c), 0, spawn_diag(c), dim3(nblk(M - n0)), dim3(TPB), 0, st, c->dev, c->w, c->d_child_off, c->d_wchild, c->d_child_state, c->d_keys, c->d_vals,
                            n0, M, p, mode, seed, step, c->invalid_key, (const DevScalars *)c->d_sc, c->d_mail, cseq, c->pack, 0, OwnerOut{nullptr, nullptr, 0, 0}, BucketArgs{}, FinArgs{}, PrjPre{}, 0);
     } else if (t_spawn >= 0) { hipEventRecord(c->ev0[t_spawn], st); hipEventRecord(c->ev1[t_spawn], st); }
   } else {
@@ -1532,7 +1537,7 @@ static int run_steps(sqmc_gpu_ctx *c, sqmc_popctl *pc, int64_t nsteps, double *s
     // pipelined head: once the target population has been reached tau and r_initiator stay put, and the head of a step
     // (gate, scan, spawn) depends on nothing else that this step's sums could change
     c->pipeline_next = ((one_step == (step_fn)sqmc_gpu_step || (one_step == (step_fn)sqmc_gpu_shard_step && c->comm != nullptr && !c->psit_on && !getenv("SQMC_SHARD_NO_PIPELINE"))) && (it + 1 < nsteps || (c->chained_runs && one_step == (step_fn)sqmc_gpu_step)) &&
-                        pc->reached_w_abs_gen == 2 && c->rng_mode != SQMC_RNG_REPLAY && !getenv("SQMC_NO_PIPELINE"));
+                        pc->reached_w_abs_gen == 2 && c->rng_mode != SQMC_RNG_REPLAY && !getenv("SQMC_NO_PIPELINE") && !c->sdiag_on);
     double out[16];
     int r = one_step(c, &sp, out);
     c->pipeline_next = false;
@@ -1657,6 +1662,7 @@ int sqmc_gpu_debug_premerge(sqmc_gpu_ctx *c, int64_t cap, int64_t *n0, int64_t *
 
 #include "abi_shard.inc"
 #include "abi_doors.inc"
+#include "abi_spawn_diag.inc"
 #include "davidson.inc"
 #include "heatbath_setup.inc"
 

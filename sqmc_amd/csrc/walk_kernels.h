@@ -299,21 +299,87 @@ extern "C" int sqmc_gpu_debug_prof(unsigned long long *out) { return (int)hipMem
 #else
 #define PROF(K)
 #endif
+// Spawn diagnostics (sqmc_gpu_set_spawn_diagnostics): the reference's histograms of abs(weight_j)/tau = |H_ij| / p(i -> j) and its max / min
+// weight ratios (do_walk.f90:1420-1429, 3619-3661, add_walker 7603-7636).  One set of 64-bit words in HBM:
+//   [0, 4 NB)  counts: any walker | iwalk == 1 (slot 0) | singles | doubles      (NB = 10001 unit-wide bins, gen_hist more_tools.f90:5449-5469)
+//   [4 NB, +8) largest ratio per excitation level 0..7 (higher levels clamped), as the bit pattern of the positive double
+//   then       smallest ratio, as the COMPLEMENT of its bit pattern (so that 0 means "none yet" in every word and the set starts as zeros), NaN count
+// The context keeps SDIAG_REPL such sets and a spawning block adds to set (block index mod SDIAG_REPL): a step's proposals crowd into a few
+// dozen bins, and adds to one word serialise in L2 however they are spread over wavefronts; k_sdiag_reduce folds the sets when they are read.
+#define SDIAG_NB 10001
+#define SDIAG_MAX (4 * SDIAG_NB)
+#define SDIAG_MIN (SDIAG_MAX + 8)
+#define SDIAG_NAN (SDIAG_MIN + 1)
+#define SDIAG_WORDS (SDIAG_NAN + 1)
+#define SDIAG_REPL 64
+__global__ void __launch_bounds__(TPB) k_sdiag_reduce(const u64 *__restrict__ sets, u64 *__restrict__ out) {
+  const int i = (int)(blockIdx.x * TPB + threadIdx.x);
+  if (i >= SDIAG_WORDS) return;
+  const bool by_max = i >= SDIAG_MAX && i <= SDIAG_MIN;
+  u64 v = 0;
+  for (int r = 0; r < SDIAG_REPL; r++) { const u64 x = sets[(size_t)r * SDIAG_WORDS + i]; v = by_max ? (x > v ? x : v) : v + x; }
+  out[i] = v;
+}
+// One add per distinct key per wavefront: nearly all proposals of a step fall into a handful of bins, and 64 lanes adding to one word
+// one by one serialise in L2.  Every lane of the wavefront calls this (key < 0: nothing to add).
+__device__ __forceinline__ void sdiag_wave_add(u64 *hist, int key) {
+  const int lane = (int)(threadIdx.x & 63);
+  u64 todo = __ballot(key >= 0);
+  while (todo) {
+    const int leader = __ffsll((unsigned long long)todo) - 1;
+    const int k = __shfl(key, leader, 64);
+    const u64 same = __ballot(key == k);
+    if (lane == leader) atomicAdd((unsigned long long *)&hist[k], (unsigned long long)__popcll(same));
+    todo &= ~same;
+  }
+}
+// One proposal of this lane's child (has: the lane holds one; every lane of the wavefront calls).  wj is weight_j as the proposal returned
+// it, before the parent's share is multiplied in and before hf_to_psit zeroes a child onto the first state (do_walk.f90:3636 / 3664 / 3676).
+__device__ __forceinline__ void sdiag_record(u64 *sd, const ChemTab &t, bool has, bool hf, double wj, double tau, u64 iu, u64 id, u64 ju, u64 jd) {
+  int bin = -1, cls = -1;
+  if (has) {
+    const double x = fabs(wj) / tau;
+    if (x != x) atomicAdd((unsigned long long *)&sd[SDIAG_NAN], 1ull);      // add_to_hist stops the run on a NaN (more_tools.f90:5472-5495): the host does
+    else if (x >= 0.0) {                           // `if (x<lbounds(1)) return` (a negative tau)
+      // ibin = min(nbins, int(1 + (nbins-1)*(x-lbounds(1))/(lbounds(nbins)-lbounds(1)))), left to right; clamped before the conversion
+      const double y = 10000.0 * (x - 0.0) / (10000.0 - 0.0);
+      const double z = 1 + y;
+      bin = (z < (double)SDIAG_NB) ? (int)z - 1 : SDIAG_NB - 1;
+      if (t.sys_type == 0 && wj != 0.0) {          // excitation_level, chemistry.f90:7162-7227 (a move without weight left no determinant to classify)
+        const int lv = __popcll(iu & ~ju) + __popcll(id & ~jd);
+        if (lv == 1 || lv == 2) cls = (lv - 1) * SDIAG_NB + bin;
+      }
+      if (x > 1e-9) {                              // do_walk.f90:3649-3661
+        int lv = __popcll(iu & ~ju) + __popcll(id & ~jd);
+        if (t.time_sym) { const int sw = __popcll(iu & ~jd) + __popcll(id & ~ju); lv = sw < lv ? sw : lv; }
+        lv = lv > 7 ? 7 : lv;
+        const u64 xb = (u64)__double_as_longlong(x);      // positive doubles order as their bit patterns
+        // the words only grow: a stale read lets a needless atomic through, never drops one
+        if (xb > sd[SDIAG_MAX + lv]) atomicMax((unsigned long long *)&sd[SDIAG_MAX + lv], (unsigned long long)xb);
+        if (~xb > sd[SDIAG_MIN]) atomicMax((unsigned long long *)&sd[SDIAG_MIN], (unsigned long long)~xb);
+      }
+    }
+  }
+  sdiag_wave_add(sd, bin);
+  if (t.sys_type == 0) sdiag_wave_add(sd + 2 * SDIAG_NB, cls);
+  if (__ballot(hf && bin >= 0)) sdiag_wave_add(sd + SDIAG_NB, hf ? bin : -1);
+}
 // one thread per child proposal; parent found by binary search in the child offsets
 // PK: the proposal -- SPAWN_UNIFORM (uniform2 / HEG / Hubbard), SPAWN_HEATBATH (fast_heatbath, two walker slots per child),
 //     SPAWN_CAUCHY (CauchySchwarz, one slot), SPAWN_CAUCHY_TS (CauchySchwarz with time_sym: the move ends in cs_time_sym_weight) -- each a
 //     kernel of its own, so that the uniform proposal and the plain Cauchy-Schwarz one keep their registers
 // FUSE: the short-list extras (children grouped by key range for the bucket tail, the block with the final sums, the projector rows);
 //       large populations run FUSE = 0, whose register and LDS budget is the plain spawn's (7 waves per SIMD)
+// DIAG: the diagnostic form (sdiag != null) also bins every proposal's weight multiplier (sdiag_record); DIAG = 0 compiles none of it
 #define SPAWN_UNIFORM 0
 #define SPAWN_HEATBATH 1
 #define SPAWN_CAUCHY 2
 #define SPAWN_CAUCHY_TS 3
-template <int PK, int FUSE>
+template <int PK, int FUSE, int DIAG>
 __global__ void __launch_bounds__(TPB) k_spawn(ChemDev dev, WalkArr w, const u64 *__restrict__ child_off, const double *__restrict__ wchild,
                                                const u64 *__restrict__ child_state, u64 *__restrict__ keys, u32 *__restrict__ vals,
                                                long long n0_arg, long long cap_all, StepP p, int mode, u64 seed, u64 step, u64 invalid_key, const DevScalars *sc,
-                                               HostMail *mail, u64 cnt_seq, int pack, int n_on_device, OwnerOut oo, BucketArgs ba, FinArgs fin, PrjPre pp, int n_extra) {
+                                               HostMail *mail, u64 cnt_seq, int pack, int n_on_device, OwnerOut oo, BucketArgs ba, FinArgs fin, PrjPre pp, int n_extra, u64 *sdiag) {
   // The first n_extra blocks do not spawn (they come first in the grid so that they run beside the spawning blocks from the start:
   // behind them they waited for the thousands of empty blocks a capacity-sized grid has, and the kernel for them -- 32 against
   // 20 us).  Steps whose child offsets came out of the bucket tail have no scan launch to carry the last step's final sums:
@@ -420,6 +486,7 @@ __global__ void __launch_bounds__(TPB) k_spawn(ChemDev dev, WalkArr w, const u64
   const long long c = c0 + threadIdx.x;
   const bool active = c < nchildren;
   u64 ckey = invalid_key;
+  bool dg_hf = false; int dg_n = 0; double dg_w[2] = {0.0, 0.0}; u64 dg_iu = 0, dg_id = 0, dg_ju[2] = {0, 0}, dg_jd[2] = {0, 0};      // DIAG: what sdiag_record needs, outside the divergent part
   if (active) {
     long long ip;
     if (s_win[SPAWN_WIN - 1] <= (u64)c) {                 // beyond the window (many childless parents in between)
@@ -439,7 +506,11 @@ __global__ void __launch_bounds__(TPB) k_spawn(ChemDev dev, WalkArr w, const u64
     PROF(3);
     if (PK == SPAWN_HEATBATH) {  // proposal_method fast_heatbath: both slots of the child are written (weight 0: no walker), do_walk.f90:3604-3611
       u64 ju2[2], jd2[2]; double wj2[2];
-      propose_heatbath(t, dev.integrals, dev.hb, g, p.tau, iu, id, ju2, jd2, wj2);
+      const int n_new = propose_heatbath(t, dev.integrals, dev.hb, g, p.tau, iu, id, ju2, jd2, wj2);
+      if (DIAG) {      // one entry per slot that holds a move; no move at all: add_walker is called once, with weight 0 (do_walk.f90:3605-3611)
+        dg_hf = ip == 0; dg_n = n_new == 2 ? 2 : 1; dg_iu = iu; dg_id = id;
+        dg_w[0] = wj2[0]; dg_ju[0] = ju2[0]; dg_jd[0] = jd2[0]; dg_w[1] = wj2[1]; dg_ju[1] = ju2[1]; dg_jd[1] = jd2[1];
+      }
       spawn_emit(dev, w, keys, vals, n0, 2 * c, pflg, ju2[0], jd2[0], wch * wj2[0], p, invalid_key, pack, oo);
       spawn_emit(dev, w, keys, vals, n0, 2 * c + 1, pflg, ju2[1], jd2[1], wch * wj2[1], p, invalid_key, pack, oo);
     } else {
@@ -450,10 +521,17 @@ __global__ void __launch_bounds__(TPB) k_spawn(ChemDev dev, WalkArr w, const u64
     if (level > 0) {
       wj = (PK == SPAWN_CAUCHY_TS) ? cs_time_sym_weight(t, dev.cs, dev.integrals, p.tau, iu, id, ju, jd, level, prob)
                                    : proposal_weight(t, dev.integrals, p.tau, iu, id, ju, jd, level, prob);
+      if (DIAG) dg_w[0] = wj;
       wj = wch * wj;
     }
+    if (DIAG) { dg_hf = ip == 0; dg_n = 1; dg_iu = iu; dg_id = id; dg_ju[0] = ju; dg_jd[0] = jd; }
     ckey = spawn_emit(dev, w, keys, vals, n0, c, pflg, ju, jd, wj, p, invalid_key, pack, oo);
     }
+  }
+  if (DIAG) {
+    u64 *sd = sdiag + (size_t)(bx % SDIAG_REPL) * SDIAG_WORDS;
+    sdiag_record(sd, t, dg_n > 0, dg_hf, dg_w[0], p.tau, dg_iu, dg_id, dg_ju[0], dg_jd[0]);
+    if (PK == SPAWN_HEATBATH) sdiag_record(sd, t, dg_n > 1, dg_hf, dg_w[1], p.tau, dg_iu, dg_id, dg_ju[1], dg_jd[1]);
   }
   if (part) bucket_partition_block(s_spl, s_wcnt, pws, active && ckey != invalid_key, (u32)ckey, (ckey << 32) | (u64)(n0 + c), (long long)bx, ba);
   PROF(5);

@@ -22,6 +22,7 @@ module sqmc_gpu_mod
   public :: sqmc_gpu_setup_cauchy_schwarz, sqmc_gpu_propose_cauchy_schwarz_batch
   public :: sqmc_gpu_diag_update_batch, sqmc_gpu_hci_set_diag_update, sqmc_gpu_hci_connections_record
   public :: sqmc_gpu_hci_pt2_stochastic_prepare, sqmc_gpu_hci_pt2_stochastic_sample, sqmc_gpu_hci_pt2_stochastic_stats, sqmc_gpu_hci_pt2_stochastic_free
+  public :: sqmc_gpu_set_spawn_diagnostics, sqmc_gpu_reset_spawn_diagnostics, sqmc_gpu_get_spawn_diagnostics
   public :: sqmc_gpu_check
 
   integer(c_int), parameter, public :: SQMC_RNG_REPLAY = 0, SQMC_RNG_COUNTER = 1
@@ -146,6 +147,21 @@ module sqmc_gpu_mod
       import; type(c_ptr), value :: ctx; integer(c_int64_t), value :: n; real(c_double), intent(in) :: old_diag(*)
       integer(c_int32_t), intent(in) :: pqrs(*); integer(c_int64_t), intent(in) :: new_up(*), new_dn(*); integer(c_int32_t), value :: form
       real(c_double), intent(out) :: new_diag(*)
+    end function
+    ! off_diag_histograms (do_walk.f90:104, 3619-3661, 7603-7636): histograms of abs(weight_j)/tau and the max / min weight ratios.
+    ! The arrays of get are optional on the C side: pass c_null_ptr for any that is not wanted.
+    integer(c_int) function sqmc_gpu_set_spawn_diagnostics(ctx, on) bind(C, name='sqmc_gpu_set_spawn_diagnostics')
+      import; type(c_ptr), value :: ctx; integer(c_int32_t), value :: on
+    end function
+    integer(c_int) function sqmc_gpu_reset_spawn_diagnostics(ctx) bind(C, name='sqmc_gpu_reset_spawn_diagnostics')
+      import; type(c_ptr), value :: ctx
+    end function
+    integer(c_int) function sqmc_gpu_get_spawn_diagnostics(ctx, nbins, bins, bins_hf, bins_single, bins_double, max_ratio_by_level, max_ratio, &
+        max_ratio_level, min_ratio, n_nan) bind(C, name='sqmc_gpu_get_spawn_diagnostics')
+      import; type(c_ptr), value :: ctx; integer(c_int32_t), intent(out) :: nbins
+      type(c_ptr), value :: bins, bins_hf, bins_single, bins_double      ! integer(c_int64_t)(10001) each, or c_null_ptr
+      real(c_double), intent(out) :: max_ratio_by_level(8), max_ratio, min_ratio
+      integer(c_int32_t), intent(out) :: max_ratio_level; integer(c_int64_t), intent(out) :: n_nan
     end function
     ! H_aa of the PT2 stages: 0 from scratch (default), 1 / 2 the O(N) update on one lane / by lane groups
     integer(c_int) function sqmc_gpu_hci_set_diag_update(ctx, mode) bind(C, name='sqmc_gpu_hci_set_diag_update')

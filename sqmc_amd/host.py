@@ -602,7 +602,8 @@ class GpuWalk:
     """A C2-style semistochastic walk resident on one GPU."""
 
     def __init__(self, host, w_target, w_begin=None, mwalk=None, n_truncate_trial_wf=100, size_deterministic=1000, tau_multiplier=0.1,
-                 e_trial=None, seed=(1346, 5634, 6635, 4361), rng_mode=RNG_COUNTER, min_wt=0.5, hf_to_psit=False, sum_order=1, proposal="uniform"):
+                 e_trial=None, seed=(1346, 5634, 6635, 4361), rng_mode=RNG_COUNTER, min_wt=0.5, hf_to_psit=False, sum_order=1, proposal="uniform",
+                 spawn_diagnostics=False):
         self.host = host
         w_begin = w_begin if w_begin is not None else w_target
         mwalk = mwalk or int(max(4 * (w_target / min_wt + size_deterministic), 200000))
@@ -632,6 +633,8 @@ class GpuWalk:
             self.g.set_ct_table(s.ct_up, s.ct_dn, s.ct_num, s.ct_den)
             wk = initial_walkers(s, w_begin)
         self.g.upload_walkers(wk)
+        if spawn_diagnostics:
+            self.g.set_spawn_diagnostics(True)
         self.pc = PopControl(s.tau, e_trial if e_trial is not None else s.e_trial0, w_target)
         self.w_abs = float(np.abs(wk["wt"]).sum())
         self.min_wt = min_wt
@@ -656,8 +659,54 @@ class GpuWalk:
         self.w_abs = pc.w_abs_gen
         return stats, totals
 
+    def spawn_diagnostics(self):
+        """histograms of abs(weight_j)/tau and max / min weight ratios of the steps so far (GpuChem.spawn_diagnostics)"""
+        return self.g.spawn_diagnostics()
+
     def close(self):
         self.g.close()
+
+
+def _fortran_es(x, width, dec):
+    """Fortran ESw.d (two exponent digits, three without the E where the exponent needs them)"""
+    if x != x:
+        return "NaN".rjust(width)
+    m, e = ("%.*e" % (dec, x)).split("e")
+    e = int(e)
+    return ("%sE%+03d" % (m, e) if abs(e) < 100 else "%s%+04d" % (m, e)).rjust(width)
+
+
+def format_spawn_histograms(diag, chem=True, spectral_range=None):
+    """The two tables every walk of the reference ends with (do_walk.f90:3295-3311), from a spawn_diagnostics() dict, as one string.
+    Rows: '(i5,f10.3,9i11)' and '(i5,f10.3,3i11,3f10.6)', totals '(a,9x,9i11)'; the headers and the HF total are list-directed
+    writes (a leading blank; an 8-byte integer takes 21 columns).  The percentages divide by the column sums and print NaN where a
+    sum is 0, as Fortran's 0./0. does in the Singles / Doubles columns of every operator but chemistry (chem = False only says so:
+    those columns are then all zero).  spectral_range = diagonal_ham_highest - diagonal_ham_lowest: adds the line of 3320,
+    'Max Ratio, Min Ratio, tau_multiplier, tau for spawning max wt 1=' '(9es12.4)', which the reference prints at ipr >= 1."""
+    nb = int(diag["nbins"])
+    hf, sg, db, an = (np.asarray(diag[k], np.int64) for k in ("bins_hf", "bins_single", "bins_double", "bins"))
+    if not chem and (sg.any() or db.any()):
+        raise ValueError("singles / doubles are classified for chemistry only")
+    def i11(v):
+        t = "%11d" % v
+        return t if len(t) == 11 else "*" * 11
+    def f106(n, tot):
+        if tot == 0:
+            return "NaN".rjust(10)
+        t = "%10.6f" % float(np.float32(n) / np.float32(tot))      # float(n)/float(sum): a quotient of default reals, rounded to single
+        return t if len(t) == 10 else "*" * 10
+    out = [" Histogram of abs weight multipliers spawned by HF:", " Bin,Lowerbound,Count"]
+    out += ["%5d%10.3f%s" % (i + 1, float(i), i11(hf[i])) for i in range(nb)]
+    out.append(" Total=%21d" % int(hf.sum()))
+    out += [" Histogram of abs weight multipliers spawned by any states:", " Bin,Lowerbound,Singles,Doubles,Total,Singles%,Doubles%,Total%"]
+    ts, td, ta = int(sg.sum()), int(db.sum()), int(an.sum())
+    out += ["%5d%10.3f%s%s%s%s%s%s" % (i + 1, float(i), i11(sg[i]), i11(db[i]), i11(an[i]), f106(sg[i], ts), f106(db[i], td), f106(an[i], ta))
+            for i in range(nb)]
+    out.append("Total=" + " " * 9 + i11(ts) + i11(td) + i11(ta))
+    if spectral_range is not None:
+        mx, mn = float(diag["max_ratio"]), float(diag["min_ratio"])
+        out.append("Max Ratio, Min Ratio, tau_multiplier, tau for spawning max wt 1=" + "".join(_fortran_es(v, 12, 4) for v in (mx, mn, spectral_range / mx, 1 / mx)))
+    return "\n".join(out) + "\n"
 
 
 # ------------------------------------------------------------------------ multi-rank glue
@@ -794,11 +843,12 @@ class ShardedWalk:
 
     def __init__(self, host, w_target, rank, world, w_begin=None, mwalk=None, n_truncate_trial_wf=100, size_deterministic=1000,
                  tau_multiplier=0.1, e_trial=None, seed=(1346, 5634, 6635, 4361), min_wt=0.5, device_index=0, n_equil_steps=10**9, owner_hash=0,
-                 semistochastic=True, hf_to_psit=False, sum_order=1, proposal="uniform"):
+                 semistochastic=True, hf_to_psit=False, sum_order=1, proposal="uniform", spawn_diagnostics=False):
         """proposal: "uniform" (the system's own), "cauchyschwarz" (chem: proposal_method CauchySchwarz) or "heatbath" (chem:
         proposal_method fast_heatbath; every rank builds the tables, a child holds two walker slots)"""
         import torch
         self.rank, self.world, self.min_wt = rank, world, min_wt
+        self._spawn_diag = bool(spawn_diagnostics)
         self.psit = bool(hf_to_psit)
         if proposal not in ("uniform", "cauchyschwarz", "heatbath"):
             raise ValueError("ShardedWalk: proposal %r (uniform, cauchyschwarz or heatbath)" % (proposal,))
@@ -880,6 +930,8 @@ class ShardedWalk:
         self.w_abs = float(np.abs(wk["wt"]).sum())          # global
         self.n_imp_global = len(s.imp_up) if self.semi else 0
         self.in_library = False
+        if self._spawn_diag:
+            g.set_spawn_diagnostics(True)
 
     def attach_rccl(self):
         """Give the library its own RCCL communicator (sqmc_gpu_comm_init) so that run() issues
@@ -933,6 +985,33 @@ class ShardedWalk:
             self.g.scale_projector(r)
         self.w_abs, self.last_local = out[1], local
         return out
+
+    def spawn_diagnostics(self):
+        """GpuChem.spawn_diagnostics over all ranks (collective): counts and the NaN count summed, max ratios reduced by max, the min
+        ratio by min; bins_hf is the sum of every rank's slot 0 (the reference prints rank 0's local histograms)"""
+        import torch
+        import torch.distributed as dist
+        d = self.g.spawn_diagnostics()
+        if _backend() is None or dist.get_world_size() == 1:
+            return d
+        on_dev = _backend() == "nccl"
+        def red(a, op):
+            t = torch.from_numpy(np.ascontiguousarray(a).copy())
+            if on_dev:
+                t = t.to(self.dev)
+            dist.all_reduce(t, op=op)
+            return t.cpu().numpy()
+        keys = ("bins", "bins_hf", "bins_single", "bins_double")
+        cnt = red(np.concatenate([d[k] for k in keys] + [np.array([d["n_nan"]], np.int64)]), dist.ReduceOp.SUM)
+        nb = d["nbins"]
+        for i, k in enumerate(keys):
+            d[k] = cnt[i * nb:(i + 1) * nb].copy()
+        d["n_nan"] = int(cnt[-1])
+        d["max_ratio_by_level"] = red(d["max_ratio_by_level"], dist.ReduceOp.MAX)
+        d["min_ratio"] = float(red(np.array([d["min_ratio"]]), dist.ReduceOp.MIN)[0])
+        d["max_ratio"] = float(d["max_ratio_by_level"].max())
+        d["max_ratio_level"] = int(np.argmax(d["max_ratio_by_level"])) if d["max_ratio"] > -1e99 else -1      # argmax: the lowest level that attains it
+        return d
 
     def close(self):
         self.g.close()

@@ -241,6 +241,8 @@ def main(argv=None):
                     "(sqmc_gpu_hci_pt2_stochastic_sample) instead of numpy on the raw connection list")
     ap.add_argument("--pt-diag-update", type=int, choices=(0, 1, 2), default=0, help="HCI decks: H_aa of the PT stage from scratch (0, default), by the O(N) update "
                     "of get_new_diag_elem on one lane (1) or by 16-lane groups (2); with n_mc > 0 it needs --pt-on-device")
+    ap.add_argument("--spawn-histograms", action="store_true", help="walk decks: keep and print the reference's histograms of abs(weight_j)/tau = |H_ij|/p "
+                    "(off_diag_histograms, do_walk.f90:3295-3311) and, at ipr >= 1, its max / min weight-ratio line; steps run un-pipelined")
     a = ap.parse_args(argv)
     text = open(a.input).read() if a.input else sys.stdin.read()
     lines = [l for l in text.splitlines() if l.strip() and not l.lstrip().startswith("!")]
@@ -248,7 +250,7 @@ def main(argv=None):
     if run_type in ("none", "no_fixed_node"):          # a projector walk: the grammar of read_input for run_type /= hci
         from .walk_run import parse_walk_deck, run_walk
         return run_walk(parse_walk_deck(text), a.fcidump, walkalize=a.walkalize, psit_con_in=a.psit_con_in, psit_con_out=a.psit_con_out,
-                        dtm_elems_in=a.dtm_elems_in, dtm_elems_out=a.dtm_elems_out)
+                        dtm_elems_in=a.dtm_elems_in, dtm_elems_out=a.dtm_elems_out, spawn_histograms=a.spawn_histograms)
     deck = parse_hci_deck(text)
     return run_hci(deck, a.fcidump, pt_on_device=a.pt_on_device, pt_diag_update=a.pt_diag_update)
 

@@ -202,7 +202,7 @@ def _nint(x):
 
 
 def run_walk(deck, fcidump="FCIDUMP", out=sys.stdout, walkalize=None, max_equil_sets=50, psit_con_in=None, psit_con_out=None,
-             dtm_elems_in=None, dtm_elems_out=None):
+             dtm_elems_in=None, dtm_elems_out=None, spawn_histograms=False):
     import torch            # noqa: F401  one libamdhip64 per process
     import sqmc_amd
     from . import host as H
@@ -250,6 +250,7 @@ def run_walk(deck, fcidump="FCIDUMP", out=sys.stdout, walkalize=None, max_equil_
     t0 = time.perf_counter()
     # the trial wave function is rediagonalised among its own determinants, as generate_space_iterate leaves it (semistoch.f90:575, 706-712)
     s = hst.setup_walk(g, rediagonalize=True, **skw) if d["hamiltonian_type"] not in ("hubbard2", "hubbardk") else hst.setup_walk(g, **skw)
+    spectral_range = skw["tau_multiplier"] / s.tau             # diagonal_ham_highest - diagonal_ham_lowest (do_walk.f90:1396-1412)
     if d["tau"] != 0:                                         # an explicit tau overrides tau_multiplier (do_walk.f90:1396-1412)
         s.prj_values = s.prj_values * (d["tau"] / s.tau); s.tau = d["tau"]
     n_core = d.get("n_core_orb", 0)
@@ -306,6 +307,8 @@ def run_walk(deck, fcidump="FCIDUMP", out=sys.stdout, walkalize=None, max_equil_
         keep = ~((wk["wt"] == 0) & (wk["initiator"] < 3))
         wk = {k: v[keep] for k, v in wk.items()}
     g.upload_walkers(wk)
+    if spawn_histograms:              # off_diag_histograms (do_walk.f90:104): on from the first step and never reset, equilibration included
+        g.set_spawn_diagnostics(True)
     e_trial = d["e_trial_initial"] if d["e_trial_initial"] != 0 else s.e_trial0
     pc = H.PopControl(s.tau, e_trial, target, r_initiator=d["r_initiator"], initiator_rescale_power=d["initiator_rescale_power"],
                       pop_exp=d["population_control_exponent"], rfi_max_multiplier=d["rfi_max_multiplier"], n_equil_steps=10 ** 18)
@@ -386,6 +389,14 @@ def run_walk(deck, fcidump="FCIDUMP", out=sys.stdout, walkalize=None, max_equil_
     p("Energy=%14.8f(%8d)%14.8f(%8d)%14.8f(%8d) energy_exact=%10.5f t_corr_nonint, t_corr, nstep=%8.2f%8.2f%6d"
       % (st.e_genabs_av, _nint(1e8 * st.e_genabs_err), st.e_blkabs_ave, _nint(1e8 * st.e_blkabs_err), st.e_blkabs_ave, _nint(1e8 * st.e_blkabs_corrected_err),
          0.0, st.t_corr_nonint, st.t_corr, nstep))
+    diag = None
+    if spawn_histograms:              # do_walk.f90:3295-3320
+        diag = g.spawn_diagnostics()
+        if diag["n_nan"]:
+            g.close()
+            raise SystemExit("ibin.le.0 means x is NaN, but that should never happen")          # add_to_hist's stop, more_tools.f90:5489-5492
+        out.write(H.format_spawn_histograms(diag, chem=d["hamiltonian_type"] == "chem", spectral_range=spectral_range if d["ipr"] >= 1 else None))
+        out.flush()
     p("\nsqmc_amd: set-up %.2f s; %d steps in %.3f s inside libsqmc_gpu: %.3e walker-steps/s" % (t0 and (time.perf_counter() - t0 - t_steps), int(nstep * (iblkk - 1)), t_steps, n_walker_steps / t_steps))
     if wfile:
         wfile.write("%6d%6d%9d%12.6f%10.6f nstep, nblk, w_abs_gen_target, e_trial, tau\n" % (nstep, nblk, int(target), pc.e_trial, s.tau))
@@ -393,4 +404,4 @@ def run_walk(deck, fcidump="FCIDUMP", out=sys.stdout, walkalize=None, max_equil_
     g.close()
     return dict(energy=st.e_blkabs_ave, energy_err=st.e_blkabs_err, energy_gen=st.e_genabs_av, energy_gen_err=st.e_genabs_err, n_blocks_total=iblkk - 1,
                 n_equil_sets=ntimes, e_trial=pc.e_trial, nwalk_av=st.nwalk_cum / passes, tau=s.tau, n_imp=len(s.imp_up), n_ct=len(s.ct_up),
-                walker_steps_per_s=n_walker_steps / t_steps)
+                walker_steps_per_s=n_walker_steps / t_steps, **({"spawn_diagnostics": diag} if diag is not None else {}))
