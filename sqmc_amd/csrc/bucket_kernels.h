@@ -85,7 +85,7 @@ __device__ __forceinline__ u64 bk_block_excl_scan(u64 v, u64 *total) {
   *total = tot;
   return off + inc - v;
 }
-// Look-back over the buckets with the whole block: every thread polls its own predecessors (two at most: B <= BK_MAXB), so the
+// Look-back over the buckets with the whole block: every thread polls its own predecessors (NQ = ceil(BK_MAXB / BK_AT) at most), so the
 // running value of all earlier buckets arrives in ONE round trip once they have published, instead of 64 predecessors per
 // poll.  Same words and protocol as lookback_exclusive (status in the top two bits: 1 = this bucket's own total, 2 = running total
 // up to and including it).  All BK_AT threads call it; returns the exclusive running value in every thread.
@@ -94,10 +94,11 @@ __device__ __forceinline__ u64 bk_lookback_wide(u64 *__restrict__ state, int b, 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   if (b == 0) { if (tid == 0) atomicExch((unsigned long long *)&state[0], SCAN_ST_INC | tot); return 0; }
   if (tid == 0) atomicExch((unsigned long long *)&state[b], SCAN_ST_AGG | tot);
-  u64 w_[BK_MAXB / BK_AT]; int ix_[BK_MAXB / BK_AT];
+  constexpr int NQ = (BK_MAXB + BK_AT - 1) / BK_AT;       // predecessors per thread
+  u64 w_[NQ]; int ix_[NQ];
   int pstar = -1;
 #pragma unroll
-  for (int q = 0; q < BK_MAXB / BK_AT; q++) {
+  for (int q = 0; q < NQ; q++) {
     const int idx = b - 1 - tid - q * BK_AT; ix_[q] = idx; w_[q] = 0;
     if (idx >= 0) {
       u64 w;
@@ -114,7 +115,7 @@ __device__ __forceinline__ u64 bk_lookback_wide(u64 *__restrict__ state, int b, 
   for (int v = 0; v < BK_AT / 64; v++) pstar = s_pstar[v] > pstar ? s_pstar[v] : pstar;
   u64 sum = 0;
 #pragma unroll
-  for (int q = 0; q < BK_MAXB / BK_AT; q++) if (ix_[q] >= 0 && ix_[q] >= pstar) sum += w_[q] & SCAN_VAL_MASK;
+  for (int q = 0; q < NQ; q++) if (ix_[q] >= 0 && ix_[q] >= pstar) sum += w_[q] & SCAN_VAL_MASK;
   for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
   if (lane == 0) s_part[wv] = sum;
   __syncthreads();
@@ -147,6 +148,8 @@ __device__ __forceinline__ double bk_wave_sum_lane63(double v) {
 #define BK_PER_S ((BK_CAP_S + BK_AT - 1) / BK_AT)
 #define BK_PER_R ((BK_CAP_R + BK_AT - 1) / BK_AT)
 #define BK_PER_T ((BK_CAP_T + BK_AT - 1) / BK_AT)
+#define BK_DIG ((1024 + BK_AT - 1) / BK_AT)              // digits of the sort's 1024 counters one thread scans
+static_assert(BK_AT % 64 == 0 && BK_AT >= 64 && BK_AT <= 1024, "k_anneal_bucket: whole wavefronts, one block");
 
 __global__ void __launch_bounds__(BK_AT, BK_PER_CU * (BK_AT / 64) / 4) k_anneal_bucket(WalkArr w, WalkArr o, const u64 *__restrict__ rkeys, int *__restrict__ loc_imp,
                                                          const u64 *__restrict__ hkey, const u32 *__restrict__ hidx, u64 hmask,
@@ -171,15 +174,23 @@ __global__ void __launch_bounds__(BK_AT, BK_PER_CU * (BK_AT / 64) / 4) k_anneal_
   __shared__ u32 s_tile; __shared__ u32 s_kmin, s_kmax;
   __shared__ double s_red[BK_AT / 64][NSTAT + 2];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  // Learnt boundaries: which bucket this block takes is known only when its ticket comes back, but the B + 1 boundary positions and
+  // keys are few -- every thread requests one of each while the ticket is in flight and parks it in LDS, so the block's own two
+  // arrive in the ticket's round trip and not in one of their own behind it.  (The ticket stays: dispatch order is no contract.)
+  __shared__ u32 s_bpos[BK_REBAL_MAXB + 1], s_bkb[BK_REBAL_MAXB + 1];
+  const int B = ba.B, nsb = ba.nsb;
+  const bool pre = ba.kb != nullptr && B <= BK_REBAL_MAXB;
   if (tid == 0) { s_tile = atomicAdd(ba.ticket, 1u); s_hqn = 0; }
+  if (pre) for (int j = tid; j <= B; j += BK_AT) { s_bpos[j] = ba.pos[j]; s_bkb[j] = ba.kb[j]; }
   __syncthreads();
-  const int b = (int)s_tile, B = ba.B, nsb = ba.nsb;
-  const long long r_lo = bk_bound(ba, b, n0), r_hi = bk_bound(ba, b + 1, n0);
+  const int b = (int)s_tile;
+  const long long r_lo = pre ? (b <= 0 ? 0ll : (b >= B ? n0 : (long long)s_bpos[b])) : bk_bound(ba, b, n0);
+  const long long r_hi = pre ? (b + 1 >= B ? n0 : (long long)s_bpos[b + 1]) : bk_bound(ba, b + 1, n0);
   const int R = (int)(r_hi - r_lo);
   BPROF(0);
   // key range of the bucket (the sort only looks at the bits that vary inside it)
-  if (tid == 0) s_kmin = b ? (ba.kb ? ba.kb[b] : (u32)(rkeys[r_lo] >> 32)) : 0u;
-  if (tid == 64) s_kmax = (b + 1 < B) ? (ba.kb ? ba.kb[b + 1] : (u32)(rkeys[r_hi] >> 32)) - 1u : (u32)invalid_key;
+  if (tid == 0) s_kmin = b ? (pre ? s_bkb[b] : (ba.kb ? ba.kb[b] : (u32)(rkeys[r_lo] >> 32))) : 0u;
+  if (tid == 64) s_kmax = (b + 1 < B) ? (pre ? s_bkb[b + 1] : (ba.kb ? ba.kb[b + 1] : (u32)(rkeys[r_hi] >> 32))) - 1u : (u32)invalid_key;
   unsigned short *seg_lo = (unsigned short *)scratch; u32 *seg_base = scratch + (BK_CAP_ROWS / 2 + 4);     // u16 x ROWS, then u32 x (ROWS + 1)
   // (key boundaries: the first and the last walker of the whole list get special treatment below and are looked for in the first
   //  and the last bucket -- which equal-residents boundaries never leave empty; here an empty one sends the step to the radix tail)
@@ -288,16 +299,16 @@ __global__ void __launch_bounds__(BK_AT, BK_PER_CU * (BK_AT / 64) / 4) k_anneal_
       }
     }
     __syncthreads();
-    {
-      u32 t2[2]; u64 sum = 0;
+    {   // (BK_DIG consecutive digits per thread: the first 1024 / BK_DIG threads cover the 1024 counters of a wave, the others hold nothing)
+      u32 t2[BK_DIG]; u64 sum = 0;
 #pragma unroll
-      for (int q = 0; q < 2; q++) { const int d = tid * 2 + q; u32 s2 = 0; for (int v = 0; v < BK_AT / 64; v++) s2 += wcnt[v][d]; t2[q] = s2; sum += s2; }
+      for (int q = 0; q < BK_DIG; q++) { const int d = tid * BK_DIG + q; u32 s2 = 0; if (d < 1024) for (int v = 0; v < BK_AT / 64; v++) s2 += wcnt[v][d]; t2[q] = s2; sum += s2; }
       u64 tt; u32 ex = (u32)bk_block_excl_scan(sum, &tt);
 #pragma unroll
-      for (int q = 0; q < 2; q++) {
-        const int d = tid * 2 + q; u32 a2 = ex;
+      for (int q = 0; q < BK_DIG; q++) {
+        const int d = tid * BK_DIG + q; u32 a2 = ex;
         if (d <= R) gst[d] = (unsigned short)ex;
-        for (int v = 0; v < BK_AT / 64; v++) { const u32 cn = wcnt[v][d]; wcnt[v][d] = (bk_cnt_t)a2; a2 += cn; }
+        if (d < 1024) for (int v = 0; v < BK_AT / 64; v++) { const u32 cn = wcnt[v][d]; wcnt[v][d] = (bk_cnt_t)a2; a2 += cn; }
         ex += t2[q];
       }
       if (tid == 0) gst[R + 1] = (unsigned short)S;
@@ -345,13 +356,13 @@ __global__ void __launch_bounds__(BK_AT, BK_PER_CU * (BK_AT / 64) / 4) k_anneal_
         if (valid) rnk[idx] = (unsigned short)(prev + rank);
       }
       __syncthreads();
-      {   // digit bases: exclusive scan over the digits of the waves' counts (two digits per thread)
-        u32 t2[2]; u64 sum = 0;
+      {   // digit bases: exclusive scan over the digits of the waves' counts (BK_DIG digits per thread)
+        u32 t2[BK_DIG]; u64 sum = 0;
 #pragma unroll
-        for (int q = 0; q < 2; q++) { const int d = tid * 2 + q; u32 s2 = 0; for (int v = 0; v < BK_AT / 64; v++) s2 += wcnt[v][d]; t2[q] = s2; sum += s2; }
+        for (int q = 0; q < BK_DIG; q++) { const int d = tid * BK_DIG + q; u32 s2 = 0; if (d < 1024) for (int v = 0; v < BK_AT / 64; v++) s2 += wcnt[v][d]; t2[q] = s2; sum += s2; }
         u64 tt; u32 ex = (u32)bk_block_excl_scan(sum, &tt);
 #pragma unroll
-        for (int q = 0; q < 2; q++) { const int d = tid * 2 + q; u32 a = ex; for (int v = 0; v < BK_AT / 64; v++) { const u32 cn = wcnt[v][d]; wcnt[v][d] = (bk_cnt_t)a; a += cn; } ex += t2[q]; }
+        for (int q = 0; q < BK_DIG; q++) { const int d = tid * BK_DIG + q; u32 a = ex; if (d < 1024) for (int v = 0; v < BK_AT / 64; v++) { const u32 cn = wcnt[v][d]; wcnt[v][d] = (bk_cnt_t)a; a += cn; } ex += t2[q]; }
       }
       __syncthreads();
       for (int idx = tid; idx < S; idx += BK_AT) {
@@ -587,10 +598,12 @@ __global__ void __launch_bounds__(BK_AT, BK_PER_CU * (BK_AT / 64) / 4) k_anneal_
     }
   }
   __syncthreads();
-  // ---- rank of every kept walker inside the bucket (lo 16 bits: position, hi: index among the deterministic-space walkers):
-  //      each thread scans a contiguous share of the merged order; then one look-back over the buckets
+  // ---- rank of every kept walker inside the bucket: each thread scans a contiguous share of the merged order and leaves, AT the
+  //      walker's position in the bucket's output, its merged slot (lo 12 bits) and its index among the deterministic-space walkers
+  //      of the bucket (hi) -- the compaction below runs over output positions, not over merged slots; then one look-back over the buckets
   BPROF(6);
   u32 *s_rank = (u32 *)sb;                              // the idle sort buffer
+  int kept;                                             // walkers this bucket keeps
   // packed running value of the look-back: position (20 bits), index among the deterministic-space walkers (18), children (24)
   u64 ex_glob;
   {
@@ -602,13 +615,14 @@ __global__ void __launch_bounds__(BK_AT, BK_PER_CU * (BK_AT / 64) / 4) k_anneal_
     for (int q = beg; q < end; q++) {
       const unsigned short k = rnk[q];
       if (k & 1) {
-        s_rank[q] = (u32)(ex & 0xFFFull) | ((u32)((ex >> 20) & 0x3FFFFull) << 12);       // inside the bucket: position < 4096, deterministic index < 2^18
+        s_rank[ex & 0xFFFull] = (u32)q | ((u32)((ex >> 20) & 0x3FFFFull) << 12);        // inside the bucket: position and merged slot < 4096, deterministic index < 2^18
         const u64 add = 1ull | ((u64)(k >> 8) << 20) | (ch ? ((u64)s_nc[q] << 38) : 0ull);
         if (ch) s_nc[q] = (u32)(ex >> 38);
         ex += add;
-      } else s_rank[q] = 0xFFFFFFFFu;
+      }
     }
-    __syncthreads();                                 // ranks and child prefixes are read row-wise below
+    kept = (int)(tot & 0xFFFFFull);
+    __syncthreads();                                 // merged slots and child prefixes are read by output position below
     // the determinants this step creates get their H_ii at the end of this kernel (no kernel of its own on a side stream, nothing to
     // join): the tables travel to the idle counters while the look-back waits for its predecessors
     stage_tab(s_tab, dev.tab, dev.tab_words);
@@ -622,20 +636,24 @@ __global__ void __launch_bounds__(BK_AT, BK_PER_CU * (BK_AT / 64) / 4) k_anneal_
   }
   BPROF(7);
   // ---- compaction into the other buffer, reweighting (2487), estimator pieces (2573-2684, more_tools.f90:4041-4098), next gate.
-  //      Two slots per thread and round: their loads (record, then C(T) probe) are in flight together.
+  //      The loop runs over the bucket's OUTPUT positions (the rank scan left every kept walker's merged slot at its position): every
+  //      lane carries a walker, consecutive lanes store to consecutive places, and a bucket of the bench size (1130 merged slots of
+  //      which 550 are kept) is through in one round where the loop over merged slots took two.  Two walkers per thread and round:
+  //      their loads (record, then C(T) probe) are in flight together.  The walker -> thread assignment is fixed (position mod BK_AT),
+  //      so the estimator sums are the same bits run to run.
   double st[NSTAT];
 #pragma unroll
   for (int k = 0; k < NSTAT; k++) st[k] = 0.0;
   constexpr int CB = 2;
-  for (int q0b = tid; q0b < T; q0b += CB * BK_AT) {
+  for (int k0b = tid; k0b < kept; k0b += CB * BK_AT) {
     int si_[CB]; u32 r_[CB]; u64 up_[CB], dn_[CB], key_[CB]; double me_[CB], en_[CB], ed_[CB]; long long hh_[CB];
 #pragma unroll
     for (int z = 0; z < CB; z++) {
-      const int q = q0b + z * BK_AT;
-      r_[z] = (q < T) ? s_rank[q] : 0xFFFFFFFFu;
+      const int kpos = k0b + z * BK_AT;
+      r_[z] = (kpos < kept) ? s_rank[kpos] : 0xFFFFFFFFu;              // (a real entry is below 2^30)
       si_[z] = 0; up_[z] = 0; dn_[z] = 0; key_[z] = 0; me_[z] = 1e51; en_[z] = 1e51; ed_[z] = 1e51; hh_[z] = -2;
       if (r_[z] != 0xFFFFFFFFu) {
-        const int si = (int)(m2s[q] & ~BK_STOP); si_[z] = si;
+        const int si = (int)(m2s[r_[z] & 0xFFFu] & ~BK_STOP); si_[z] = si;
         if (si < R) { const long long ix = r_lo + si; up_[z] = w.up[ix]; dn_[z] = w.dn[ix]; me_[z] = w.me[ix]; en_[z] = w.en[ix]; ed_[z] = w.ed[ix]; key_[z] = rk[si]; }
         else { const u64 x = sa[si - R]; const SpawnRec *rp = w.sp + ((long long)(u32)x - n0); up_[z] = rp->up; dn_[z] = rp->dn; key_[z] = x >> 32; }
       }
@@ -648,7 +666,8 @@ __global__ void __launch_bounds__(BK_AT, BK_PER_CU * (BK_AT / 64) / 4) k_anneal_
     for (int z = 0; z < CB; z++) {
       if (r_[z] == 0xFFFFFFFFu) continue;
       const int si = si_[z];
-      const long long q0 = (long long)(ex_glob & 0xFFFFFull) + (long long)(r_[z] & 0xFFFu);
+      const int kpos = k0b + z * BK_AT;                              // position inside the bucket's output
+      const long long q0 = (long long)(ex_glob & 0xFFFFFull) + (long long)kpos;
       const long long qd = (long long)((ex_glob >> 20) & 0x3FFFFull) + (long long)(r_[z] >> 12);
       const double wt = s_w[si] * p.rfi;
       const u32 fl = s_f[si];
@@ -657,15 +676,15 @@ __global__ void __launch_bounds__(BK_AT, BK_PER_CU * (BK_AT / 64) / 4) k_anneal_
       o.up[q0] = up_[z]; o.dn[q0] = dn_[z]; o.wt[q0] = wt; o.flg[q0] = fl;
       o.me[q0] = me_[z]; o.en[q0] = en; o.ed[q0] = ed;
       if (me_[z] > 1e50 && !(p.semi && d < 1)) {                   // k_diag's rule (walk_kernels.h): death/clone will want H_ii
-        const int slot = atomicAdd(&s_hqn, 1);
-        s_hq[slot] = (unsigned short)(r_[z] & 0xFFFu);
+        const int slot = atomicAdd(&s_hqn, 1);                     // the queue's order is whatever the atomics make it: every consumer (the deferred
+        s_hq[slot] = (unsigned short)kpos;                         // positions of BK_HQ_DEFER, the in-tail passes) reads a position from an entry, none an order
         if (slot < BK_HQ_DETS) { s_hdet[2 * slot] = up_[z]; s_hdet[2 * slot + 1] = dn_[z]; }
       }
       if (go.on) {
         u64 nc; double wc;
         gate_children(wt, go.cutoff, seed, go.step_next, key_[z], nc, wc);
         go.keys[q0] = (key_[z] << 32) | (u64)q0; go.wchild[q0] = wc;
-        if (go.child_off) { const u64 off = (ex_glob >> 38) + (u64)s_nc[q0b + z * BK_AT]; go.child_off[q0] = off; gate_block_parents(go.bpar, off, nc, q0); } else go.nchild[q0] = nc;
+        if (go.child_off) { const u64 off = (ex_glob >> 38) + (u64)s_nc[r_[z] & 0xFFFu]; go.child_off[q0] = off; gate_block_parents(go.bpar, off, nc, q0); } else go.nchild[q0] = nc;
       }
       if (d == 0 && p.semi && qd < p.nimp_cap) { loc_imp[qd] = (int)q0; o.irk[q0] = (u32)qd; if (fs.x_out) fs.x_out[qd] = wt; }
       st[0] += wt; st[1] += fabs(wt); st[8] += wt * wt;
@@ -699,9 +718,10 @@ __global__ void __launch_bounds__(BK_AT, BK_PER_CU * (BK_AT / 64) / 4) k_anneal_
 #define BK_HII_PASSES(HG)                                                                                          \
     {                                                                                                              \
       const int G = tid / HG, g = tid % HG;                                                                        \
-      double *sg = s_w + G * BK_HG_TERMS(HG);            /* the weights were last read by the compaction */        \
-      for (int k0 = n_def; k0 < nq; k0 += BK_AT / HG) {                                                            \
-        const int k = k0 + G; const bool valid = k < nq;                                                           \
+      const bool room = G < BK_HG_GROUPS(HG);            /* threads beyond what the weight array holds sit the passes out (they meet the barriers) */ \
+      double *sg = s_w + (room ? G : 0) * BK_HG_TERMS(HG);      /* the weights were last read by the compaction */ \
+      for (int k0 = n_def; k0 < nq; k0 += BK_HG_GROUPS(HG)) {                                                      \
+        const int k = k0 + G; const bool valid = room && k < nq;                                                   \
         const long long q0 = valid ? base + (long long)s_hq[k] : 0;                                                \
         u64 u = 0, dd = 0;                                                                                         \
         if (valid) { if (k < BK_HQ_DETS) { u = s_hdet[2 * k]; dd = s_hdet[2 * k + 1]; } else { u = o.up[q0]; dd = o.dn[q0]; } }   \
@@ -712,8 +732,8 @@ __global__ void __launch_bounds__(BK_AT, BK_PER_CU * (BK_AT / 64) / 4) k_anneal_
     // few determinants (a bucket creates 13 on average at the bench size, 28 at most): more lanes each -- the phase is the latency
     // of one lane's decode + fetch + sum chain, and a lane with 2 tasks is through sooner than one with 5
     if (nq == n_def) { }
-    else if ((hg == 8 || hg == 16) && nq - n_def <= BK_AT / 32 && bk_hii_terms(*s_tab) <= BK_HG_TERMS(32)) BK_HII_PASSES(32)
-    else if (hg == 8 && nq - n_def <= BK_AT / 16) BK_HII_PASSES(16)
+    else if ((hg == 8 || hg == 16) && nq - n_def <= BK_HG_GROUPS(32) && bk_hii_terms(*s_tab) <= BK_HG_TERMS(32)) BK_HII_PASSES(32)
+    else if (hg == 8 && nq - n_def <= BK_HG_GROUPS(16)) BK_HII_PASSES(16)
     else if (hg == 8) BK_HII_PASSES(8)
     else if (hg == 16) BK_HII_PASSES(16)
     else {
@@ -735,8 +755,16 @@ __global__ void __launch_bounds__(BK_AT, BK_PER_CU * (BK_AT / 64) / 4) k_anneal_
   }
   __syncthreads();
   if (tid < NSTAT + 2) {
-    double v = 0.0;
-    for (int q = 0; q < BK_AT / 64; q++) v += s_red[q][tid];
+    // the waves' sums by a fixed pairwise tree (0+1, 2+3, ...; then pairs of pairs): the same bits run to run, a chain of
+    // log2(waves) additions instead of one per wave
+    double a_[BK_AT / 64];
+#pragma unroll
+    for (int q = 0; q < BK_AT / 64; q++) a_[q] = s_red[q][tid];
+#pragma unroll
+    for (int s = 1; s < BK_AT / 64; s <<= 1)
+#pragma unroll
+      for (int q = 0; q + s < BK_AT / 64; q += 2 * s) a_[q] += a_[q + s];
+    const double v = a_[0];
     if (tid < NSTAT) partials[(long long)b * NSTAT + tid] = v;
     else wabs_part[2 * b + (tid - NSTAT)] = v;
   }

@@ -26,7 +26,7 @@ typedef unsigned short bk_cnt_t;      // digit counters of the in-LDS sort (a bu
 #define BK_CAP_T 3584
 #define BK_TARGET 1150                // one block per CU
 #define BK_PER_CU 1
-typedef u32 bk_cnt_t;
+typedef unsigned short bk_cnt_t;      // (BK_CAP_S <= 65535: the static_assert beside the counters)
 #endif
 #define BK_RESIDENTS_MAX (BK_HALF ? BK_CAP_R * 80 / 100 : 1000)     // boundaries that would put more residents into a bucket are not used
 #define BK_HQ_DEFER 64                // deferred H_ii positions per bucket (13 on average at the bench size; the rest is done in the tail)

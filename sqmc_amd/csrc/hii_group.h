@@ -1,13 +1,23 @@
 // hii_group.h -- the diagonal element of one determinant by a group of lanes, terms in the reference's order (hamiltonian_chem's
 // diagonal branch, chemistry.f90:8605-8700 region as restated in h_diag, chem_device.h).  Textually included by sqmc_gpu.hip.
 #pragma once
-#define BK_AT 512                      // threads of k_anneal_bucket: one block per CU, so the block itself has to keep the memory pipes busy
+#ifndef BK_AT                          // (any multiple of 64 up to 1024 works: -DBK_AT=... builds the others for a measurement)
+#if !BK_HALF
+#define BK_AT 768                      // threads of k_anneal_bucket: one block per CU, so the block itself has to keep the memory pipes busy.  A bucket of
+#else                                  // the bench size (550 residents, 580 spawns, 550 kept) is one round of every strided phase at 768, two at 512: measured, DESIGN 4a
+#define BK_AT 512                      // half-size buckets, two blocks per CU: as they were measured (at 768 the two blocks would be held to 80 registers)
+#endif
+#endif
 // ---- H_ii of one determinant by 16 lanes (chemistry, no time symmetry).  h_diag (chem_device.h) is three running sums -- one-body,
 // exchange, direct -- of ~50 integrals; a lane on its own pays one L2 round trip per group of four.  Here every term of a sum has its
 // place in the reference's order (closed form from the electron indices), the 16 lanes fetch all terms at once into LDS, and one
 // lane per sum adds them up in that order: the same value bit for bit, one round trip instead of ~25.
 // HG lanes per determinant: 8 (64 determinants per pass) when its terms fit 56 doubles -- up to 4 + 4 electrons --, else 16
-#define BK_HG_TERMS(HG) (BK_CAP_T / (BK_AT / (HG)))            // LDS doubles per group: the groups share the weight array (112 at HG = 16)
+// A group's room does not follow the block size of k_anneal_bucket: k_diag and k_spawn's spare blocks size their own arrays by it, and
+// which systems take the group form (5 + 5 electrons: 75 terms, 6 + 6: 108) must not depend on BK_AT.  In the bucket tail the groups
+// share the weight array, which holds BK_HG_GROUPS(HG) of them: no more groups work in one pass, however many threads the block has.
+#define BK_HG_TERMS(HG) (BK_CAP_T / (512 / (HG)))               // LDS doubles per group (56 at HG = 8, 112 at HG = 16, 224 at HG = 32)
+#define BK_HG_GROUPS(HG) ((BK_AT < 512 ? BK_AT : 512) / (HG))   // groups of one pass of the bucket tail: BK_HG_GROUPS x BK_HG_TERMS <= BK_CAP_T doubles
 #define BK_HG_TASKS 6                                           // tasks per lane at the cap of HG = 16; 12 at HG = 8
 __device__ __forceinline__ int bk_nth_orb(u64 x, int n) { for (int k = 0; k < n; k++) x &= x - 1; return ctz64(x); }     // 0-based orbital of the n-th electron
 __host__ __device__ __forceinline__ int bk_hii_terms_of(int nup, int ndn) { return (nup + ndn) + (nup * (nup - 1) + ndn * (ndn - 1)) + nup * ndn; }      // doubles a group needs for one determinant

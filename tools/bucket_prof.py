@@ -10,7 +10,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ["SQMC_EXTRA_CFLAGS"] = "-DBUCKET_PROF"
+os.environ["SQMC_EXTRA_CFLAGS"] = ("-DBUCKET_PROF " + os.environ.get("SQMC_BUCKET_PROF_CFLAGS", "")).strip()      # e.g. SQMC_BUCKET_PROF_CFLAGS=-DBK_AT=512
 import torch  # noqa: F401
 import sqmc_amd
 sqmc_amd.build_library()
@@ -52,6 +52,18 @@ print("latest to publish: " + ", ".join("%.1f us after its start (S %d R %d)" % 
 print("H_ii phase: wait for the block's last compaction thread mean %.2f max %.2f us; the passes mean %.2f max %.2f us; determinants per bucket mean %.0f max %d" % (
     ((a[:, 14] - a[:, 8]) / 100.0).mean(), ((a[:, 14] - a[:, 8]) / 100.0).max(), ((a[:, 11] - a[:, 14]) / 100.0).mean(), ((a[:, 11] - a[:, 14]) / 100.0).max(), a[:, 15].mean(), a[:, 15].max()))
 print("S: mean %.0f max %d; R mean %.0f min %d max %d; T max %d" % (a[:, 12].mean(), a[:, 12].max(), a[:, 13].mean(), a[:, 13].min(), a[:, 13].max(), (a[:, 12] + a[:, 13]).max()))
+# how the buckets' contents sit against the strides they are processed with: a phase that strides by BK_AT threads (the compaction:
+# by CB = 2 x BK_AT slots) runs one more round for every stride its content crosses
+import re
+A = int(re.search(r"#define BK_AT (\d+)", open(os.path.join(ROOT, "sqmc_amd", "csrc", "hii_group.h")).read()).group(1))
+if re.search(r"-DBK_AT=(\d+)", os.environ["SQMC_EXTRA_CFLAGS"]):          # the library this run was built with (SQMC_BUCKET_PROF_CFLAGS) has another block size
+    A = int(re.search(r"-DBK_AT=(\d+)", os.environ["SQMC_EXTRA_CFLAGS"]).group(1))
+Rv, Sv = a[:, 13], a[:, 12]
+for nm, v in (("R", Rv), ("S", Sv), ("T", Rv + Sv)):
+    print("%s over the buckets: min %d  p10 %d  p25 %d  median %d  p75 %d  p90 %d  max %d  mean %.0f" % ((nm, v.min()) + tuple(int(x) for x in np.percentile(v, [10, 25, 50, 75, 90])) + (v.max(), v.mean())))
+nwalk = w.g.num_walkers()
+print("BK_AT %d: buckets with R > BK_AT %.1f %%, S > BK_AT %.1f %%, T > 2 BK_AT %.1f %%, T > 3 BK_AT %.1f %%; kept walkers %d, %.0f per bucket" % (
+    A, 100.0 * (Rv > A).mean(), 100.0 * (Sv > A).mean(), 100.0 * (Rv + Sv > 2 * A).mean(), 100.0 * (Rv + Sv > 3 * A).mean(), nwalk, nwalk / float(nb)))
 ids = np.nonzero(np.array(buf, dtype=np.int64).reshape(1024, 16)[:, 0] != old[:, 0])[0]
 top = np.argsort(-(a[:, 12] + a[:, 13]))[:8]
 print("fullest buckets (id: R + S): " + ", ".join("%d: %d + %d" % (ids[i], a[i, 13], a[i, 12]) for i in top))
