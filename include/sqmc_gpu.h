@@ -107,7 +107,7 @@ typedef struct {
   int64_t mwalk;
 } sqmc_hubbard_cfg;
 int sqmc_gpu_init_hubbard(const sqmc_hubbard_cfg *cfg, sqmc_gpu_ctx **out);
-/* Hubbard model in its plane-wave basis on a periodic l_x by l_y lattice (hamiltonian_type 'hubbardk', space_sym = .false.):
+/* Hubbard model in its plane-wave basis on a periodic l_x by l_y lattice (hamiltonian_type 'hubbardk'; space_sym = .true.: sqmc_gpu_set_hubbardk_space_sym):
  * hubbard.f90:2179-2324 (generate_k_vectors), 2866-2924 (hamiltonian_hubbard_k), 3649-3848 (off_diagonal_move_hubbard_k),
  * 5462 (find_connected_dets_hubbard_k).  The orbital table arrives as data in the reference's orbital order, as
  * sqmc_gpu_init_heg takes its plane waves: k_vectors is the reference's k_vectors(2, nsites) (int32, two per orbital, units of
@@ -131,6 +131,31 @@ typedef struct {
   int64_t mwalk;
 } sqmc_hubbardk_cfg;
 int sqmc_gpu_init_hubbardk(const sqmc_hubbardk_cfg *cfg, sqmc_gpu_ctx **out);
+/* space_sym = .true. for hubbardk (read_hubbard, hubbard.f90:181-208): the walk lives on the representatives of the orbits of the
+ * determinants under C4 x lattice reflection x spin inversion (16 elements), in the sector z (spin inversion), p (reflection), C4-A1.
+ * replaces: generate_fourfold_k_configs_efficient (more_tools.f90:4670-4819: the 16 images with their phases, the representative = the
+ * smallest image by (up, dn), phase_w_rep, norm, num_distinct), hamiltonian_hubbard_k_space_sym (hubbard.f90:2927-2989), the space_sym
+ * branch of off_diagonal_move_hubbard_k (3771-3817: the child is replaced by its representative, proposal_prob_inv / nnzero, weight 0 onto
+ * a determinant of norm 0, onto the parent's own orbit, or with nnzero = 0; the same three random_int draws) and the closing block of
+ * find_connected_dets_hubbard_k (5611-5627).  c4_map is the reference's c4_map(3, nsites) as it lies in memory (three entries per orbital)
+ * and reflection_map its reflection_map(nsites), both 1-based, as create_kspace_sym_maps (more_tools.f90:4209-4310) builds them.
+ * After this call every element (sqmc_gpu_hamiltonian_batch, H_ii of the walk), every move and every connection of the context is the
+ * one between orbit sums; a bra that is not a representative stands for its representative, and an element with a determinant of norm 0
+ * is 0.  The connection generator emits every raw child as (its representative, its term of the symmetrised element times c): the
+ * deduplication sums them; children in the source's own orbit land on the source's slot, which holds the plain diagonal in diag_mode 1
+ * (together: the symmetrised H_ii); the eps screen stays on the raw term |U/nsites c|.
+ * Refused (SQMC_ERR_UNSUPPORTED): a context that is not hubbardk, l_x /= l_y or odd l, nup /= ndn.  SQMC_ERR_BAD_ARG: |z| or |p| /= 1; maps
+ * that are not permutations, do not preserve k_energies or do not compose as C4 and a reflection; a context that already holds walkers, a
+ * projector or a C(T) table.  With space_sym set, sqmc_gpu_upload_walkers and sqmc_gpu_set_ct_table refuse (SQMC_ERR_BAD_ARG) a determinant
+ * that is not its own representative or whose norm is 0 (sqmc_gpu_set_projector takes a matrix without determinants: its rows are the
+ * uploaded walkers with imp_distance 0, which are checked), and sqmc_gpu_hci_pt2, sqmc_gpu_build_sparse_ham and sqmc_gpu_build_spmv_plan
+ * return SQMC_ERR_UNSUPPORTED in addition to what a hubbardk context refuses anyway. */
+int sqmc_gpu_set_hubbardk_space_sym(sqmc_gpu_ctx *ctx, int32_t z, int32_t p, const int32_t *c4_map, const int32_t *reflection_map);
+/* per determinant of a list (any determinants of nup + ndn electrons, representatives or not): images_up / images_dn [16 n] and phases [16 n]
+ * in the reference's order (image k of determinant i at [16 i + k]), the representative, phase_w_rep, norm and num_distinct
+ * (0 when the norm vanishes).  What symmetry_reduce_hubbardk (hubbard.f90:9061) needs to reduce a determinant list. */
+int sqmc_gpu_hubbardk_sym_images(sqmc_gpu_ctx *ctx, int64_t n, const uint64_t *up, const uint64_t *dn, uint64_t *images_up, uint64_t *images_dn,
+                                 int32_t *phases, uint64_t *rep_up, uint64_t *rep_dn, int32_t *phase_w_rep, double *norm, int32_t *num_distinct);
 int sqmc_gpu_finalize(sqmc_gpu_ctx *ctx);
 const char *sqmc_gpu_last_error(void);
 

@@ -22,7 +22,7 @@ RNG_REPLAY, RNG_COUNTER = 0, 1
 _LIB = None
 
 EXPORTS = [
-    "sqmc_gpu_set_device", "sqmc_gpu_init_chem", "sqmc_gpu_init_heg", "sqmc_gpu_init_hubbard", "sqmc_gpu_init_hubbardk", "sqmc_gpu_finalize", "sqmc_gpu_last_error", "sqmc_gpu_set_hb_tables", "sqmc_gpu_set_heatbath_tables", "sqmc_gpu_setup_efficient_heatbath", "sqmc_gpu_get_heatbath_tables", "sqmc_gpu_propose_heatbath_batch", "sqmc_gpu_setup_cauchy_schwarz", "sqmc_gpu_propose_cauchy_schwarz_batch", "sqmc_gpu_set_projector",
+    "sqmc_gpu_set_device", "sqmc_gpu_init_chem", "sqmc_gpu_init_heg", "sqmc_gpu_init_hubbard", "sqmc_gpu_init_hubbardk", "sqmc_gpu_set_hubbardk_space_sym", "sqmc_gpu_hubbardk_sym_images", "sqmc_gpu_finalize", "sqmc_gpu_last_error", "sqmc_gpu_set_hb_tables", "sqmc_gpu_set_heatbath_tables", "sqmc_gpu_setup_efficient_heatbath", "sqmc_gpu_get_heatbath_tables", "sqmc_gpu_propose_heatbath_batch", "sqmc_gpu_setup_cauchy_schwarz", "sqmc_gpu_propose_cauchy_schwarz_batch", "sqmc_gpu_set_projector",
     "sqmc_gpu_scale_projector", "sqmc_gpu_set_ct_table", "sqmc_gpu_set_hf_to_psit", "sqmc_gpu_set_hf_to_psit_shard", "sqmc_gpu_upload_walkers", "sqmc_gpu_num_walkers",
     "sqmc_gpu_download_walkers", "sqmc_gpu_step", "sqmc_gpu_run", "sqmc_gpu_annihilate", "sqmc_gpu_det_owner", "sqmc_gpu_set_owner_hash", "sqmc_gpu_shard_config",
     "sqmc_gpu_shard_begin", "sqmc_gpu_shard_pack", "sqmc_gpu_shard_finish", "sqmc_gpu_shard_finish_psit", "sqmc_gpu_comm_unique_id", "sqmc_gpu_comm_init", "sqmc_gpu_comm_size",
@@ -236,6 +236,28 @@ class GpuChem:
         _chk(L.sqmc_gpu_init_hubbardk(C.byref(cfg), C.byref(h)))
         self.h, self.norb, self.mwalk = h, l_x * l_y, mwalk
         return self
+
+    def set_hubbardk_space_sym(self, z, p, c4_map, reflection_map):
+        """space_sym = .true. on a hubbardk context: c4_map[nsites, 3] (the reference's c4_map(3, nsites) in memory) and reflection_map[nsites],
+        1-based orbital -> 1-based orbital; before walkers, projector and C(T) table"""
+        c4, rf = np.ascontiguousarray(c4_map, np.int32), np.ascontiguousarray(reflection_map, np.int32)
+        if c4.shape != (self.norb, 3) or rf.shape != (self.norb,):
+            raise ValueError("c4_map must be [nsites, 3] and reflection_map [nsites]")
+        self.L.sqmc_gpu_set_hubbardk_space_sym.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+        _chk(self.L.sqmc_gpu_set_hubbardk_space_sym(self.h, int(z), int(p), _p(c4), _p(rf)))
+
+    def hubbardk_sym_images(self, up, dn):
+        """per determinant: dict of images_up / images_dn [n, 16] and phases [n, 16] in the reference's order, rep_up, rep_dn, phase_w_rep,
+        norm and num_distinct (0 where the determinant has no state in the (z, p) sector)"""
+        u, d = _u64(up), _u64(dn)
+        n = len(u)
+        o = dict(images_up=np.zeros((n, 16), np.uint64), images_dn=np.zeros((n, 16), np.uint64), phases=np.zeros((n, 16), np.int32),
+                 rep_up=np.zeros(n, np.uint64), rep_dn=np.zeros(n, np.uint64), phase_w_rep=np.zeros(n, np.int32), norm=np.zeros(n),
+                 num_distinct=np.zeros(n, np.int32))
+        self.L.sqmc_gpu_hubbardk_sym_images.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 10
+        _chk(self.L.sqmc_gpu_hubbardk_sym_images(self.h, n, _p(u), _p(d), *[_p(o[k]) for k in ("images_up", "images_dn", "phases", "rep_up", "rep_dn",
+                                                                                                    "phase_w_rep", "norm", "num_distinct")]))
+        return o
 
     def close(self):
         if self.h:

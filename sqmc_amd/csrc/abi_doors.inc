@@ -128,6 +128,8 @@ static int ham_rows_dev(sqmc_gpu_ctx *c, int64_t n, const uint64_t *up, const ui
 int sqmc_gpu_build_sparse_ham(sqmc_gpu_ctx *c, int64_t n, const uint64_t *up, const uint64_t *dn, int64_t *out_nnz,
                               int64_t **out_row_counts, int64_t **out_indices, double **out_values) {
   if (!c || !out_nnz || !out_row_counts || !out_indices || !out_values || n <= 0) return fail(SQMC_ERR_BAD_ARG, "bad argument");
+  if (c->htab.sys_type == 3 && c->htab.hk_sym)
+    return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_build_sparse_ham is not built for hubbardk with space_sym: the matrix among representatives is assembled from sqmc_gpu_hci_connections in raw mode");
   for (long long i = 1; i < n; i++)
     if (!(up[i - 1] < up[i] || (up[i - 1] == up[i] && dn[i - 1] < dn[i]))) return fail(SQMC_ERR_BAD_ARG, "determinant list must be strictly sorted by (up,dn)");
   hipStream_t st = c->st;
@@ -156,6 +158,7 @@ int sqmc_gpu_build_sparse_ham(sqmc_gpu_ctx *c, int64_t n, const uint64_t *up, co
 // preconditioner) and the number of stored (upper-triangular) nonzeros come back to the host.
 int sqmc_gpu_build_spmv_plan(sqmc_gpu_ctx *c, int64_t n, const uint64_t *up, const uint64_t *dn, sqmc_spmv_plan **plan, double *diag, int64_t *out_nnz) {
   if (!c || !plan || !diag || !out_nnz || n <= 0) return fail(SQMC_ERR_BAD_ARG, "bad argument");
+  if (c->htab.sys_type == 3 && c->htab.hk_sym) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_build_spmv_plan is not built for hubbardk with space_sym (see sqmc_gpu_build_sparse_ham)");
   for (long long i = 1; i < n; i++)
     if (!(up[i - 1] < up[i] || (up[i - 1] == up[i] && dn[i - 1] < dn[i]))) return fail(SQMC_ERR_BAD_ARG, "determinant list must be strictly sorted by (up,dn)");
   hipStream_t st = c->st;
@@ -557,6 +560,7 @@ int sqmc_gpu_hci_connections_record(sqmc_gpu_ctx *c, int64_t n_ref, const uint64
 int sqmc_gpu_hci_pt2(sqmc_gpu_ctx *c, int64_t n_var, const uint64_t *var_up, const uint64_t *var_dn, const double *coeffs, double e_var, double eps_pt,
                      int32_t n_slices, double *delta_e, int64_t *n_connections) {
   if (!c || !delta_e || !n_connections || n_var <= 0 || n_slices < 1) return fail(SQMC_ERR_BAD_ARG, "bad argument");
+  if (c->htab.sys_type == 3 && c->htab.hk_sym) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_hci_pt2 is not built for hubbardk with space_sym");
   hipStream_t st = c->st;
   static const bool timed = getenv("SQMC_PT2_TIME") != nullptr;      // tools/pt2_diag_time.py: HIP events around the term kernel (membership + H_aa + term)
   c->pt2_terms_ms = 0.0;

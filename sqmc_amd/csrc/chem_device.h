@@ -39,6 +39,8 @@ struct ChemTab {
       double hk_energies[SQ_MAXORB + 1];
       double hk_ubyn;
       int hk_lx, hk_ly;
+      int hk_sym, hk_z, hk_p;          // space_sym (hubbard.f90:181-208): walk among the representatives of the orbits under C4 x reflection x spin inversion
+      unsigned char hk_map[4][SQ_MAXORB + 1];   // c4_map(1..3, :) and reflection_map(:) of create_kspace_sym_maps, 1-based orbital -> 1-based orbital
     };
   };
   signed char krel[SQ_MAXORB + 1][3];  // the same in units of 2 pi / L (k_vectors_rel): exact momentum bookkeeping.  hubbardk: the lattice momentum
@@ -400,7 +402,7 @@ __device__ __forceinline__ int hk_orbital(const ChemTab &t, int mx, int my) {   
   if (my < 0) my += ly; else if (my >= ly) my -= ly;
   return (int)reinterpret_cast<const unsigned char *>(t.c2)[mx * ly + my];
 }
-__device__ __noinline__ double h_hubbardk(const ChemTab &t, u64 iu, u64 id, u64 ju, u64 jd) {
+__device__ __forceinline__ double h_hubbardk_body(const ChemTab &t, u64 iu, u64 id, u64 ju, u64 jd) {
   if (iu == ju && id == jd) {
     double me = t.hk_ubyn * t.nup * t.ndn;
     for (u64 d = iu; d; d &= d - 1) me = me + t.hk_energies[ctz64(d) + 1];
@@ -413,11 +415,115 @@ __device__ __noinline__ double h_hubbardk(const ChemTab &t, u64 iu, u64 id, u64 
   if (hk_orbital(t, t.krel[p][0] + t.krel[q][0] - t.krel[r][0], t.krel[p][1] + t.krel[q][1] - t.krel[r][1]) != s) return 0.0;
   return t.hk_ubyn * permutation_factor(iu, ju) * permutation_factor(id, jd);
 }
+__device__ __noinline__ double h_hubbardk(const ChemTab &t, u64 iu, u64 id, u64 ju, u64 jd) { return h_hubbardk_body(t, iu, id, ju, jd); }
+
+// ---- hubbardk with space_sym (hubbard.f90:181-208): a determinant stands for the orbit sum  sum_g chi(g) g|det> / norm  over the 16 elements
+// g = Z^s P^f R^r of C4 x reflection x spin inversion, chi = z^s p^f (the A1 irrep of C4), and the walk lives on the orbits' representatives.
+//   images, phases, norm, representative   generate_fourfold_k_configs_efficient, more_tools.f90:4670-4819
+//   element                                hamiltonian_hubbard_k_space_sym, hubbard.f90:2927-2989
+//   move                                   off_diagonal_move_hubbard_k, hubbard.f90:3771-3817
+// Image k (0-based) = r + 4 s + 8 f is the reference's image k + 1.  The sign of an orbital map on a string is the parity of the inversions of
+// the mapped locations, counted from the bit strings as they are built (relabel_efficient sorts and counts the moves; with nup = ndn, which
+// space_sym requires, the two agree).  norm^2 = the sum of the phases of the images equal to the determinant: the order of its stabiliser,
+// or 0 when one of the stabiliser's phases is -1 -- the determinant then has no state in the (z, p) sector.  With norm > 0 every distinct
+// image occurs norm^2 times among the 16, each time with the same phase, so the reference's sum over the distinct images is the sum over all
+// 16 divided by norm^2, and its count of distinct non-zero terms is the count among the 16 divided by norm^2: no list of images seen is kept.
+// Everything a kernel calls here is an out-of-line LEAF function reached only with hk_sym set, with one copy of the per-image work in a rolled
+// loop: a kernel's registers and scratch are the maximum over what it can call, and a function that calls another saves registers on a stack.
+__device__ __forceinline__ u64 hk_map_string(const unsigned char *map, u64 x, int &inv) {
+  u64 acc = 0;
+#pragma nounroll
+  for (u64 d = x; d; d &= d - 1) { const int n = map[ctz64(d) + 1] - 1; inv += popc64(acc >> n); acc |= bit64(n); }
+  return acc;
+}
+template <class F>
+__device__ __forceinline__ void hk_orbit(const ChemTab &t, u64 u, u64 d, F f) {      // f(k, up, dn, phase) for the 16 images; one rotation at a time: as it is,
+#pragma nounroll                                                                     // spins exchanged, then the same two of its reflection
+  for (int r = 0; r < 4; r++) {
+    int inv = 0; u64 a = u, b = d;
+    if (r) { a = hk_map_string(t.hk_map[r - 1], u, inv); b = hk_map_string(t.hk_map[r - 1], d, inv); }
+    int ph = (inv & 1) ? -1 : 1;
+#pragma nounroll
+    for (int j = 0; j < 4; j++) {
+      if (j == 2) {
+        inv = 0;
+        const u64 a2 = hk_map_string(t.hk_map[3], a, inv), b2 = hk_map_string(t.hk_map[3], b, inv);
+        a = a2; b = b2; ph = ((inv & 1) ? -ph : ph) * t.hk_p;
+      }
+      f(r + 4 * j, (j & 1) ? b : a, (j & 1) ? a : b, (j & 1) ? ph * t.hk_z : ph);
+    }
+  }
+}
+// one pass over the images of s: its representative (the smallest image by (up, dn); among equal ones the first in the reference's order gives
+// phase_w_rep, as its strict comparisons do), norm^2, and -- ELEM --  sum_k phase_k <image_k|H|ket>  with the number of non-zero terms.
+// Inside the loop everything is a small integer (few registers live): an image's element with the ket is the plain diagonal when it IS the ket,
+// else +-U/nsites or nothing, so the loop counts signs and the sum is put together once, behind it.
+struct HkScan { u64 ru, rd; double sum; int phase_w_rep, norm2, nnz; };
+__device__ __forceinline__ int hk_offdiag_sign(const ChemTab &t, u64 iu, u64 id, u64 ju, u64 jd) {      // h_hubbardk_body's off-diagonal branch / ubyn
+  const u64 au = iu & ~ju, bu = ju & ~iu, ad = id & ~jd, bd = jd & ~id;
+  if (popc64(au) != 1 || popc64(bu) != 1 || popc64(ad) != 1 || popc64(bd) != 1) return 0;
+  const int p = ctz64(au) + 1, r = ctz64(bu) + 1, q = ctz64(ad) + 1, s = ctz64(bd) + 1;
+  if (hk_orbital(t, t.krel[p][0] + t.krel[q][0] - t.krel[r][0], t.krel[p][1] + t.krel[q][1] - t.krel[r][1]) != s) return 0;
+  return permutation_factor(iu, ju) * permutation_factor(id, jd);
+}
+template <bool ELEM>
+__device__ __forceinline__ HkScan hk_scan_body(const ChemTab &t, u64 su, u64 sd, u64 ku, u64 kd) {
+  u64 ru = su, rd = sd; int pw = 1, best = 0, norm2 = 0, nnz = 0, n_off = 0, n_diag = 0, n_diag_terms = 0;
+#pragma nounroll
+  for (int r = 0; r < 4; r++) {          // hk_orbit's loops, written out: no closure stands between these counters and their registers
+    int inv = 0; u64 a = su, b = sd;
+    if (r) { a = hk_map_string(t.hk_map[r - 1], su, inv); b = hk_map_string(t.hk_map[r - 1], sd, inv); }
+    int ph0 = (inv & 1) ? -1 : 1;
+#pragma nounroll
+    for (int j = 0; j < 4; j++) {
+      if (j == 2) {
+        inv = 0;
+        const u64 a2 = hk_map_string(t.hk_map[3], a, inv), b2 = hk_map_string(t.hk_map[3], b, inv);
+        a = a2; b = b2; ph0 = ((inv & 1) ? -ph0 : ph0) * t.hk_p;
+      }
+      const int k = r + 4 * j, ph = (j & 1) ? ph0 * t.hk_z : ph0;
+      const u64 iu = (j & 1) ? b : a, id = (j & 1) ? a : b;
+      if (iu == su && id == sd) norm2 += ph;
+      if (iu < ru || (iu == ru && (id < rd || (id == rd && k < best)))) { ru = iu; rd = id; pw = ph; best = k; }
+      if (ELEM) {
+        if (iu == ku && id == kd) { n_diag += ph; n_diag_terms++; }
+        else { const int sg = hk_offdiag_sign(t, iu, id, ku, kd); if (sg) { n_off += sg * ph; nnz++; } }
+      }
+    }
+  }
+  HkScan o; o.ru = ru; o.rd = rd; o.sum = 0.0; o.phase_w_rep = pw; o.norm2 = norm2; o.nnz = nnz;
+  if (ELEM) {
+    if (fabs(t.hk_ubyn) > 1.0e-10) o.sum = t.hk_ubyn * n_off; else o.nnz = 0;      // (a term counts when |.| > 1e-10, hubbard.f90:2980)
+    if (n_diag_terms) { const double hd = h_hubbardk_body(t, ku, kd, ku, kd); if (fabs(hd) > 1.0e-10) { o.sum = o.sum + hd * n_diag; o.nnz += n_diag_terms; } }
+  }
+  return o;
+}
+__device__ __noinline__ HkScan hk_scan(const ChemTab &t, u64 su, u64 sd, u64 ku, u64 kd) { return hk_scan_body<true>(t, su, sd, ku, kd); }
+// <bra|H|ket> between orbit sums; the bra stands for its representative, the ket is one.  bra == ket: H_ii, which holds the images of i one double
+// excitation away from i (do_walk.f90:3757-3758).  0 when either has no state in the sector.
+__device__ __noinline__ double h_hubbardk_sym(const ChemTab &t, u64 bu, u64 bd, u64 ku, u64 kd) {
+  const HkScan s = hk_scan_body<true>(t, bu, bd, ku, kd);
+  if (s.norm2 <= 0) return 0.0;
+  int n2r = s.norm2;
+  if (!(bu == ku && bd == kd)) { n2r = hk_scan_body<false>(t, ku, kd, ku, kd).norm2; if (n2r <= 0) return 0.0; }
+  return s.phase_w_rep * (sqrt((double)s.norm2) / sqrt((double)n2r)) * (s.sum / s.norm2);
+}
+// the weight of a move i -> (ju, jd), the child's representative as propose_hubbardk returns it: the symmetrised element with norm_j / norm_i and
+// proposal_prob_inv / nnzero (hubbard.f90:3805-3808, 3843-3845)
+__device__ __noinline__ double hk_sym_weight(const ChemTab &t, double tau, double prob, u64 iu, u64 id, u64 ju, u64 jd) {
+  const HkScan s = hk_scan_body<true>(t, ju, jd, iu, id);
+  if (s.norm2 <= 0 || s.nnz == 0) return 0.0;
+  const int n2i = hk_scan_body<false>(t, iu, id, iu, id).norm2;
+  if (n2i <= 0) return 0.0;
+  const double me = s.phase_w_rep * (sqrt((double)s.norm2) / sqrt((double)n2i)) * (s.sum / s.norm2);
+  const double acc = fabs(me) * tau * (prob / (s.nnz / s.norm2));
+  return acc * copysign(1.0, -me);
+}
 
 __device__ inline double h_any(const ChemTab &t, const double *__restrict__ ints, u64 iu, u64 id, u64 ju, u64 jd) {
   if (t.sys_type == 1) return h_heg(t, iu, id, ju, jd);
   if (t.sys_type == 2) return h_hubbard(t, iu, id, ju, jd);
-  if (t.sys_type == 3) return h_hubbardk(t, iu, id, ju, jd);
+  if (t.sys_type == 3) return t.hk_sym ? h_hubbardk_sym(t, iu, id, ju, jd) : h_hubbardk(t, iu, id, ju, jd);
   if (t.time_sym) return h_time_sym(t, ints, iu, id, ju, jd);
   int lev = excitation_level(iu, id, ju, jd);
   return lev < 0 ? 0.0 : h_level(t, ints, iu, id, ju, jd, lev);
@@ -573,6 +679,7 @@ __device__ inline double proposal_weight(const ChemTab &t, const double *__restr
     return acc * copysign(1.0, -me);
   }
   if (t.sys_type == 3) {                 // hubbard.f90:3820, 3843-3845; prob holds proposal_prob_inv = nup * ndn * (nsites - nup)
+    if (t.hk_sym) return hk_sym_weight(t, tau, prob, iu, id, ju, jd);
     const double me = h_hubbardk(t, iu, id, ju, jd);
     const double acc = fabs(me) * tau * prob;
     return acc * copysign(1.0, -me);
@@ -701,13 +808,13 @@ __device__ inline int propose_hubbard(const ChemTab &t, Rng &g, u64 iu, u64 id, 
   prob = (double)(t.nelec * ctr);
   return 1;
 }
-// off_diagonal_move_hubbard_k, hubbard.f90:3738-3767 (space_sym and importance sampling off): random_int(nup), random_int(ndn) and
+// off_diagonal_move_hubbard_k, hubbard.f90:3738-3767 (importance sampling off; space_sym: propose_hubbardk_sym_call below): random_int(nup), random_int(ndn) and
 // random_int(nsites - nup), in that order: the chosen up and dn electrons (k-th set bits, ascending), the up hole (k-th empty orbital,
 // ascending); the dn electron goes to the orbital that takes the momentum the up electron gained.  Returns 2 with prob = the INVERSE
 // proposal probability real(nup * ndn * (nsites - nup)), or 0 when that orbital is occupied -- all three draws consumed either way.
 // Out of line, with everything passed and returned in registers (no reference to a caller's local: that would give every spawn kernel a stack).
 struct HkMove { u64 ju, jd, x; int level; };
-__device__ __noinline__ HkMove propose_hubbardk_call(const ChemTab &t, int mode, u64 x, u64 iu, u64 id) {
+__device__ __forceinline__ HkMove propose_hubbardk_body(const ChemTab &t, int mode, u64 x, u64 iu, u64 id) {
   Rng g; g.mode = mode; g.x = x;
   HkMove m; m.ju = iu; m.jd = id; m.level = 0;
   const int cu = kth_set_wide(iu, rng_int(g, t.nup));
@@ -721,8 +828,20 @@ __device__ __noinline__ HkMove propose_hubbardk_call(const ChemTab &t, int mode,
   m.level = 2;
   return m;
 }
+__device__ __noinline__ HkMove propose_hubbardk_call(const ChemTab &t, int mode, u64 x, u64 iu, u64 id) { return propose_hubbardk_body(t, mode, x, iu, id); }
+// space_sym (hubbard.f90:3771-3817): the same three draws, then the child is replaced by its representative; no move (level 0) onto a determinant
+// without a state in the sector, onto the parent's own orbit, or with a symmetrised element of no terms
+__device__ __noinline__ HkMove propose_hubbardk_sym_call(const ChemTab &t, int mode, u64 x, u64 iu, u64 id) {
+  HkMove m = propose_hubbardk_body(t, mode, x, iu, id);
+  if (m.level) {
+    const HkScan s = hk_scan_body<true>(t, m.ju, m.jd, iu, id);
+    m.ju = s.ru; m.jd = s.rd;
+    if (s.norm2 <= 0 || (s.ru == iu && s.rd == id) || s.nnz == 0) m.level = 0;
+  }
+  return m;
+}
 __device__ __forceinline__ int propose_hubbardk(const ChemTab &t, Rng &g, u64 iu, u64 id, u64 &ju, u64 &jd, double &prob) {
-  const HkMove m = propose_hubbardk_call(t, g.mode, g.x, iu, id);
+  const HkMove m = t.hk_sym ? propose_hubbardk_sym_call(t, g.mode, g.x, iu, id) : propose_hubbardk_call(t, g.mode, g.x, iu, id);
   g.x = m.x; ju = m.ju; jd = m.jd;
   if (m.level) prob = (double)(t.nup * t.ndn * (t.norb - t.nup));
   return m.level;

@@ -119,6 +119,30 @@ __global__ void __launch_bounds__(TPB) k_propose_batch(ChemDev dev, const u64 *u
   if (level > 0) w = proposal_weight(t, dev.integrals, tau, up[i], dn[i], a, b, level, prob);
   ju[i] = a; jd[i] = b; wj[i] = w; state_out[i] = g.x;
 }
+// hubbardk with space_sym: the 16 images of each determinant in the reference's order with their phases, its representative, phase_w_rep, norm
+// and num_distinct (generate_fourfold_k_configs_efficient, more_tools.f90:4670-4819; num_distinct 0 when the norm vanishes)
+__global__ void __launch_bounds__(TPB) k_hk_sym_images(ChemDev dev, const u64 *up, const u64 *dn, long long n, u64 *img_up, u64 *img_dn, int *phases,
+                                                       u64 *rep_up, u64 *rep_dn, int *phase_w_rep, double *norm, int *num_distinct) {
+  __shared__ ChemTab t;
+  stage_tab(&t, dev.tab, dev.tab_words);
+  long long i = (long long)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  const u64 u = up[i], d = dn[i];
+  hk_orbit(t, u, d, [&](int k, u64 a, u64 b, int ph) { img_up[16 * i + k] = a; img_dn[16 * i + k] = b; phases[16 * i + k] = ph; });
+  const HkScan s = hk_scan(t, u, d, u, d);
+  rep_up[i] = s.ru; rep_dn[i] = s.rd; phase_w_rep[i] = s.phase_w_rep;
+  norm[i] = sqrt(fabs((double)s.norm2));
+  num_distinct[i] = (s.norm2 > 0) ? (int)lrint(16.0 / s.norm2) : 0;
+}
+// the upload checks of a space_sym context: bad[0] = the first determinant (lowest index) that is not its own representative or has no state in the sector, else n
+__global__ void __launch_bounds__(TPB) k_hk_sym_check(ChemDev dev, const u64 *up, const u64 *dn, long long n, unsigned long long *bad) {
+  __shared__ ChemTab t;
+  stage_tab(&t, dev.tab, dev.tab_words);
+  long long i = (long long)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  const HkScan s = hk_scan(t, up[i], dn[i], up[i], dn[i]);
+  if (s.norm2 <= 0 || s.ru != up[i] || s.rd != dn[i]) atomicMin(bad, (unsigned long long)i);
+}
 
 // ---- host helpers of sqmc_gpu_set_heatbath_tables (templates: outside the extern "C" block)
 // column-major (i,j,k) of extent n^3 -> [i][j][k] with k fastest

@@ -60,6 +60,55 @@ __device__ __noinline__ void hci_fill_hubbardk(const ChemTab &t, u64 up, u64 dn,
     onum[k] = mel * c; oden[k] = den;
   }
 }
+// hubbardk with space_sym (find_connected_dets_hubbard_k's closing block, hubbard.f90:5611-5627): the reference maps the raw connections to
+// representatives, keeps each once and asks hamiltonian_hubbard_k_space_sym for its element.  Here every raw child j' is emitted as
+// (representative of j',  phase_w_rep(j') norm_j / norm_i <j'|H|i> c): the raw children of i inside one orbit are that orbit's distinct images
+// with an element to i, so the caller's sort-and-sum adds exactly the terms of the symmetrised element.  Raw children in the orbit of i itself
+// land on i's own slot, which therefore holds the plain diagonal in diag_mode 1 (the two add up to the symmetrised H_ii, where the reference has
+// those terms) and only those terms in diag_mode 0.  Children without a state in the (z, p) sector are dropped; a slice selects on the
+// representative's key.  The eps screen stays what it is without space_sym, on the raw term |U / nsites c|, not on the summed element.
+// The counting pass and the writing pass make the same decisions; the writing pass leaves phase_w_rep norm_j times the two permutation factors
+// in onum, and hci_fill_hubbardk_sym turns it into H c.
+__device__ __noinline__ u64 hci_gen_hubbardk_sym(const ChemTab &t, const u64 *binom, u64 n_dn_strings, u64 up, u64 dn, u64 *ou, u64 *od, double *onum, u64 key_lo, u64 key_hi) {
+  const bool sliced = !(key_lo == 0 && key_hi == ~0ull);
+  u64 cnt = 0;
+#pragma nounroll
+  for (u64 eu = up; eu; eu &= eu - 1) {
+    const int p = ctz64(eu) + 1;
+#pragma nounroll
+    for (u64 ed = dn; ed; ed &= ed - 1) {
+      const int q = ctz64(ed) + 1;
+#pragma nounroll
+      for (u64 hr = t.orb_mask & ~up; hr; hr &= hr - 1) {
+        const int r = ctz64(hr) + 1;
+        const int s_ = hk_orbital(t, t.krel[q][0] - (t.krel[r][0] - t.krel[p][0]), t.krel[q][1] - (t.krel[r][1] - t.krel[p][1]));
+        if (!s_ || ((dn >> (s_ - 1)) & 1)) continue;
+        const u64 nu = (up & ~bit64(p - 1)) | bit64(r - 1), nd = (dn & ~bit64(q - 1)) | bit64(s_ - 1);
+        const HkScan sc = hk_scan_body<false>(t, nu, nd, up, dn);
+        if (sc.norm2 <= 0) continue;
+        if (sliced) {
+          u64 ru = 0, rd = 0; int k = 1;
+#pragma nounroll
+          for (u64 d = sc.ru; d; d &= d - 1, k++) ru += binom[ctz64(d) * SQ_BINOM_STRIDE + k];
+          k = 1;
+#pragma nounroll
+          for (u64 d = sc.rd; d; d &= d - 1, k++) rd += binom[ctz64(d) * SQ_BINOM_STRIDE + k];
+          const u64 kk = ru * n_dn_strings + rd;
+          if (!(kk >= key_lo && kk < key_hi)) continue;
+        }
+        if (ou) { ou[cnt] = sc.ru; od[cnt] = sc.rd; onum[cnt] = sc.phase_w_rep * sqrt((double)sc.norm2) * permutation_factor(up, nu) * permutation_factor(dn, nd); }
+        cnt++;
+      }
+    }
+  }
+  return cnt;
+}
+__device__ __noinline__ void hci_fill_hubbardk_sym(const ChemTab &t, u64 up, u64 dn, double c, double den, double *onum, double *oden, u64 cnt) {
+  const int n2i = hk_scan_body<false>(t, up, dn, up, dn).norm2;
+  const double norm_i = sqrt((double)n2i);
+#pragma nounroll
+  for (u64 k = 0; k < cnt; k++) { onum[k] = (n2i > 0) ? (t.hk_ubyn * (onum[k] / norm_i)) * c : 0.0; oden[k] = den; }      // (a source without a state in the sector: elements 0, as hamiltonian_hubbard_k_space_sym has them)
+}
 template <bool REC>
 __global__ void __launch_bounds__(TPB) k_hci_gen(ChemDev dev, const u64 *__restrict__ rup, const u64 *__restrict__ rdn, const double *__restrict__ coef,
                                                  double eps_var, int diag_mode, long long n_ref, int pass, u64 *__restrict__ counts,
@@ -96,7 +145,8 @@ __global__ void __launch_bounds__(TPB) k_hci_gen(ChemDev dev, const u64 *__restr
 #define EMIT(U, D, M, DEN, PK) do { bool in_ = true; if (sliced) { const u64 kk_ = det_key(dev, (U), (D)); in_ = (kk_ >= key_lo && kk_ < key_hi); } \
     if (in_) { if (pass) { ou[base + cnt] = (U); od[base + cnt] = (D); onum[base + cnt] = (M) * c; oden[base + cnt] = (diag_mode == 2) ? (double)i : (DEN); \
       if constexpr (REC) { orec_old[base + cnt] = hii; orec_pk[base + cnt] = (PK); } } cnt++; } } while (0)
-  { double hd = (diag_mode == 1) ? h_any(t, dev.integrals, up, dn, up, dn) : 0.0; EMIT(up, dn, hd, c, DU_NONE); }
+  { double hd = (diag_mode == 1) ? ((t.sys_type == 3) ? h_hubbardk(t, up, dn, up, dn) : h_any(t, dev.integrals, up, dn, up, dn)) : 0.0;      // (hubbardk: the plain diagonal also with space_sym, see hci_gen_hubbardk_sym)
+    EMIT(up, dn, hd, c, DU_NONE); }
   if (t.sys_type == 1) {
     // find_important_connected_dets_heg, heg.f90:2475-2727: no single excitations (momentum); every
     // double p,q -> r,s with k_p + k_q = k_r + k_s whose |H| exceeds eps/|c|.  The reference walks
@@ -136,9 +186,15 @@ __global__ void __launch_bounds__(TPB) k_hci_gen(ChemDev dev, const u64 *__restr
   if (t.sys_type == 3) {
     if (fabs(t.hk_ubyn * c) > eps_var) {      // |H c| > eps, with the one |H| there is
       const u64 at = base + cnt;
-      const u64 m = hci_gen_hubbardk(t, dev.binom, dev.n_dn_strings, up, dn, pass ? ou + at : nullptr, pass ? od + at : nullptr, key_lo, key_hi);
-      if (pass) hci_fill_hubbardk(t, up, dn, c, (diag_mode == 2) ? (double)i : 0.0, ou + at, od + at, onum + at, oden + at, m);
-      cnt += m;
+      if (t.hk_sym) {
+        const u64 m = hci_gen_hubbardk_sym(t, dev.binom, dev.n_dn_strings, up, dn, pass ? ou + at : nullptr, pass ? od + at : nullptr, pass ? onum + at : nullptr, key_lo, key_hi);
+        if (pass) hci_fill_hubbardk_sym(t, up, dn, c, (diag_mode == 2) ? (double)i : 0.0, onum + at, oden + at, m);
+        cnt += m;
+      } else {
+        const u64 m = hci_gen_hubbardk(t, dev.binom, dev.n_dn_strings, up, dn, pass ? ou + at : nullptr, pass ? od + at : nullptr, key_lo, key_hi);
+        if (pass) hci_fill_hubbardk(t, up, dn, c, (diag_mode == 2) ? (double)i : 0.0, ou + at, od + at, onum + at, oden + at, m);
+        cnt += m;
+      }
     }
     if (!pass) counts[i] = cnt;
     return;

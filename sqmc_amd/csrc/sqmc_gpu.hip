@@ -471,7 +471,7 @@ int sqmc_gpu_init_hubbard(const sqmc_hubbard_cfg *cfg, sqmc_gpu_ctx **out) {
   return init_common(c, (int)ns, cfg->nup, cfg->ndn, cfg->rng_mode, cfg->irand_seed, cfg->mwalk, out);
 }
 
-// Hubbard model in its plane-wave basis (hamiltonian_type 'hubbardk', space_sym off): generate_k_vectors' table (hubbard.f90:2179-2324)
+// Hubbard model in its plane-wave basis (hamiltonian_type 'hubbardk'; space_sym: sqmc_gpu_set_hubbardk_space_sym below): generate_k_vectors' table (hubbard.f90:2179-2324)
 // arrives as data in the reference's orbital order; the momentum -> orbital lookup (the reference's kmap) is built here, in the bytes
 // of combine_2 this system has no use for.  Every k component is even in the reference's units of pi / L, so k / 2 mod l is the
 // lattice momentum.
@@ -508,6 +508,90 @@ int sqmc_gpu_init_hubbardk(const sqmc_hubbardk_cfg *cfg, sqmc_gpu_ctx **out) {
   memcpy(t.c2, lut, sizeof(lut));
   t.c2_stride = 6; t.c2_pad = 1;        // (c2_stride only sizes the staging of the table: 6 * 6 shorts hold the 64 bytes)
   return init_common(c, (int)ns, cfg->nup, cfg->ndn, cfg->rng_mode, cfg->irand_seed, cfg->mwalk, out);
+}
+
+// space_sym = .true. for hubbardk (hubbard.f90:181-208): the quantum numbers and the four orbital maps of create_kspace_sym_maps
+// (more_tools.f90:4209-4310) as the reference holds them, c4_map(3, nsites) column-major and reflection_map(nsites), 1-based.  From here on
+// every element, move and connection of this context is the one between orbit sums (chem_device.h).  The maps are data, like the k table;
+// what makes them the maps of a C4 x reflection group of this lattice is checked here.
+int sqmc_gpu_set_hubbardk_space_sym(sqmc_gpu_ctx *c, int32_t z, int32_t p, const int32_t *c4_map, const int32_t *reflection_map) {
+  abandon_head(c);
+  if (!c || !c4_map || !reflection_map) return fail(SQMC_ERR_BAD_ARG, "null argument");
+  ChemTab &t = c->htab;
+  if (t.sys_type != 3) return fail(SQMC_ERR_UNSUPPORTED, "space_sym: the z / p symmetries are those of hubbardk");
+  if (t.hk_lx != t.hk_ly || (t.hk_lx & 1)) return fail(SQMC_ERR_UNSUPPORTED, "space_sym needs a square lattice of even side: the maps fold k = l onto itself (create_kspace_sym_maps)");
+  if (t.nup != t.ndn) return fail(SQMC_ERR_UNSUPPORTED, "nup must equal ndn for space symmetry (hubbard.f90:191)");
+  if ((z != 1 && z != -1) || (p != 1 && p != -1)) return fail(SQMC_ERR_BAD_ARG, "z and p must be 1 or -1");
+  if (c->nwalk > 0 || c->d_prj_ptr || c->d_ct_up) return fail(SQMC_ERR_BAD_ARG, "space_sym must be set before walkers, a projector or a C(T) table: they would be in the determinant basis");
+  const int ns = t.norb;
+  int m[4][SQ_MAXORB + 1];
+  for (int q = 0; q < 4; q++) {
+    bool seen[SQ_MAXORB + 1] = {false};
+    for (int i = 1; i <= ns; i++) {
+      const int v = (q < 3) ? c4_map[(i - 1) * 3 + q] : reflection_map[i - 1];
+      if (v < 1 || v > ns || seen[v]) return fail(SQMC_ERR_BAD_ARG, "space_sym: a map is not a permutation of the orbitals");
+      if (fabs(t.hk_energies[v] - t.hk_energies[i]) > 1.0e-10) return fail(SQMC_ERR_BAD_ARG, "space_sym: a map does not preserve k_energies");
+      seen[v] = true; m[q][i] = v;
+    }
+  }
+  for (int i = 1; i <= ns; i++) {
+    if (m[0][m[0][i]] != m[1][i] || m[0][m[1][i]] != m[2][i] || m[0][m[2][i]] != i || m[3][m[3][i]] != i)
+      return fail(SQMC_ERR_BAD_ARG, "space_sym: the maps do not compose as a C4 (map1 map1 = map2, map1 map2 = map3, map1 map3 = 1) and a reflection (its square = 1)");
+  }
+  for (int q = 0; q < 4; q++) { t.hk_map[q][0] = 0; for (int i = 1; i <= ns; i++) t.hk_map[q][i] = (unsigned char)m[q][i]; }
+  t.hk_z = z; t.hk_p = p; t.hk_sym = 1;
+  HIPCHK(hipMemcpy(c->d_tab, &c->htab, sizeof(ChemTab), hipMemcpyHostToDevice));
+  return SQMC_OK;
+}
+// with space_sym: every determinant of an uploaded list must be its own representative and have a state in the (z, p) sector.
+// (Both doors below work in ONE device buffer that their caller-side half allocates and frees, whatever the HIP calls in between return.)
+static int hk_sym_check_run(sqmc_gpu_ctx *c, int64_t n, const uint64_t *up, const uint64_t *dn, u64 *buf, unsigned long long *bad) {
+  u64 *du = buf, *dd = buf + n; unsigned long long *dbad = (unsigned long long *)(buf + 2 * n);
+  HIPCHK(hipMemcpy(du, up, n * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dd, dn, n * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dbad, bad, 8, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_hk_sym_check, dim3(nblk(n)), dim3(TPB), 0, c->st, c->dev, du, dd, (long long)n, dbad);
+  HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(c->st));
+  HIPCHK(hipMemcpy(bad, dbad, 8, hipMemcpyDeviceToHost));
+  return SQMC_OK;
+}
+static int hk_sym_check_list(sqmc_gpu_ctx *c, int64_t n, const uint64_t *up, const uint64_t *dn, const char *what) {
+  if (c->htab.sys_type != 3 || !c->htab.hk_sym || n <= 0) return SQMC_OK;
+  u64 *buf = nullptr; unsigned long long bad = (unsigned long long)n;
+  HIPCHK(hipMalloc(&buf, (2 * n + 1) * 8));
+  const int rc = hk_sym_check_run(c, n, up, dn, buf, &bad);
+  hipFree(buf);
+  if (rc) return rc;
+  if (bad < (unsigned long long)n) return fail(SQMC_ERR_BAD_ARG, what);
+  return SQMC_OK;
+}
+static int hk_sym_images_run(sqmc_gpu_ctx *c, int64_t n, const uint64_t *up, const uint64_t *dn, uint64_t *images_up, uint64_t *images_dn, int32_t *phases,
+                             uint64_t *rep_up, uint64_t *rep_dn, int32_t *phase_w_rep, double *norm, int32_t *num_distinct, u64 *buf) {
+  // 8-byte items first: up, dn, rep_up, rep_dn [n each], norm [n], images_up, images_dn [16 n each]; then the 4-byte ones: phases [16 n], phase_w_rep, num_distinct [n each]
+  u64 *du = buf, *dd = buf + n, *dru = buf + 2 * n, *drd = buf + 3 * n; double *dnm = (double *)(buf + 4 * n);
+  u64 *diu = buf + 5 * n, *did = buf + 21 * n; int *dph = (int *)(buf + 37 * n), *dpw = dph + 16 * n, *dnd = dpw + n;
+  HIPCHK(hipMemcpy(du, up, n * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dd, dn, n * 8, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_hk_sym_images, dim3(nblk(n)), dim3(TPB), 0, c->st, c->dev, du, dd, (long long)n, diu, did, dph, dru, drd, dpw, dnm, dnd);
+  HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(c->st));
+  HIPCHK(hipMemcpy(images_up, diu, n * 128, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(images_dn, did, n * 128, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(phases, dph, n * 64, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(rep_up, dru, n * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(rep_dn, drd, n * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(phase_w_rep, dpw, n * 4, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(num_distinct, dnd, n * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(norm, dnm, n * 8, hipMemcpyDeviceToHost));
+  return SQMC_OK;
+}
+int sqmc_gpu_hubbardk_sym_images(sqmc_gpu_ctx *c, int64_t n, const uint64_t *up, const uint64_t *dn, uint64_t *images_up, uint64_t *images_dn, int32_t *phases,
+                                 uint64_t *rep_up, uint64_t *rep_dn, int32_t *phase_w_rep, double *norm, int32_t *num_distinct) {
+  if (!c) return fail(SQMC_ERR_BAD_ARG, "null ctx");
+  if (c->htab.sys_type != 3 || !c->htab.hk_sym) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_hubbardk_sym_images: not a hubbardk context with space_sym set");
+  if (n <= 0) return SQMC_OK;
+  if (!up || !dn || !images_up || !images_dn || !phases || !rep_up || !rep_dn || !phase_w_rep || !norm || !num_distinct) return fail(SQMC_ERR_BAD_ARG, "null argument");
+  const u64 lim = c->htab.orb_mask;
+  for (long long i = 0; i < n; i++) if ((up[i] & ~lim) || (dn[i] & ~lim)) return fail(SQMC_ERR_BAD_ARG, "determinant has bits beyond norb");
+  u64 *buf = nullptr;
+  HIPCHK(hipMalloc(&buf, (size_t)n * (37 * 8 + 18 * 4)));
+  const int rc = hk_sym_images_run(c, n, up, dn, images_up, images_dn, phases, rep_up, rep_dn, phase_w_rep, norm, num_distinct, buf);
+  hipFree(buf);
+  return rc;
 }
 
 static void comm_release(sqmc_gpu_ctx *c);
@@ -593,6 +677,7 @@ int sqmc_gpu_set_ct_table(sqmc_gpu_ctx *c, int64_t n, const uint64_t *up, const 
   if (!c) return fail(SQMC_ERR_BAD_ARG, "null ctx");
   for (long long i = 1; i < n; i++)
     if (!(up[i - 1] < up[i] || (up[i - 1] == up[i] && dn[i - 1] < dn[i]))) return fail(SQMC_ERR_BAD_ARG, "C(T) list must be strictly sorted by (up,dn)");
+  { int rs = hk_sym_check_list(c, n, up, dn, "space_sym: a C(T) determinant is not its own representative or has no state in the (z, p) sector"); if (rs) return rs; }
   psit_off(c);
   hipFree(c->d_ct_up); hipFree(c->d_ct_dn); hipFree(c->d_ct_num); hipFree(c->d_ct_den);
   c->n_ct = n;
@@ -711,6 +796,7 @@ int sqmc_gpu_upload_walkers(sqmc_gpu_ctx *c, int64_t n, const uint64_t *up, cons
     if (seg > 0) HIPCHK(hipMemcpy(c->d_ps_impof, impof.data(), seg * 4, hipMemcpyHostToDevice));
     c->psit.n_perm = n_perm;
   }
+  { int rs = hk_sym_check_list(c, n, up, dn, "space_sym: a walker is not its own representative or has no state in the (z, p) sector"); if (rs) return rs; }
   HIPCHK(hipMemcpy(c->w.up, up, n * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(c->w.dn, dn, n * 8, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(c->w.wt, wt, n * 8, hipMemcpyHostToDevice));
   { std::vector<u32> f(n); for (long long i = 0; i < n; i++) f[i] = pack_flg(impd[i], init[i], psign[i]);

@@ -23,6 +23,7 @@ module sqmc_gpu_mod
   public :: sqmc_gpu_diag_update_batch, sqmc_gpu_hci_set_diag_update, sqmc_gpu_hci_connections_record
   public :: sqmc_gpu_hci_pt2_stochastic_prepare, sqmc_gpu_hci_pt2_stochastic_sample, sqmc_gpu_hci_pt2_stochastic_stats, sqmc_gpu_hci_pt2_stochastic_free
   public :: sqmc_gpu_set_spawn_diagnostics, sqmc_gpu_reset_spawn_diagnostics, sqmc_gpu_get_spawn_diagnostics
+  public :: sqmc_gpu_set_hubbardk_space_sym, sqmc_gpu_hubbardk_sym_images
   public :: sqmc_gpu_check
 
   integer(c_int), parameter, public :: SQMC_RNG_REPLAY = 0, SQMC_RNG_COUNTER = 1
@@ -58,7 +59,7 @@ module sqmc_gpu_mod
     integer(c_int64_t) :: mwalk
   end type
 
-  type, bind(C) :: sqmc_hubbardk_cfg   ! hamiltonian_type 'hubbardk' (space_sym = .false.): the tables of generate_k_vectors
+  type, bind(C) :: sqmc_hubbardk_cfg   ! hamiltonian_type 'hubbardk': the tables of generate_k_vectors (space_sym: sqmc_gpu_set_hubbardk_space_sym)
     integer(c_int32_t) :: l_x, l_y, nup, ndn
     real(c_double) :: t, U
     type(c_ptr) :: k_vectors           ! integer(c_int32_t) k_vectors(2, nsites), as in module hubbard
@@ -270,6 +271,17 @@ module sqmc_gpu_mod
     end function
     integer(c_int) function sqmc_gpu_init_hubbardk(cfg, ctx) bind(C, name='sqmc_gpu_init_hubbardk')
       import; type(sqmc_hubbardk_cfg), intent(in) :: cfg; type(c_ptr), intent(out) :: ctx
+    end function
+    ! space_sym = .true. for hubbardk: z, p and the module variables c4_map(3, nsites), reflection_map(nsites) of hubbard.f90 as they are
+    integer(c_int) function sqmc_gpu_set_hubbardk_space_sym(ctx, z, p, c4_map, reflection_map) bind(C, name='sqmc_gpu_set_hubbardk_space_sym')
+      import; type(c_ptr), value :: ctx; integer(c_int32_t), value :: z, p; integer(c_int32_t), intent(in) :: c4_map(3, *), reflection_map(*)
+    end function
+    ! generate_fourfold_k_configs_efficient for a list: images and phases as (16, n) arrays
+    integer(c_int) function sqmc_gpu_hubbardk_sym_images(ctx, n, up, dn, images_up, images_dn, phases, rep_up, rep_dn, phase_w_rep, norm, num_distinct) &
+        bind(C, name='sqmc_gpu_hubbardk_sym_images')
+      import; type(c_ptr), value :: ctx; integer(c_int64_t), value :: n; integer(c_int64_t), intent(in) :: up(*), dn(*)
+      integer(c_int64_t), intent(out) :: images_up(16, *), images_dn(16, *), rep_up(*), rep_dn(*)
+      integer(c_int32_t), intent(out) :: phases(16, *), phase_w_rep(*), num_distinct(*); real(c_double), intent(out) :: norm(*)
     end function
     integer(c_int) function sqmc_gpu_finalize(ctx) bind(C, name='sqmc_gpu_finalize')
       import; type(c_ptr), value :: ctx

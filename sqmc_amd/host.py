@@ -1273,18 +1273,56 @@ class HubbardHost:
 
 
 class HubbardKHost:
-    """Hubbard model in its plane-wave basis on a periodic l_x by l_y lattice (hamiltonian_type 'hubbardk', space_sym = .false.):
+    """Hubbard model in its plane-wave basis on a periodic l_x by l_y lattice (hamiltonian_type 'hubbardk', with or without space_sym):
     the orbital table of generate_k_vectors (hubbard.f90:2237-2281), the start determinant of k_hf_up / k_hf_dn (the first nup / ndn
     orbitals of that order) and the walk set-up with a determinant-list trial wavefunction.  Connections come from the device
-    generator (find_connected_dets_hubbard_k); the z / p symmetries and the Gutzwiller trial functions are outside this path."""
+    generator (find_connected_dets_hubbard_k); the Gutzwiller trial functions are outside this path.
+    space_sym (hubbard.f90:181-208): the walk among the representatives of the orbits under C4 x reflection x spin inversion, in the sector
+    z (spin inversion), p (reflection), C4-A1, on a square lattice of even side with nup = ndn.  The start determinant (start = (up, dn), by
+    default the first orbitals) must have total momentum 0 and a state in the sector; it is replaced by its representative.  Every context
+    from gpu() then carries the maps, and the deterministic projector comes from sym_sparse_ham.  Reducing the start determinant is the
+    device's work (sqmc_gpu_hubbardk_sym_images), so with space_sym the constructor opens a context on the current device for that one call
+    and closes it again: it needs a GPU and can raise SqmcGpuError; without space_sym it touches no device."""
 
-    def __init__(self, l_x, l_y, nup, ndn, t=1.0, U=4.0):
+    def __init__(self, l_x, l_y, nup, ndn, t=1.0, U=4.0, space_sym=False, z=1, p=1, start=None):
         self.l_x, self.l_y, self.nup, self.ndn, self.t, self.U = int(l_x), int(l_y), int(nup), int(ndn), float(t), float(U)
         self.norb, self.nelec = self.l_x * self.l_y, self.nup + self.ndn
         if not abs(self.U) / self.norb > 1e-290:
             raise ValueError("HubbardKHost needs U != 0: every connection is an element +-U/nsites, and the set-up finds them by screening on it")
         self.k_vectors, self.k_energies = self._k_table()
         self.hf_up, self.hf_dn = (1 << self.nup) - 1, (1 << self.ndn) - 1
+        if start is not None:
+            self.hf_up, self.hf_dn = int(start[0]), int(start[1])
+            if bin(self.hf_up).count("1") != self.nup or bin(self.hf_dn).count("1") != self.ndn or (self.hf_up | self.hf_dn) >> self.norb:
+                raise ValueError("start determinant does not hold nup / ndn electrons in nsites orbitals")
+        self.space_sym, self.z, self.p = bool(space_sym), int(z), int(p)
+        if self.space_sym:
+            if self.l_x != self.l_y or self.l_x % 2:
+                raise ValueError("space_sym needs a square lattice of even side")
+            if self.nup != self.ndn:
+                raise ValueError("Time symmetry for hubbardk will not work when nup and ndn are not equal!")
+            if abs(self.z) != 1 or abs(self.p) != 1:
+                raise ValueError("z and p must be either 1 or -1")
+            self.c4_map, self.reflection_map = self._sym_maps()
+            q = [sum(int(self.k_vectors[o, a]) for det in (self.hf_up, self.hf_dn) for o in range(self.norb) if det >> o & 1) % (2 * self.l_x) for a in (0, 1)]
+            if q != [0, 0]:
+                raise ValueError("space_sym: the start determinant has total momentum %s (units of pi / L), not 0: give start=(up, dn)" % (q,))
+            im = self._with_ctx(None, lambda g: g.hubbardk_sym_images([self.hf_up], [self.hf_dn]))
+            if int(im["num_distinct"][0]) == 0:
+                raise ValueError("space_sym: the start determinant has no state in the sector z = %d, p = %d" % (self.z, self.p))
+            self.hf_up, self.hf_dn = int(im["rep_up"][0]), int(im["rep_dn"][0])
+
+    def _sym_maps(self):
+        """c4_map[nsites, 3] and reflection_map[nsites], 1-based: the orbital whose momentum is the image of orbital i's under
+        (kx, ky) -> (ky, -kx), (-kx, -ky), (-ky, kx) and (kx, ky) -> (-ky, -kx), momenta compared modulo 2 l (so k = l maps to itself)"""
+        m = 2 * self.l_x
+        where = {(int(kx) % m, int(ky) % m): i + 1 for i, (kx, ky) in enumerate(self.k_vectors.tolist())}
+        c4, rf = np.zeros((self.norb, 3), np.int32), np.zeros(self.norb, np.int32)
+        for i, (kx, ky) in enumerate(self.k_vectors.tolist()):
+            for q, (a, b) in enumerate(((ky, -kx), (-kx, -ky), (-ky, kx))):
+                c4[i, q] = where[(a % m, b % m)]
+            rf[i] = where[((-ky) % m, (-kx) % m)]
+        return c4, rf
 
     def _k_table(self):
         """k_vectors[nsites, 2] (units of pi / L) and k_energies[nsites], sorted as the reference sorts them: repeatedly the first
@@ -1314,7 +1352,44 @@ class HubbardKHost:
     def gpu(self, proposal="uniform", **kw):
         if proposal != "uniform":
             raise ValueError("the hubbardk context has the one proposal of its system (off_diagonal_move_hubbard_k)")
-        return GpuChem.hubbardk(self.l_x, self.l_y, self.nup, self.ndn, self.t, self.U, self.k_vectors, self.k_energies, **kw)
+        g = GpuChem.hubbardk(self.l_x, self.l_y, self.nup, self.ndn, self.t, self.U, self.k_vectors, self.k_energies, **kw)
+        if self.space_sym:
+            try:
+                g.set_hubbardk_space_sym(self.z, self.p, self.c4_map, self.reflection_map)
+            except Exception:
+                g.close()
+                raise
+        return g
+
+    def sym_sparse_ham(self, imp_up, imp_dn, g):
+        """space_sym: the matrix among the representatives (imp_up, imp_dn) (sorted), in build_sparse_ham's form (per row the diagonal, then
+        the columns j < i ascending, 1-based; zero elements absent).  Every number is the device's: the diagonal from hamiltonian_batch, the rest
+        from the connection generator in raw mode, whose terms of one (row, column) add up to the symmetrised element; the membership
+        search and the assembly are done here."""
+        up, dn = np.asarray(imp_up, np.uint64), np.asarray(imp_dn, np.uint64)
+        n = len(up)
+        diag = g.hamiltonian_batch(up, dn, up, dn)
+        cu, cd, num, src = g.hci_connections(up, dn, np.ones(n), 1e-300, diag_mode=2)
+        row = _slots_in(cu, cd, up, dn)
+        col = src.astype(np.int64)
+        keep = (row >= 0) & (col < row)
+        flat = row[keep] * n + col[keep]
+        cells, inv = np.unique(flat, return_inverse=True)
+        vals = np.zeros(len(cells))
+        np.add.at(vals, inv, num[keep])
+        nz = vals != 0.0
+        cells, vals = cells[nz], vals[nz]                       # sorted by (row, column)
+        r_, c_ = cells // n, cells % n
+        counts = 1 + np.bincount(r_, minlength=n).astype(np.int64)
+        starts = np.concatenate(([0], np.cumsum(counts)))[:-1]
+        idx, val = np.zeros(int(counts.sum()), np.int64), np.zeros(int(counts.sum()))
+        idx[starts], val[starts] = np.arange(1, n + 1), diag
+        pos = starts[r_] + 1 + (np.arange(len(r_)) - np.searchsorted(r_, r_, side="left"))
+        idx[pos], val[pos] = c_ + 1, vals
+        return counts, idx, val
+
+    def _sparse_ham(self, g, up, dn):
+        return self.sym_sparse_ham(up, dn, g) if self.space_sym else g.build_sparse_ham(up, dn)
 
     def _with_ctx(self, g, fn):
         if g is not None:
@@ -1361,7 +1436,15 @@ class HubbardKHost:
     def setup_walk(self, g, n_truncate_trial_wf=20, size_deterministic=500, tau_multiplier=0.5, n_levels=1):
         s = WalkSetup()
         up, dn = self.first_order_space(n_levels, g)
-        w, X, _ = lowest_state(g, up, dn)
+        if self.space_sym:
+            counts, idx, val = self.sym_sparse_ham(up, dn, g)
+            plan = SpmvPlan(counts, idx, val)
+            try:
+                w, X = davidson_lowest(plan, val[np.concatenate(([0], np.cumsum(counts)))[:-1]])
+            finally:
+                plan.close()
+        else:
+            w, X, _ = lowest_state(g, up, dn)
         c = X[:, 0]
         if c[np.argmax(np.abs(c))] < 0:
             c = -c
@@ -1373,7 +1456,7 @@ class HubbardKHost:
         o = sort_dets(up_s[:n_i], dn_s[:n_i])
         s.imp_up, s.imp_dn = up_s[:n_i][o].copy(), dn_s[:n_i][o].copy()
         s.tau, s.e_var = tau_multiplier / self.spectral_range_bound(), float(w[0])
-        pc, pi_, pv = g.build_sparse_ham(s.imp_up, s.imp_dn)
+        pc, pi_, pv = self._sparse_ham(g, s.imp_up, s.imp_dn)
         s.prj_counts, s.prj_indices, s.prj_values = pc, pi_, -s.tau * pv
         s.ct_up, s.ct_dn, s.ct_num, s.ct_den = g.hci_connections(s.psi_up, s.psi_dn, s.psi_c, 1e-300, diag_mode=1)
         s.e_trial0 = float(np.dot(s.ct_num, s.ct_den) / np.dot(s.ct_den, s.ct_den))

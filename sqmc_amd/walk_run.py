@@ -88,8 +88,22 @@ def parse_walk_deck(text):
         a = _numbers(nxt(), 2); d.update(t=a[0], U=a[1])
         a = _numbers(nxt(), 2); d.update(nup=int(a[0]), ndn=int(a[1]))
         d["space_sym"] = _logical(nxt().split()[0])
-        if d["space_sym"]:
-            raise SystemExit("sqmc_amd.walk_run: space_sym = t (the z / p symmetries of hubbardk) is not on the GPU path; use space_sym = f")
+        d["z"], d["p"] = 1, 1
+        if d["space_sym"]:                        # hubbard.f90:185-204: the line z p, then the reference's three stops
+            if d["l_x"] != d["l_y"] or d["l_x"] % 2:
+                raise SystemExit("sqmc_amd.walk_run: space_sym = t needs a square lattice of even side (l_x = l_y = 4, 6 or 8): the C4 and reflection maps "
+                                 "of create_kspace_sym_maps are defined there only")
+            try:
+                a = _numbers(nxt(), 2)
+            except (StopIteration, IndexError, ValueError):
+                raise SystemExit("sqmc_amd.walk_run: space_sym = t must be followed by the line z p")
+            d.update(z=int(a[0]), p=int(a[1]))
+            if d["nup"] != d["ndn"]:
+                raise SystemExit("Time symmetry for hubbardk will not work when nup and ndn are not equal! Stopping the program....")
+            if abs(d["z"]) != 1:
+                raise SystemExit("z(time reversal) must be either 1 or -1")
+            if abs(d["p"]) != 1:
+                raise SystemExit("p(reflection about y-axis) must be either 1 or -1")
     else:
         raise SystemExit("sqmc_amd.walk_run: hamiltonian_type %r has no GPU operator (chem, heg, hubbard2, hubbardk)" % d["hamiltonian_type"])
     if d["proposal_method"] not in ("uniform2", "uniform") and not (d["proposal_method"] in ("fast_heatbath", "cauchyschwarz") and d["hamiltonian_type"] == "chem"):
@@ -220,7 +234,13 @@ def run_walk(deck, fcidump="FCIDUMP", out=sys.stdout, walkalize=None, max_equil_
         hst = H.HegHost(d["n_dim"], d["r_s"], d["nelec"], d["nup"], d["cutoff_radius"])
         skw = dict(n_truncate_trial_wf=1, size_deterministic=max(d["size_deterministic"], 1), tau_multiplier=d["tau_multiplier"])
     elif d["hamiltonian_type"] == "hubbardk":
-        hst = H.HubbardKHost(d["l_x"], d["l_y"], d["nup"], d["ndn"], d["t"], d["U"])
+        if d["space_sym"]:                        # hubbard.f90:187-189
+            p(" Spatial + time symmetries of hubbardk being used")
+            p("z(time reversal), p(reflection about y-axis)=%4d%4d" % (d["z"], d["p"]))
+        try:
+            hst = H.HubbardKHost(d["l_x"], d["l_y"], d["nup"], d["ndn"], d["t"], d["U"], space_sym=d["space_sym"], z=d["z"], p=d["p"])
+        except (ValueError, sqmc_amd.SqmcGpuError) as e:          # (with space_sym the constructor reduces the start determinant on the device)
+            raise SystemExit("sqmc_amd.walk_run: %s" % e)
         skw = dict(n_truncate_trial_wf=20, size_deterministic=max(d["size_deterministic"], 1), tau_multiplier=d["tau_multiplier"])
     else:
         hst = H.HubbardHost(d["l_x"], d["l_y"], d["pbc"], d["nup"], d["ndn"], d["t"], d["U"])
