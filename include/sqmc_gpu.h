@@ -543,6 +543,16 @@ int sqmc_gpu_diag_update_batch(sqmc_gpu_ctx *ctx, int64_t n, const double *old_d
  * context: honoured by sqmc_gpu_hci_pt2 (any slice count) and by a plan from sqmc_gpu_hci_pt2_stochastic_prepare (the mode as it
  * stands at prepare).  Modes 1 and 2 are refused (SQMC_ERR_UNSUPPORTED) on time_sym and hubbard2 contexts. */
 int sqmc_gpu_hci_set_diag_update(sqmc_gpu_ctx *ctx, int32_t mode);
+/* Test door, not for hosts: runs the bucket-boundary kernel of the short-list tail on the context's stream over caller-supplied
+ * arrays.  keys: n0 >= 1 ascending 32-bit sort keys of a resident list (the door forms the key << 32 | index words).  B buckets;
+ * every other input is B + 1 words or null: kb / hint (boundary keys of this step and about where they lie; kb null: no positions
+ * are looked for, and pos must be null too), kb_prev / pos_prev (the boundaries scount was counted with and where they lay; either
+ * null: equal numbers of residents), scount (spawns per bucket; needed with kb_out).  Outputs: pos (B + 1 words: first position
+ * whose key is >= kb[j]), kb_out and hint_out (B words each: the next boundaries and their places; kb_out null: not made;
+ * B <= 256 with kb_out). */
+int sqmc_gpu_debug_bucket_boundaries(sqmc_gpu_ctx *ctx, int64_t n0, const uint32_t *keys, int32_t B, const uint32_t *kb, const uint32_t *hint,
+                                     const uint32_t *kb_prev, const uint32_t *pos_prev, const uint32_t *scount, uint32_t *pos, uint32_t *kb_out,
+                                     uint32_t *hint_out);
 /* sqmc_gpu_hci_connections_slice with the record every connection carries for the update (diag_elems_info as
  * find_important_connected_dets_chem fills it, chemistry.f90:7148-7152): out_old_diag = H_ii of the source the connection was
  * generated from, out_pqrs = four int32 per connection, all 0 for a self slot or a single excitation.  Merged modes keep the record

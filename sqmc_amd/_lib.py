@@ -29,7 +29,7 @@ EXPORTS = [
     "sqmc_gpu_shard_step", "sqmc_gpu_shard_run", "sqmc_gpu_shard_time_split", "sqmc_gpu_get_rng", "sqmc_gpu_set_rng", "sqmc_gpu_tail_stats", "sqmc_gpu_last_tail", "sqmc_gpu_slowest_steps", "sqmc_gpu_set_chained_runs", "sqmc_gpu_spmv_prepare", "sqmc_gpu_davidson",
     "sqmc_gpu_spmv_apply", "sqmc_gpu_spmv_free", "sqmc_gpu_build_spmv_plan", "sqmc_gpu_spmv_sym_upper", "sqmc_gpu_hamiltonian_batch",
     "sqmc_gpu_propose_batch", "sqmc_gpu_hamiltonian_chem_batch", "sqmc_gpu_build_sparse_ham", "sqmc_gpu_hci_connections", "sqmc_gpu_hci_connections_slice", "sqmc_gpu_hci_pt2", "sqmc_gpu_hci_pt2_stochastic_prepare", "sqmc_gpu_hci_pt2_stochastic_sample", "sqmc_gpu_hci_pt2_stochastic_stats", "sqmc_gpu_hci_pt2_stochastic_free", "sqmc_gpu_hci_set_active_space", "sqmc_gpu_diag_update_batch", "sqmc_gpu_hci_set_diag_update", "sqmc_gpu_hci_connections_record", "sqmc_gpu_free", "sqmc_gpu_set_timing", "sqmc_gpu_get_timing",
-    "sqmc_gpu_set_spawn_diagnostics", "sqmc_gpu_reset_spawn_diagnostics", "sqmc_gpu_get_spawn_diagnostics",
+    "sqmc_gpu_set_spawn_diagnostics", "sqmc_gpu_reset_spawn_diagnostics", "sqmc_gpu_get_spawn_diagnostics", "sqmc_gpu_debug_bucket_boundaries",
 ]
 
 
@@ -788,6 +788,22 @@ def _gpuchem_spawn_diagnostics(self):
                 max_ratio_level=ml.value, min_ratio=mn.value, n_nan=nn.value)
 
 
+def _gpuchem_debug_bucket_boundaries(self, keys, B, kb=None, hint=None, kb_prev=None, pos_prev=None, scount=None, want_next=True):
+    """sqmc_gpu_debug_bucket_boundaries (test door): the bucket-boundary kernel over ascending 32-bit keys.  kb, hint, kb_prev, pos_prev,
+    scount: B + 1 words or None.  Returns (pos[B + 1] or None without kb, kb_out[B], hint_out[B]) -- the last two None unless want_next."""
+    k = np.ascontiguousarray(keys, np.uint32)
+    arrs = [None if a is None else np.ascontiguousarray(a, np.uint32) for a in (kb, hint, kb_prev, pos_prev, scount)]
+    for a in arrs:
+        if a is not None and len(a) != B + 1:
+            raise ValueError("kb, hint, kb_prev, pos_prev and scount hold B + 1 words")
+    pos = np.zeros(B + 1, np.uint32) if kb is not None else None
+    kb_out, hint_out = (np.zeros(B, np.uint32), np.zeros(B, np.uint32)) if want_next else (None, None)
+    self.L.sqmc_gpu_debug_bucket_boundaries.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32] + [C.c_void_p] * 8
+    _chk(self.L.sqmc_gpu_debug_bucket_boundaries(self.h, len(k), _p(k), int(B), *[None if a is None else _p(a) for a in arrs + [pos, kb_out, hint_out]]))
+    return pos, kb_out, hint_out
+
+
+GpuChem.debug_bucket_boundaries = _gpuchem_debug_bucket_boundaries
 GpuChem.set_spawn_diagnostics = _gpuchem_set_spawn_diagnostics
 GpuChem.reset_spawn_diagnostics = _gpuchem_reset_spawn_diagnostics
 GpuChem.spawn_diagnostics = _gpuchem_spawn_diagnostics

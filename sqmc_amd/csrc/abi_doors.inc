@@ -544,6 +544,42 @@ int sqmc_gpu_hci_set_diag_update(sqmc_gpu_ctx *c, int32_t mode) {
 }
 // milliseconds the term kernel of the last sqmc_gpu_hci_pt2 took, all slices (0 unless SQMC_PT2_TIME was set when the library loaded); not part of the ABI
 int sqmc_gpu_debug_pt2_terms_ms(sqmc_gpu_ctx *c, double *ms) { if (!c || !ms) return SQMC_ERR_BAD_ARG; *ms = c->pt2_terms_ms; return SQMC_OK; }
+// Test door of the bucket-boundary blocks (bucket_partition.h): k_bucket_boundaries on the context's stream over the caller's sorted keys.
+int sqmc_gpu_debug_bucket_boundaries(sqmc_gpu_ctx *c, int64_t n0, const uint32_t *keys, int32_t B, const uint32_t *kb, const uint32_t *hint, const uint32_t *kb_prev,
+                                     const uint32_t *pos_prev, const uint32_t *scount, uint32_t *pos, uint32_t *kb_out, uint32_t *hint_out) {
+  if (!c || !keys || n0 < 1 || n0 >= (1ll << 31) || B < 1 || B > BK_MAXB) return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_debug_bucket_boundaries: bad argument");
+  if ((kb != nullptr) != (pos != nullptr)) return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_debug_bucket_boundaries: kb and pos go together");
+  if (hint_out && !kb_out) return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_debug_bucket_boundaries: hint_out without kb_out");
+  if (kb_out && (!scount || B > BK_REBAL_MAXB)) return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_debug_bucket_boundaries: next boundaries need scount and B <= BK_REBAL_MAXB");
+  for (int64_t i = 1; i < n0; i++) if (keys[i] < keys[i - 1]) return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_debug_bucket_boundaries: keys are not ascending");
+  if (!kb && !kb_out) return SQMC_OK;
+  const size_t nb = (size_t)B + 1;
+  std::vector<u64> words(n0);
+  for (int64_t i = 0; i < n0; i++) words[i] = ((u64)keys[i] << 32) | (u64)i;
+  u64 *d_keys = nullptr; u32 *d_w = nullptr;                 // eight arrays of B + 1 words: kb, hint, kb_prev, pos_prev, scount, pos, kb_out, hint_out
+  if (hipMalloc(&d_keys, (size_t)n0 * 8) != hipSuccess || hipMalloc(&d_w, 8 * nb * 4) != hipSuccess) { (void)hipGetLastError(); hipFree(d_keys); return fail(SQMC_ERR_HIP, "hipMalloc"); }
+  const uint32_t *in[5] = {kb, hint, kb_prev, pos_prev, scount};
+  hipError_t e = hipMemcpy(d_keys, words.data(), (size_t)n0 * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(d_w, 0, 8 * nb * 4);
+  for (int q = 0; q < 5 && e == hipSuccess; q++) if (in[q]) e = hipMemcpy(d_w + q * nb, in[q], nb * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    BucketArgs ba; memset(&ba, 0, sizeof(ba));
+    ba.B = B; ba.scount = d_w + 4 * nb;
+    if (kb) { ba.kb = d_w; ba.pos = d_w + 5 * nb; if (hint) ba.hint = d_w + nb; }
+    if (kb_prev) ba.kb_prev = d_w + 2 * nb;
+    if (pos_prev) ba.pos_prev = d_w + 3 * nb;
+    if (kb_out) { ba.kb_out = d_w + 6 * nb; if (hint_out) ba.hint_out = d_w + 7 * nb; }
+    hipLaunchKernelGGL(k_bucket_boundaries, dim3(2), dim3(BK_T), 0, c->st, (const u64 *)d_keys, (long long)n0, ba);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(c->st);
+  }
+  if (e == hipSuccess && pos) e = hipMemcpy(pos, d_w + 5 * nb, nb * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && kb_out) e = hipMemcpy(kb_out, d_w + 6 * nb, (size_t)B * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && hint_out) e = hipMemcpy(hint_out, d_w + 7 * nb, (size_t)B * 4, hipMemcpyDeviceToHost);
+  hipFree(d_keys); hipFree(d_w);
+  if (e != hipSuccess) return fail(SQMC_ERR_HIP, std::string("sqmc_gpu_debug_bucket_boundaries: ") + hipGetErrorString(e));
+  return SQMC_OK;
+}
 int sqmc_gpu_hci_connections_record(sqmc_gpu_ctx *c, int64_t n_ref, const uint64_t *ref_up, const uint64_t *ref_dn, const double *coeffs, double eps,
                                     int diag_mode, int32_t slice, int32_t n_slices, int64_t *out_n, uint64_t **out_up, uint64_t **out_dn,
                                     double **out_num, double **out_den, double **out_old_diag, int32_t **out_pqrs) {

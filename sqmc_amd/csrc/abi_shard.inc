@@ -234,7 +234,7 @@ static int shard_begin_impl(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double 
         BucketArgs hb; memset(&hb, 0, sizeof(hb));
         hb.B = (int)B; hb.scount = c->d_bscount;
         c->head_kb_use = choose_boundaries(c, B, n0, hb);
-        if (hb.kb || hb.kb_out) hipLaunchKernelGGL(k_bucket_boundaries, dim3(1), dim3(BK_T), 0, c->st2, (const u64 *)c->d_keys, n0, hb);
+        if (hb.kb || hb.kb_out) hipLaunchKernelGGL(k_bucket_boundaries, dim3(2), dim3(BK_T), 0, c->st2, (const u64 *)c->d_keys, n0, hb);
         c->shard_ba = hb;
       }
       HIPCHK(hipEventRecord(c->e_join, c->st2));

@@ -11,7 +11,7 @@
 //                        no atomics, no scan kernel.  The ranges: until boundaries have been learnt, the keys of the resident
 //                        walkers at positions b n0 / B (every step leaves the residents sorted); then boundary keys that
 //                        equalise residents + spawns per bucket, remade every step from the last tail's counts
-//                        (bk_rebalance_block, bucket_partition.h).
+//                        (bk_next_block, bucket_partition.h).
 //   k_anneal_bucket      one block per bucket: gathers its children from every partition block (two dependent loads), sorts
 //                        them in LDS -- one stable counting pass on the GAP between residents a child falls into, then a
 //                        ranking inside the gap: the order of merge_sort2_up_dn (do_walk.f90:5411-5614), residents first on
@@ -28,10 +28,10 @@
 #pragma once
 
 // the boundary block as a kernel of its own (sharded steps: on the side stream, beside the exchange)
-__global__ void __launch_bounds__(BK_T) k_bucket_boundaries(const u64 *__restrict__ keys, long long n0, BucketArgs ba) { bk_rebalance_block(ba, keys, n0); }
+__global__ void __launch_bounds__(BK_T) k_bucket_boundaries(const u64 *__restrict__ keys, long long n0, BucketArgs ba) { if ((int)blockIdx.x < bk_boundary_blocks(ba)) bk_boundary_block(ba, keys, n0, (int)blockIdx.x, false); }      // launched with two blocks
 // stand-alone: for spawn lists that did not come out of k_spawn (the annihilation door) or heads launched without it
 __global__ void __launch_bounds__(BK_T) k_bucket_partition(const u64 *__restrict__ keys, long long n0, long long nch, u64 invalid_key, BucketArgs ba, int n_extra) {
-  if ((int)blockIdx.x < n_extra) { bk_rebalance_block(ba, keys, n0); return; }      // the boundary block, in front (as in k_spawn)
+  if ((int)blockIdx.x < n_extra) { bk_boundary_block(ba, keys, n0, (int)blockIdx.x, false); return; }      // the boundary blocks, in front (as in k_spawn)
   __shared__ u32 spl[BK_MAXB];
   __shared__ u32 wcnt[BK_T / 64][BK_MAXB];
   const long long blk = (long long)blockIdx.x - n_extra;

@@ -77,7 +77,10 @@ __device__ __forceinline__ long long bk_bound(const BucketArgs &ba, int b, long 
   return ba.kb ? (long long)ba.pos[b] : ((long long)b * n0) / ba.B;
 }
 // first resident position whose key is >= k (rkeys: key << 32 | index, ascending), looked for around `hint` first: the list
-// changes by a fraction of a percent from step to step, so a boundary found yesterday is within a few hundred places today
+// changes by a fraction of a percent from step to step, so a boundary found yesterday is within a few hundred places today.
+// A bisection, on purpose: a 16-ary search (15 probes a level in one round trip, three levels for the window) was built and
+// measured at 3 to 4 us a LEVEL on the MI355X -- 256 lanes x 15 scattered keys a level are bound by the loads, not by their
+// latency -- against 0.45 us a step here (profiles/boundary_chain_16ary.txt).
 __device__ __forceinline__ long long bk_lower_bound_near(const u64 *__restrict__ rkeys, long long n0, u32 k, long long hint) {
   const long long W = 384;
   long long lo = hint - W < 0 ? 0 : hint - W, hi = hint + W > n0 ? n0 : hint + W;
@@ -89,37 +92,61 @@ __device__ __forceinline__ long long bk_lower_bound_near(const u64 *__restrict__
   while (lo < hi) { const long long m = (lo + hi) >> 1; if ((u32)(rkeys[m] >> 32) < k) lo = m + 1; else hi = m; }
   return lo;
 }
-// One block of BK_T threads beside the spawning blocks of k_spawn: (1) where this step's boundaries lie in this step's resident
-// list; (2) the next boundaries: every bucket the same cost, if residents and spawns fall as they did when scount was taken,
-// evenly over the KEY range of each bucket of then.  (Evenly over its residents does not work: most spawns land on
+// Two blocks of BK_T threads beside the spawning blocks of k_spawn, which share no data (the second never reads today's pos).
+// As one block, with a prefix sum that fetched its terms from HBM eight at a time (8.4 us for 256 additions), they lived 20 us:
+// as long as the kernel.  Apart they are 5 and 11 us:
+// (1) bk_positions_block: where this step's boundaries lie in this step's resident list (a search around the hints);
+// (2) bk_next_block: the next boundaries: every bucket the same cost, if residents and spawns fall as they did when scount was
+// taken, evenly over the KEY range of each bucket of then.  (Evenly over its residents does not work: most spawns land on
 // determinants nobody occupies, whole key ranges of them, and die there by the initiator rule -- a bucket can hold 2000 spawns
 // in a range its 650 residents only line the edges of.)  If the new boundaries would overfill a block with residents, or leave
 // the first or the last bucket without any, equal-residents boundaries are written instead.
-__device__ __forceinline__ void bk_rebalance_block(const BucketArgs &ba, const u64 *__restrict__ rkeys, long long n0) {
-  __shared__ double s_pre[BK_REBAL_MAXB + 1]; __shared__ u32 s_pp[BK_REBAL_MAXB + 1], s_kk[BK_REBAL_MAXB + 1], s_kn[BK_REBAL_MAXB + 1], s_pn[BK_REBAL_MAXB + 1];
-  __shared__ int s_bad;
+__device__ __forceinline__ void bk_positions_block(const BucketArgs &ba, const u64 *__restrict__ rkeys, long long n0) {
+  const int B = ba.B;
+  for (int j = threadIdx.x; j <= B; j += BK_T)
+    ba.pos[j] = (j == 0) ? 0u : (j == B ? (u32)n0 : (u32)bk_lower_bound_near(rkeys, n0, ba.kb[j], ba.hint ? (long long)ba.hint[j] : n0 / 2));
+}
+__device__ __forceinline__ void bk_next_block(const BucketArgs &ba, const u64 *__restrict__ rkeys, long long n0, const bool stamp) {
+  __shared__ double s_pre[BK_REBAL_MAXB + 1], s_term[BK_REBAL_MAXB + 1];
+  __shared__ u32 s_pp[BK_REBAL_MAXB + 1], s_kk[BK_REBAL_MAXB + 1];
+  u32 *s_kn = (u32 *)s_term, *s_pn = s_kn + BK_REBAL_MAXB + 1;      // the terms are spent (behind a barrier) by the time the new boundaries are parked
   const int tid = threadIdx.x, B = ba.B;
-  if (tid == 0) s_bad = 0;
+  const bool prev = ba.kb_prev && ba.pos_prev;
   for (int j = tid; j <= B; j += BK_T) {
-    const bool inner = j > 0 && j < B;
-    if (ba.kb) ba.pos[j] = (j == 0) ? 0u : (j == B ? (u32)n0 : (u32)bk_lower_bound_near(rkeys, n0, ba.kb[j], ba.hint ? (long long)ba.hint[j] : n0 / 2));
-    if (ba.kb_out) {
-      // the boundaries of then, where they lay then: the residents they held are the ones the spawns were counted beside
-      long long pp = (j == 0) ? 0 : (j == B ? n0 : ((ba.kb_prev && ba.pos_prev) ? (long long)ba.pos_prev[j] : ((long long)j * n0) / B));
-      if (pp > n0) pp = n0;
-      s_pp[j] = (u32)pp;
-      s_kk[j] = (j == 0) ? 0u : (j == B ? (u32)(rkeys[n0 - 1] >> 32) + 1u : ((ba.kb_prev && ba.pos_prev) ? ba.kb_prev[j] : (u32)(rkeys[pp < n0 ? pp : n0 - 1] >> 32)));
-    }
-    (void)inner;
+    // Everything the block needs from HBM but the residents of the second search, in one round trip: no load hangs on j (every
+    // array holds B + 1 words), so none waits for another.
+    // The boundaries of then, where they lay then: the residents they held are the ones the spawns were counted beside.
+    long long pp = ((long long)j * n0) / B;      // (0 and n0 at the two ends, whatever pos_prev holds there)
+    const u32 sc = ba.scount[j], k_last = (u32)(rkeys[n0 - 1] >> 32);
+    u32 kk;
+    if (prev) { const u32 p = ba.pos_prev[j]; kk = ba.kb_prev[j]; if (j > 0 && j < B) pp = (long long)p; }
+    else kk = (u32)(rkeys[pp < n0 ? pp : n0 - 1] >> 32);
+    if (pp > n0) pp = n0;
+    s_pp[j] = (u32)pp;
+    s_kk[j] = (j == 0) ? 0u : (j == B ? k_last + 1u : kk);
+    s_term[j] = BK_REBAL_SPAWN_COST * (double)sc;
   }
-  if (!ba.kb_out) return;
   __syncthreads();
-  if (tid == 0) {                      // 256 additions beside a kernel that runs for tens of microseconds
-    double acc = 0.0;
-    for (int b = 0; b < B; b++) { s_pre[b] = acc; acc += (double)(s_pp[b + 1] - s_pp[b]) + BK_REBAL_SPAWN_COST * (double)ba.scount[b]; }
+  for (int b = tid; b < B; b += BK_T) s_term[b] = (double)(s_pp[b + 1] - s_pp[b]) + s_term[b];      // every bucket's cost, side by side
+  __syncthreads();
+  if (stamp) PROF(1);
+  if (tid == 0) {
+    // The prefix is added left to right by one thread: a parallel scan rounds some prefixes differently in the last bit, which is
+    // enough to move a boundary by a resident, and with it the grouping of the step's sums.  Eight terms leave LDS ahead of their
+    // adds, so that only the 256 fp64 additions are a chain.
+    double acc = 0.0; int b = 0;
+    for (; b + 8 <= B; b += 8) {
+      double t8[8];
+#pragma unroll
+      for (int q = 0; q < 8; q++) t8[q] = s_term[b + q];
+#pragma unroll
+      for (int q = 0; q < 8; q++) { s_pre[b + q] = acc; acc += t8[q]; }
+    }
+    for (; b < B; b++) { s_pre[b] = acc; acc += s_term[b]; }
     s_pre[B] = acc;
   }
   __syncthreads();
+  if (stamp) PROF(2);
   const double total = s_pre[B];
   for (int j = tid; j <= B; j += BK_T) {
     u32 kn = (j == 0) ? 0u : s_kk[B];
@@ -134,37 +161,43 @@ __device__ __forceinline__ void bk_rebalance_block(const BucketArgs &ba, const u
       const u32 p_lo = s_pp[lo], p_hi = s_pp[lo + 1], K_lo = s_kk[lo], K_hi = s_kk[lo + 1];
       const double d = (K_hi > K_lo) ? BK_REBAL_SPAWN_COST * (double)ba.scount[lo] / (double)(K_hi - K_lo) : 0.0;
       u32 a = p_lo, e = p_hi;           // residents [p_lo, a) are admitted, [e, p_hi) are not
+      u32 kp = 0, ke = 0;               // key(a - 1) once a has left p_lo, key(e) once e has left p_hi: the last probes on either side
       while (a < e) {
         const u32 m = (a + e) >> 1;
         const u32 km = (u32)(rkeys[m] >> 32);
         const double f = (double)(m - p_lo) + d * (double)(km > K_lo ? km - K_lo : 0u);
-        if (f <= r) a = m + 1; else e = m;
+        if (f <= r) { a = m + 1; kp = km; } else { e = m; ke = km; }
       }
       if (a == p_lo) kn = K_lo + (d > 0.0 ? (u32)(r / d) : 0u);                      // in front of the bucket's first resident
       else {
-        const u32 kp = (u32)(rkeys[a - 1] >> 32);
         const double f = (double)(a - 1 - p_lo) + d * (double)(kp > K_lo ? kp - K_lo : 0u);
         kn = kp + 1u + (d > 0.0 ? (u32)((r - f) / d) : 0u);
       }
-      const u32 cap_k = (a < p_hi) ? (u32)(rkeys[a] >> 32) : K_hi;                   // not past the first resident that was not admitted
+      const u32 cap_k = (a < p_hi) ? ke : K_hi;                                      // not past the first resident that was not admitted
       if (kn > cap_k) kn = cap_k;
       s_pn[j] = a;                       // kn lies in (key(a - 1), key(a)]: a is its place in today's list
     } else s_pn[j] = (j == 0) ? 0u : (u32)n0;
     s_kn[j] = kn;
   }
   __syncthreads();
-  for (int j = tid + 1; j < B; j += BK_T) if (s_kn[j] <= s_kn[j - 1] || s_pn[j] < s_pn[j - 1]) s_bad = 1;
-  __syncthreads();
+  if (stamp) PROF(3);
+  int mine = 0;
   for (int j = tid; j < B; j += BK_T) {
+    if (j > 0 && (s_kn[j] <= s_kn[j - 1] || s_pn[j] < s_pn[j - 1])) mine = 1;
     const u32 r = s_pn[j + 1] - s_pn[j];
-    if (r > (u32)BK_RESIDENTS_MAX || ((j == 0 || j == B - 1) && r == 0u)) s_bad = 1;
+    if (r > (u32)BK_RESIDENTS_MAX || ((j == 0 || j == B - 1) && r == 0u)) mine = 1;
   }
-  __syncthreads();
-  const bool bad = s_bad != 0;
+  const bool bad = __syncthreads_or(mine) != 0;
   for (int j = tid; j < B; j += BK_T) {
     ba.kb_out[j] = (j == 0) ? 0u : (bad ? (u32)(rkeys[((long long)j * n0) / B] >> 32) : s_kn[j]);
     if (ba.hint_out) ba.hint_out[j] = bad ? (u32)(((long long)j * n0) / B) : s_pn[j];
   }
+}
+// how many blocks the boundaries of a launch take, and the idx-th of them
+__host__ __device__ __forceinline__ int bk_boundary_blocks(const BucketArgs &ba) { return (ba.kb ? 1 : 0) + (ba.kb_out ? 1 : 0); }
+__device__ __forceinline__ void bk_boundary_block(const BucketArgs &ba, const u64 *__restrict__ rkeys, long long n0, int idx, const bool stamp) {
+  if (ba.kb && idx == 0) { if (stamp) PROF_KIND(PROF_BOUNDARIES); bk_positions_block(ba, rkeys, n0); }
+  else { if (stamp) PROF_KIND(PROF_BOUNDARIES_NEXT); bk_next_block(ba, rkeys, n0, stamp); }
 }
 
 // ------------------------------------------------------------------------------------------------ partition

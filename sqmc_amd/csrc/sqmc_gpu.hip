@@ -33,6 +33,7 @@
 #include "heatbath_device.h"
 #include "cauchy_device.h"
 #include "scan_sort.h"
+#include "spawn_prof.h"
 #include "bucket_partition.h"
 #include "hii_group.h"
 
@@ -1085,13 +1086,15 @@ static int enqueue_head(sqmc_gpu_ctx *c, const StepP &p, u64 step, long long n0,
   const long long nfree = dev_n ? M : M - n0;          // dev_n: nothing is known about the count but that it is >= 0
   const int spawn_fuse = (hb.B > 0 || spawn_fin.on || pp.n_imp > 0 || c->shard_y_ok || hq_blk > 0) ? 1 : 0;
   const size_t spawn_lds = std::max<size_t>(hb.B > 0 ? (size_t)BK_PART_LDS(hb.B) : 0, hq_blk > 0 ? (size_t)(TPB / 16) * bk_hii_terms_of(c->htab.nup, c->htab.ndn) * 8 : 0);
+  // the blocks in front of the spawning ones (k_spawn): final sums, one per H_ii queue, eight projector rows each, the boundaries' one or two
+  const int n_spare = (spawn_fin.on ? 1 : 0) + hq_blk + (pp.n_imp > 0 ? nblk(prj_row_waves(pp.n_imp), TPB / 64) : 0) + bk_boundary_blocks(hb);
   if (nfree > 0) {
     if (s0)
-      SPAWN_LAUNCH_EXT(spawn_kind(c), spawn_fuse, spawn_diag(c), dim3(nblk(nfree) + (spawn_fin.on ? 1 : 0) + hq_blk + (pp.n_imp > 0 ? nblk(pp.n_imp, TPB / 64) : 0) + ((hb.kb || hb.kb_out) ? 1 : 0)), dim3(TPB), spawn_lds, st, s0, s1, 0, c->dev, c->w, c->d_child_off, c->d_wchild,
-                            c->d_child_state, c->d_keys, c->d_vals, n0, M, p, c->rng_mode, c->seed64, step, c->invalid_key, (const DevScalars *)c->d_sc, c->d_mail, *cseq, c->pack, dev_n ? 1 : 0, oo, hb, spawn_fin, pp, (spawn_fin.on ? 1 : 0) + hq_blk + (pp.n_imp > 0 ? nblk(pp.n_imp, TPB / 64) : 0) + ((hb.kb || hb.kb_out) ? 1 : 0));
+      SPAWN_LAUNCH_EXT(spawn_kind(c), spawn_fuse, spawn_diag(c), dim3((unsigned)(nblk(nfree) + n_spare)), dim3(TPB), spawn_lds, st, s0, s1, 0, c->dev, c->w, c->d_child_off, c->d_wchild,
+                            c->d_child_state, c->d_keys, c->d_vals, n0, M, p, c->rng_mode, c->seed64, step, c->invalid_key, (const DevScalars *)c->d_sc, c->d_mail, *cseq, c->pack, dev_n ? 1 : 0, oo, hb, spawn_fin, pp, n_spare);
     else
-      SPAWN_LAUNCH(spawn_kind(c), spawn_fuse, spawn_diag(c), dim3(nblk(nfree) + (spawn_fin.on ? 1 : 0) + hq_blk + (pp.n_imp > 0 ? nblk(pp.n_imp, TPB / 64) : 0) + ((hb.kb || hb.kb_out) ? 1 : 0)), dim3(TPB), spawn_lds, st, c->dev, c->w, c->d_child_off, c->d_wchild, c->d_child_state, c->d_keys, c->d_vals,
-                         n0, M, p, c->rng_mode, c->seed64, step, c->invalid_key, (const DevScalars *)c->d_sc, c->d_mail, *cseq, c->pack, dev_n ? 1 : 0, oo, hb, spawn_fin, pp, (spawn_fin.on ? 1 : 0) + hq_blk + (pp.n_imp > 0 ? nblk(pp.n_imp, TPB / 64) : 0) + ((hb.kb || hb.kb_out) ? 1 : 0));
+      SPAWN_LAUNCH(spawn_kind(c), spawn_fuse, spawn_diag(c), dim3((unsigned)(nblk(nfree) + n_spare)), dim3(TPB), spawn_lds, st, c->dev, c->w, c->d_child_off, c->d_wchild, c->d_child_state, c->d_keys, c->d_vals,
+                         n0, M, p, c->rng_mode, c->seed64, step, c->invalid_key, (const DevScalars *)c->d_sc, c->d_mail, *cseq, c->pack, dev_n ? 1 : 0, oo, hb, spawn_fin, pp, n_spare);
   } else if (s0) { hipEventRecord(s0, st); hipEventRecord(s1, st); }
   HIPCHK(hipEventRecord(c->e_spawned, st)); c->spawned_valid = true;
   HIPCHK(hipGetLastError());
@@ -1222,7 +1225,7 @@ static int step_tail_impl(sqmc_gpu_ctx *c, const StepP &p_in, long long n0, long
             ba.kb = c->shard_ba.kb; ba.pos = c->shard_ba.pos; ba.hint = c->shard_ba.hint;
           } else if (!c->d_grow) {
             c->head_kb_use = choose_boundaries(c, B, n0, ba);
-            n_extra = (ba.kb || ba.kb_out) ? 1 : 0;
+            n_extra = bk_boundary_blocks(ba);
           } else c->head_kb_use = -1;
           c->shard_ba.B = 0;
           hipLaunchKernelGGL(k_bucket_partition, dim3((unsigned)(nsb + n_extra)), dim3(BK_T), 0, st, (const u64 *)c->d_keys, n0, nch, c->invalid_key, ba, n_extra);
@@ -1466,7 +1469,7 @@ static int step_tail_impl(sqmc_gpu_ctx *c, const StepP &p_in, long long n0, long
         rb.kb_prev = set_failed >= 0 ? c->d_bkb + set_failed * (BK_MAXB + 1) : (const u32 *)nullptr;
         rb.pos_prev = set_failed >= 0 ? c->d_bpos + c->scount_pos * (BK_MAXB + 1) : (const u32 *)nullptr;
         rb.kb_out = c->d_bkb + out * (BK_MAXB + 1); rb.hint_out = c->d_bhint + out * (BK_MAXB + 1);
-        hipLaunchKernelGGL(k_bucket_boundaries, dim3(1), dim3(BK_T), 0, st, (const u64 *)c->d_keys, n0, rb);
+        hipLaunchKernelGGL(k_bucket_boundaries, dim3(2), dim3(BK_T), 0, st, (const u64 *)c->d_keys, n0, rb);
         c->kb_B[0] = c->kb_B[1] = c->kb_B[2] = 0; c->kb_B[out] = B_failed; c->kb_next = out; learnt = true;
       } else { c->kb_B[0] = c->kb_B[1] = c->kb_B[2] = 0; c->kb_next = -1; }
       c->scount_B = 0; c->scount_buf = -1;

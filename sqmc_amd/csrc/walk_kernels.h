@@ -292,13 +292,6 @@ __device__ __forceinline__ void prj_row_product(const PrjPre &pp, int row) {
   }
   if (lane == 0) pp.y[row] = y;
 }
-#ifdef SPAWN_PROF
-__device__ unsigned long long g_prof[8 * 8192];
-#define PROF(K) do { if (threadIdx.x == 0 && blockIdx.x < 8192) g_prof[blockIdx.x * 8 + (K)] = wall_clock64(); } while (0)
-extern "C" int sqmc_gpu_debug_prof(unsigned long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_prof), sizeof(g_prof)); }
-#else
-#define PROF(K)
-#endif
 // Spawn diagnostics (sqmc_gpu_set_spawn_diagnostics): the reference's histograms of abs(weight_j)/tau = |H_ij| / p(i -> j) and its max / min
 // weight ratios (do_walk.f90:1420-1429, 3619-3661, add_walker 7603-7636).  One set of 64-bit words in HBM:
 //   [0, 4 NB)  counts: any walker | iwalk == 1 (slot 0) | singles | doubles      (NB = 10001 unit-wide bins, gen_hist more_tools.f90:5449-5469)
@@ -306,6 +299,7 @@ extern "C" int sqmc_gpu_debug_prof(unsigned long long *out) { return (int)hipMem
 //   then       smallest ratio, as the COMPLEMENT of its bit pattern (so that 0 means "none yet" in every word and the set starts as zeros), NaN count
 // The context keeps SDIAG_REPL such sets and a spawning block adds to set (block index mod SDIAG_REPL): a step's proposals crowd into a few
 // dozen bins, and adds to one word serialise in L2 however they are spread over wavefronts; k_sdiag_reduce folds the sets when they are read.
+__host__ __device__ __forceinline__ int prj_row_waves(int n_imp) { return (n_imp + 2) / 2; }      // wavefronts of k_spawn's spare blocks that multiply the projector's rows
 #define SDIAG_NB 10001
 #define SDIAG_MAX (4 * SDIAG_NB)
 #define SDIAG_MIN (SDIAG_MAX + 8)
@@ -384,17 +378,19 @@ __global__ void __launch_bounds__(TPB) k_spawn(ChemDev dev, WalkArr w, const u64
   // behind them they waited for the thousands of empty blocks a capacity-sized grid has, and the kernel for them -- 32 against
   // 20 us).  Steps whose child offsets came out of the bucket tail have no scan launch to carry the last step's final sums:
   // block 0 does them (nothing it touches is read by the spawning blocks).  The blocks behind it multiply the deterministic
-  // projector into last step's deterministic weights, one wavefront per row: the part of the projection that needs nothing
-  // the host still has to decide (E_T enters in the tail, bucket_kernels.h).  The last of them makes the next bucket boundaries.
+  // projector into last step's deterministic weights, two rows per wavefront: the part of the projection that needs nothing
+  // the host still has to decide (E_T enters in the tail, bucket_kernels.h).  The last two find and make the bucket boundaries.
   __shared__ ChemTab t;
   extern __shared__ u32 s_part[];      // BK_PART_LDS(B) bytes when the launch partitions (at least 16 x terms doubles when its spare blocks compute H_ii), none otherwise (large populations keep their occupancy)
   if (FUSE && (int)blockIdx.x < n_extra) {
     const int xb = (int)blockIdx.x;
-    if (fin.on && xb == 0) { finish_all(fin, const_cast<DevScalars *>(sc)); return; }
+    PROF(0);
+    if (fin.on && xb == 0) { PROF_KIND(PROF_FINAL_SUMS); finish_all(fin, const_cast<DevScalars *>(sc)); PROF(5); return; }
     if (n_on_device && sc->retry) return;
     int hb0 = xb - (fin.on ? 1 : 0);
-    if ((ba.kb || ba.kb_out) && xb == n_extra - 1) {      // the last spare block: bucket boundaries (bucket_partition.h)
-      bk_rebalance_block(ba, keys, n_on_device ? (long long)sc->nwalk : n0_arg);
+    if (xb >= n_extra - bk_boundary_blocks(ba)) {      // the last spare blocks: bucket boundaries, positions and next (bucket_partition.h)
+      bk_boundary_block(ba, keys, n_on_device ? (long long)sc->nwalk : n0_arg, xb - (n_extra - bk_boundary_blocks(ba)), true);
+      PROF_B(5);
       return;
     }
     if (hb0 < ba.hq_nblk) {
@@ -402,6 +398,7 @@ __global__ void __launch_bounds__(TPB) k_spawn(ChemDev dev, WalkArr w, const u64
       // (bucket_kernels.h).  One block per bucket, 16 lanes per determinant, terms in the reference's order -- a bucket creates 13 on
       // average at the bench size, so a block is through after one pass, well inside the spawning blocks' time.  Death/clone of THIS
       // step's tail reads the values.
+      PROF_KIND(PROF_HII_QUEUE);
       stage_tab(&t, dev.tab, dev.tab_words);
       __syncthreads();
       const int bkt = hb0, cnt = (int)ba.hq_cnt[bkt];
@@ -423,11 +420,20 @@ __global__ void __launch_bounds__(TPB) k_spawn(ChemDev dev, WalkArr w, const u64
           w.me[q0] = h_any(t, dev.integrals, u, dd, u, dd);
         }
       }
+      PROF_B(5);
       return;
     }
     hb0 -= ba.hq_nblk;
-    const int row = hb0 * (TPB / 64) + (int)(threadIdx.x >> 6);
-    if (pp.n_imp > 0 && row < pp.n_imp) prj_row_product(pp, row);
+    // Two rows a wavefront, w and n_imp - w: half as many spare blocks, so that at the bench size every block of the launch is
+    // resident at once (four a CU) and no spawning block waits for a spare one to end.  Row 0 (the first state's: it touches the
+    // whole deterministic space and takes as long as four others) has its wavefront to itself.
+    const int w = hb0 * (TPB / 64) + (int)(threadIdx.x >> 6), nw = prj_row_waves(pp.n_imp);
+    PROF_KIND(PROF_PRJ_ROWS);
+    if (pp.n_imp > 0 && w < nw) {
+      prj_row_product(pp, w);
+      if (w > 0 && pp.n_imp - w >= nw) prj_row_product(pp, pp.n_imp - w);
+    }
+    PROF_B(5);
     return;
   }
   if (n_on_device && sc->retry) return;                                 // see k_gate
@@ -435,7 +441,7 @@ __global__ void __launch_bounds__(TPB) k_spawn(ChemDev dev, WalkArr w, const u64
   const long long n0 = n_on_device ? (long long)sc->nwalk : n0_arg;     // pipelined head: launched before the host learnt the walker count
   // the grid covers the free capacity of the walker arrays; the number of children is read from
   // device memory so that the launch does not wait for the host to learn it
-  PROF(0);
+  PROF(0); PROF_KIND(PROF_SPAWNING);
   __shared__ u64 s_win[SPAWN_WIN];
   // short lists (ba.B > 0): the block also groups its children by key range for the bucket tail (bucket_kernels.h)
   const int pws = BK_PART_STRIDE(ba.B);

@@ -23,7 +23,7 @@ module sqmc_gpu_mod
   public :: sqmc_gpu_diag_update_batch, sqmc_gpu_hci_set_diag_update, sqmc_gpu_hci_connections_record
   public :: sqmc_gpu_hci_pt2_stochastic_prepare, sqmc_gpu_hci_pt2_stochastic_sample, sqmc_gpu_hci_pt2_stochastic_stats, sqmc_gpu_hci_pt2_stochastic_free
   public :: sqmc_gpu_set_spawn_diagnostics, sqmc_gpu_reset_spawn_diagnostics, sqmc_gpu_get_spawn_diagnostics
-  public :: sqmc_gpu_set_hubbardk_space_sym, sqmc_gpu_hubbardk_sym_images
+  public :: sqmc_gpu_set_hubbardk_space_sym, sqmc_gpu_hubbardk_sym_images, sqmc_gpu_debug_bucket_boundaries
   public :: sqmc_gpu_check
 
   integer(c_int), parameter, public :: SQMC_RNG_REPLAY = 0, SQMC_RNG_COUNTER = 1
@@ -167,6 +167,12 @@ module sqmc_gpu_mod
     ! H_aa of the PT2 stages: 0 from scratch (default), 1 / 2 the O(N) update on one lane / by lane groups
     integer(c_int) function sqmc_gpu_hci_set_diag_update(ctx, mode) bind(C, name='sqmc_gpu_hci_set_diag_update')
       import; type(c_ptr), value :: ctx; integer(c_int32_t), value :: mode
+    end function
+    ! test door of the bucket-boundary kernel; every array but keys may be c_null_ptr (include/sqmc_gpu.h says which go together)
+    integer(c_int) function sqmc_gpu_debug_bucket_boundaries(ctx, n0, keys, B, kb, hint, kb_prev, pos_prev, scount, pos, kb_out, hint_out) &
+        bind(C, name='sqmc_gpu_debug_bucket_boundaries')
+      import; type(c_ptr), value :: ctx; integer(c_int64_t), value :: n0; integer(c_int32_t), intent(in) :: keys(*); integer(c_int32_t), value :: B
+      type(c_ptr), value :: kb, hint, kb_prev, pos_prev, scount, pos, kb_out, hint_out
     end function
     integer(c_int) function sqmc_gpu_hci_connections_record(ctx, n_ref, ref_up, ref_dn, coeffs, eps, diag_mode, slice, n_slices, out_n, out_up, out_dn, &
         out_num, out_den, out_old_diag, out_pqrs) bind(C, name='sqmc_gpu_hci_connections_record')
