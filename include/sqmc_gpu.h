@@ -97,8 +97,13 @@ int sqmc_gpu_init_heg(const sqmc_heg_cfg *cfg, sqmc_gpu_ctx **out);
  * operator pair.  The energy estimator is the library's usual one over a determinant-list trial
  * wavefunction (the 'else' branch of energy_pieces_hubbard, 4514-4527, as a C(T) table); the
  * Gutzwiller/Slater trial functions of hubbard.f90 are host-side code outside this path.
+ * The connection generator (sqmc_gpu_hci_connections, _slice, sqmc_gpu_hci_pt2) is find_connected_dets_hubbard
+ * (hubbard.f90:5306-5457): sites ascending, at each site the up electron before the dn electron, per electron LEFT, RIGHT, UP,
+ * DOWN, a hop where the neighbour is allowed and empty in that spin's string; the source itself in slot 0 (the reference puts it
+ * last).  A hop is kept when |H c| > eps: every |H| is |t|, so the screen selects on |c| alone, and t = 0 leaves the own slot only.
  * A periodic direction of length 2 is refused: the reference's connected list counts that bond
- * twice while hamiltonian_hubbard counts it once. */
+ * twice while hamiltonian_hubbard counts it once.  On such a context the diagonal-update record, modes and batch, the active-space
+ * masks, the stochastic-PT plan, hf_to_psit and the heat-bath and Cauchy-Schwarz set-up return SQMC_ERR_UNSUPPORTED. */
 typedef struct {
   int32_t l_x, l_y, pbc, nup, ndn;
   double t, U;
@@ -496,7 +501,9 @@ int sqmc_gpu_propose_batch(sqmc_gpu_ctx *ctx, int64_t n, double tau, const uint6
  * for n_ref reference dets with coefficients coeffs, the connections that pass the screen at eps/|c|, per class as the
  * reference has it: single excitations with |H| >= eps/|c| (chemistry.f90:6956, a tie is kept), chemistry doubles with
  * |H| > eps/|c| (chemistry.f90:7042, a tie is dropped; none when eps/|c| > max_double, :6995), HEG doubles with |H| > eps/|c|
- * (heg.f90:2608, 2629); H is the raw element, before the time-reversal factors.  The reference det itself is included, except
+ * (heg.f90:2608, 2629), the hops of hubbard2 (find_connected_dets_hubbard, hubbard.f90:5306-5457) and the connections of hubbardk
+ * (find_connected_dets_hubbard_k, :5462) with |H c| > eps (the product itself is compared; a tie is dropped); H is the raw element,
+ * before the time-reversal factors.  The reference det itself is included, except
  * that a det with c == 0 contributes nothing, its own slot included (the generator is not called for it, semistoch.f90:1762,
  * 1798, 1854, 1891).  Sorted by (up,dn), duplicates merged:
  * e_mix_num = sum_j H_ij c_j, e_mix_den = c_i on the reference determinants, else 0
@@ -566,7 +573,7 @@ int sqmc_gpu_hci_connections_record(sqmc_gpu_ctx *ctx, int64_t n_ref, const uint
  * delta_e = sum_a (sum_i H_ai c_i)^2 / (E_var - H_aa) over the connected determinants outside the variational space, the inner
  * sum screened by |H_ai c_i| >= eps_pt; n_connections = connected determinants visited (the reference prints it).  Everything
  * stays on the device; n_slices > 1 does the connected space in parts of the determinant range.  Needs sqmc_gpu_set_hb_tables
- * (chem) like the generator.  For a time-symmetrised wavefunction pass the determinant-basis expansion, as the reference does
+ * (chem) like the generator; heg, hubbard2 and hubbardk (without space_sym) contexts need nothing more.  For a time-symmetrised wavefunction pass the determinant-basis expansion, as the reference does
  * (convert_time_symmetrized_to_dets, hci.f90:4365-4564) on a context initialised with time_sym = 0. */
 int sqmc_gpu_hci_pt2(sqmc_gpu_ctx *ctx, int64_t n_var, const uint64_t *var_up, const uint64_t *var_dn, const double *coeffs, double e_var,
                      double eps_pt, int32_t n_slices, double *delta_e, int64_t *n_connections);
@@ -578,7 +585,7 @@ int sqmc_gpu_hci_pt2(sqmc_gpu_ctx *ctx, int64_t n_var, const uint64_t *var_up, c
  * prepare (hci.f90:1373-1436): uploads the variational wavefunction once -- determinants, coefficients, their sorted ranks -- and
  * owns the work buffers, which are reused from sample to sample and grow only when a sample has more raw connections than any before
  * it.  The list must be sorted by (up, dn) without repeats (hci.f90:1373-1380: an unsorted one is refused); n_mc >= 2.  Chemistry
- * (sqmc_gpu_set_hb_tables first) and HEG; hubbard2 is refused as the generator refuses it.  p_i = |c_i| / sum |c|.
+ * (sqmc_gpu_set_hb_tables first) and HEG; the plan is not built for hubbard2 or hubbardk (refused).  p_i = |c_i| / sum |c|.
  * The plan borrows ctx: free it before sqmc_gpu_finalize.  Active-space masks (sqmc_gpu_hci_set_active_space) are generator
  * state of ctx and apply to every sample as they stand when it runs. */
 typedef struct sqmc_pt2s_plan sqmc_pt2s_plan;

@@ -384,7 +384,6 @@ static int hci_connections_impl(sqmc_gpu_ctx *c, int64_t n_ref, const uint64_t *
     key_lo = (u64)(span * slice); key_hi = (slice == n_slices - 1) ? (~0ull - 1ull) : (u64)(span * (slice + 1));
   }
   if (c->htab.sys_type == 0 && !c->dev.hb_r) return fail(SQMC_ERR_BAD_ARG, "heat-bath tables not set (sqmc_gpu_set_hb_tables)");
-  if (c->htab.sys_type == 2) return fail(SQMC_ERR_UNSUPPORTED, "connection generation for hubbard2 is the host's 4*nelec neighbour list (find_connected_dets_hubbard); no heat-bath screening applies");
   if (c->htab.sys_type == 1 && c->htab.heg_nmax > 4) return fail(SQMC_ERR_UNSUPPORTED, "HEG connections: plane-wave index beyond +-4");
   *out_n = 0;
   if (n_ref <= 0) return SQMC_OK;
@@ -512,7 +511,7 @@ int sqmc_gpu_hci_connections_slice(sqmc_gpu_ctx *c, int64_t n_ref, const uint64_
 int sqmc_gpu_diag_update_batch(sqmc_gpu_ctx *c, int64_t n, const double *old_diag, const int32_t *pqrs, const uint64_t *new_up, const uint64_t *new_dn,
                                int32_t form, double *new_diag) {
   if (!c) return fail(SQMC_ERR_BAD_ARG, "null ctx");
-  if (c->htab.sys_type == 2) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_diag_update_batch: hubbard2 has no heat-bath generator and no diagonal update");
+  if (c->htab.sys_type == 2) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_diag_update_batch: hubbard2 has no diagonal update (its H_ii is U times the number of doubly occupied sites)");
   if (c->htab.sys_type == 3) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_diag_update_batch: hubbardk has no diagonal update (its H_ii is a sum of nup + ndn orbital energies)");
   if (c->htab.time_sym) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_diag_update_batch: a determinant-basis formula; run PT2 in the determinant basis on a context with time_sym = 0");
   if (form != 0 && form != 1) return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_diag_update_batch: form must be 0 (one lane, reference order) or 1 (lane group)");
@@ -736,7 +735,7 @@ int sqmc_gpu_hci_pt2_stochastic_prepare(sqmc_gpu_ctx *c, int64_t n_var, const ui
   *plan = nullptr;
   if (n_mc < 2) return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_hci_pt2_stochastic_prepare: n_mc must be at least 2 (the estimator divides by n_mc (n_mc - 1))");
   if (n_var >= (1ll << 31)) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_hci_pt2_stochastic_prepare: more than 2^31 variational determinants");
-  if (c->htab.sys_type == 2) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_hci_pt2_stochastic_prepare: hubbard2 has no heat-bath connection generator (find_connected_dets_hubbard is the host's)");
+  if (c->htab.sys_type == 2) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_hci_pt2_stochastic_prepare: the stochastic PT plan is not built for hubbard2");
   if (c->htab.sys_type == 3) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_hci_pt2_stochastic_prepare: the stochastic PT plan is not built for hubbardk");
   if (c->htab.sys_type == 0 && !c->dev.hb_r) return fail(SQMC_ERR_BAD_ARG, "heat-bath tables not set (sqmc_gpu_set_hb_tables)");
   if (c->htab.sys_type == 1 && c->htab.heg_nmax > 4) return fail(SQMC_ERR_UNSUPPORTED, "HEG connections: plane-wave index beyond +-4");

@@ -109,6 +109,50 @@ __device__ __noinline__ void hci_fill_hubbardk_sym(const ChemTab &t, u64 up, u64
 #pragma nounroll
   for (u64 k = 0; k < cnt; k++) { onum[k] = (n2i > 0) ? (t.hk_ubyn * (onum[k] / norm_i)) * c : 0.0; oden[k] = den; }      // (a source without a state in the sector: elements 0, as hamiltonian_hubbard_k_space_sym has them)
 }
+// hubbard2 (find_connected_dets_hubbard, hubbard.f90:5306-5457): sites ascending, at each site the up electron before the dn electron, for each
+// electron the four directions in hub_nbr's order (LEFT, RIGHT, UP, DOWN) -- the "generation order" of diag_mode 2; a hop exists when the
+// neighbour is allowed and empty in that spin's string.  The reference puts the source last; here it is slot 0, as for every system.  At most
+// 4 nelec hops, no two to the same child (the set-up refuses a periodic direction of length 2).  Every |H| is |t|, so the screen |H c| > eps
+// (strict, on the product) keeps all of a source's hops or none, and the caller makes it.  Two out-of-line calls as for hubbardk:
+// hci_gen_hubbard counts the hops and, given ou / od, writes the children (a slice selects on the child's det_key; the counting pass and the
+// writing pass make the same decisions); hci_fill_hubbard then writes h_hubbard's own value for the pair times c, and e_mix_den.
+__device__ __noinline__ u64 hci_gen_hubbard(const ChemTab &t, const u64 *binom, u64 n_dn_strings, u64 up, u64 dn, u64 *ou, u64 *od, u64 key_lo, u64 key_hi) {
+  const bool sliced = !(key_lo == 0 && key_hi == ~0ull);
+  u64 cnt = 0;
+#pragma nounroll
+  for (u64 e = up | dn; e; e &= e - 1) {
+    const int site = ctz64(e) + 1;
+#pragma nounroll
+    for (int sp = 0; sp < 2; sp++) {
+      const u64 cfg = sp ? dn : up;
+      if (!((cfg >> (site - 1)) & 1)) continue;
+#pragma nounroll
+      for (int k = 0; k < 4; k++) {
+        const int nb = t.hub_nbr[site][k];
+        if (!nb || ((cfg >> (nb - 1)) & 1)) continue;
+        const u64 nc = (cfg & ~bit64(site - 1)) | bit64(nb - 1);
+        const u64 nu = sp ? up : nc, nd = sp ? nc : dn;
+        if (sliced) {                     // det_key, one electron at a time, as hci_gen_hubbardk
+          u64 ru = 0, rd = 0; int j = 1;
+#pragma nounroll
+          for (u64 d = nu; d; d &= d - 1, j++) ru += binom[ctz64(d) * SQ_BINOM_STRIDE + j];
+          j = 1;
+#pragma nounroll
+          for (u64 d = nd; d; d &= d - 1, j++) rd += binom[ctz64(d) * SQ_BINOM_STRIDE + j];
+          const u64 kk = ru * n_dn_strings + rd;
+          if (!(kk >= key_lo && kk < key_hi)) continue;
+        }
+        if (ou) { ou[cnt] = nu; od[cnt] = nd; }      // null in the counting pass
+        cnt++;
+      }
+    }
+  }
+  return cnt;
+}
+__device__ __noinline__ void hci_fill_hubbard(const ChemTab &t, u64 up, u64 dn, double c, double den, const u64 *ou, const u64 *od, double *onum, double *oden, u64 cnt) {
+#pragma nounroll
+  for (u64 k = 0; k < cnt; k++) { onum[k] = h_hubbard(t, up, dn, ou[k], od[k]) * c; oden[k] = den; }
+}
 template <bool REC>
 __global__ void __launch_bounds__(TPB) k_hci_gen(ChemDev dev, const u64 *__restrict__ rup, const u64 *__restrict__ rdn, const double *__restrict__ coef,
                                                  double eps_var, int diag_mode, long long n_ref, int pass, u64 *__restrict__ counts,
@@ -179,6 +223,16 @@ __global__ void __launch_bounds__(TPB) k_hci_gen(ChemDev dev, const u64 *__restr
           }
         }
       }
+    }
+    if (!pass) counts[i] = cnt;
+    return;
+  }
+  if (t.sys_type == 2) {
+    if (t.hub_t != 0.0 && fabs(t.hub_t * c) > eps_var) {      // |H c| > eps, with the one |H| there is; t == 0: no hops at all
+      const u64 at = base + cnt;
+      const u64 m = hci_gen_hubbard(t, dev.binom, dev.n_dn_strings, up, dn, pass ? ou + at : nullptr, pass ? od + at : nullptr, key_lo, key_hi);
+      if (pass) hci_fill_hubbard(t, up, dn, c, (diag_mode == 2) ? (double)i : 0.0, ou + at, od + at, onum + at, oden + at, m);
+      cnt += m;
     }
     if (!pass) counts[i] = cnt;
     return;

@@ -51,7 +51,7 @@ module sqmc_gpu_mod
     integer(c_int64_t) :: mwalk
   end type
 
-  type, bind(C) :: sqmc_hubbard_cfg    ! hamiltonian_type 'hubbard2': the scalars of read_hubbard
+  type, bind(C) :: sqmc_hubbard_cfg    ! hamiltonian_type 'hubbard2': the scalars of read_hubbard (walk, sqmc_gpu_hci_connections(_slice), sqmc_gpu_hci_pt2)
     integer(c_int32_t) :: l_x, l_y, pbc, nup, ndn
     real(c_double) :: t, U
     integer(c_int32_t) :: rng_mode
@@ -188,7 +188,8 @@ module sqmc_gpu_mod
       real(c_double), intent(out) :: delta_e; integer(c_int64_t), intent(out) :: n_connections
     end function
     ! second_order_pt_alias (hci.f90:1314-1660): the variational wavefunction and the work buffers stay on the device (prepare),
-    ! one call per sample with the merged draws (0-based ids, ascending, and their counts), free at the end
+    ! one call per sample with the merged draws (0-based ids, ascending, and their counts), free at the end; chem and heg contexts
+    ! (hubbard2 and hubbardk are refused)
     integer(c_int) function sqmc_gpu_hci_pt2_stochastic_prepare(ctx, n_var, var_up, var_dn, coeffs, e_var, eps_pt, eps_pt_big, n_mc, plan) &
         bind(C, name='sqmc_gpu_hci_pt2_stochastic_prepare')
       import; type(c_ptr), value :: ctx; integer(c_int64_t), value :: n_var; integer(c_int64_t), intent(in) :: var_up(*), var_dn(*)
@@ -387,6 +388,8 @@ module sqmc_gpu_mod
       integer(c_int64_t), intent(in) :: up(*), dn(*); integer(c_int32_t), intent(in) :: seeds(*)
       integer(c_int64_t), intent(out) :: ju(*), jd(*); real(c_double), intent(out) :: weight_j(*); integer(c_int32_t), intent(out) :: seeds_after(*)
     end function
+    ! find_doubly_excited with the system's generator: find_important_connected_dets_chem / _heg, find_connected_dets_hubbard
+    ! ('hubbard2': the hops in the reference's order, the source in slot 0, |H c| > eps) and find_connected_dets_hubbard_k ('hubbardk')
     integer(c_int) function sqmc_gpu_hci_connections(ctx, n_ref, ref_up, ref_dn, coeffs, eps, diag_mode, out_n, out_up, out_dn, out_num, out_den) &
         bind(C, name='sqmc_gpu_hci_connections')
       import; type(c_ptr), value :: ctx; integer(c_int64_t), value :: n_ref; integer(c_int64_t), intent(in) :: ref_up(*), ref_dn(*)

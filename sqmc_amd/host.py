@@ -743,6 +743,8 @@ def hci_variational(host, g, eps_var, eps_sched=(), n_states=1, max_iters=50, lo
     (hci.f90:865-1040): every piece that scales with the number of determinants runs on the
     GPU -- eps-screened connection generation + dedup (sqmc_gpu_hci_connections), sparse
     Hamiltonian (sqmc_gpu_build_sparse_ham), Davidson matvec (sqmc_gpu_spmv_apply).
+    Only hf_up / hf_dn of the host are read, so it also runs for HubbardHost with a hubbard2 context: every |H_ij| is |t| there,
+    and a determinant brings in all of its hops once |t c| > eps.
     Returns (up, dn, coeffs[n, n_states], energies, history of ndets)."""
     sched = list(eps_sched) + [eps_var]
     up = np.array([host.hf_up], np.uint64); dn = np.array([host.hf_dn], np.uint64)
@@ -1208,8 +1210,31 @@ class HubbardHost:
             raise ValueError("the hubbard context has the one proposal of its system (Cauchy-Schwarz is chemistry only)")
         return GpuChem.hubbard(self.l_x, self.l_y, self.pbc, self.nup, self.ndn, self.t, self.U, **kw)
 
-    def connected(self, up, dn):
-        """the determinant and its nearest-neighbour hops (find_connected_dets_hubbard, hubbard.f90:5306-5457), unique, sorted"""
+    def _with_ctx(self, g, fn):
+        if g is not None:
+            return fn(g)
+        g = self.gpu()
+        try:
+            return fn(g)
+        finally:
+            g.close()
+
+    def _check_t(self):
+        if not abs(self.t) > 1e-290:
+            raise ValueError("HubbardHost needs t != 0 here: every connection is an element -+t, and the device generator finds them by screening on it")
+
+    def connected(self, up, dn, g=None):
+        """the determinant and its nearest-neighbour hops, from the device generator (find_connected_dets_hubbard, hubbard.f90:5306-5457),
+        unique, sorted.  g: a context to use; without one a context is opened for the call."""
+        self._check_t()
+
+        def run(g):
+            cu, cd, _, _ = g.hci_connections([up], [dn], [1.0], 1e-300)
+            return cu, cd
+        return self._with_ctx(g, run)
+
+    def _connected_host(self, up, dn):
+        """connected() as a Python loop over sites and neighbours: the yardstick of the device path"""
         out = {(up, dn)}
         for site in range(1, self.norb + 1):
             for is_up in (True, False):
@@ -1226,13 +1251,32 @@ class HubbardHost:
     def spectral_range_bound(self):
         return self.U * (min(self.nup, self.ndn) - max(0, self.nelec - self.norb)) + 4.0 * abs(self.t) * self.nelec
 
-    def first_order_space(self, n_levels=2):
+    def first_order_space(self, n_levels=2, g=None):
+        """the start determinant and everything within n_levels hops of it, unique, sorted: one generator call per level"""
+        self._check_t()
+
+        def run(g):
+            up, dn = np.array([self.hf_up], np.uint64), np.array([self.hf_dn], np.uint64)
+            fu, fd = up, dn
+            for _ in range(n_levels):
+                cu, cd, _, _ = g.hci_connections(fu, fd, np.ones(len(fu)), 1e-300)
+                new = ~_dets_in(cu, cd, up, dn)
+                if not np.any(new):
+                    break
+                fu, fd = cu[new], cd[new]
+                up, dn = np.concatenate((up, fu)), np.concatenate((dn, fd))
+                o = sort_dets(up, dn)
+                up, dn = up[o], dn[o]
+            return up, dn
+        return self._with_ctx(g, run)
+
+    def _first_order_space_host(self, n_levels=2):
         seen = {(self.hf_up, self.hf_dn)}
         frontier = [(self.hf_up, self.hf_dn)]
         for _ in range(n_levels):
             nxt = []
             for (a, b) in frontier:
-                cu, cd = self.connected(a, b)
+                cu, cd = self._connected_host(a, b)
                 for k in zip(cu.tolist(), cd.tolist()):
                     if k not in seen:
                         seen.add(k); nxt.append(k)
@@ -1240,9 +1284,9 @@ class HubbardHost:
         keys = sorted(seen)
         return np.array([k[0] for k in keys], np.uint64), np.array([k[1] for k in keys], np.uint64)
 
-    def setup_walk(self, g, n_truncate_trial_wf=20, size_deterministic=500, tau_multiplier=0.5, n_levels=2):
+    def _trial_and_projector(self, g, up, dn, n_truncate_trial_wf, size_deterministic, tau_multiplier):
+        """Psi_T, the deterministic space and its projector from the lowest state of H among (up, dn): what the two set-ups share"""
         s = WalkSetup()
-        up, dn = self.first_order_space(n_levels)
         w, X, _ = lowest_state(g, up, dn)
         c = X[:, 0]
         if c[np.argmax(np.abs(c))] < 0:
@@ -1257,10 +1301,25 @@ class HubbardHost:
         s.tau, s.e_var = tau_multiplier / self.spectral_range_bound(), float(w[0])
         pc, pi_, pv = g.build_sparse_ham(s.imp_up, s.imp_dn)
         s.prj_counts, s.prj_indices, s.prj_values = pc, pi_, -s.tau * pv
+        return s
+
+    def setup_walk(self, g, n_truncate_trial_wf=20, size_deterministic=500, tau_multiplier=0.5, n_levels=2):
+        """Psi_T, C(T) and the deterministic space: the first-order space and C(T) from the device generator, one call per level and
+        one for C(T), as setup_walk does for chemistry.  Bit for bit what _setup_walk_host builds."""
+        s = self._trial_and_projector(g, *self.first_order_space(n_levels, g), n_truncate_trial_wf, size_deterministic, tau_multiplier)
+        s.ct_up, s.ct_dn, s.ct_num, s.ct_den = g.hci_connections(s.psi_up, s.psi_dn, s.psi_c, 1e-300, diag_mode=1)
+        s.e_trial0 = float(np.dot(s.ct_num, s.ct_den) / np.dot(s.ct_den, s.ct_den))
+        return s
+
+    def _setup_walk_host(self, g, n_truncate_trial_wf=20, size_deterministic=500, tau_multiplier=0.5, n_levels=2):
+        """setup_walk with the first-order space and C(T) from Python loops (one hamiltonian_batch call per Psi_T determinant): the
+        construction the device path replaced, kept as its yardstick"""
+        s = self._trial_and_projector(g, *self._first_order_space_host(n_levels), n_truncate_trial_wf, size_deterministic, tau_multiplier)
+        n_t = len(s.psi_up)
         acc = {}
         psi_index = {(int(a), int(b)): k for k, (a, b) in enumerate(zip(s.psi_up, s.psi_dn))}
         for j in range(n_t):
-            cu, cd = self.connected(int(s.psi_up[j]), int(s.psi_dn[j]))
+            cu, cd = self._connected_host(int(s.psi_up[j]), int(s.psi_dn[j]))
             h = g.hamiltonian_batch(cu, cd, np.full(len(cu), s.psi_up[j]), np.full(len(cu), s.psi_dn[j]))
             for a, b, v in zip(cu.tolist(), cd.tolist(), h.tolist()):
                 acc[(a, b)] = acc.get((a, b), 0.0) + v * s.psi_c[j]
