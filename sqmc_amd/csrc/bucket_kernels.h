@@ -13,8 +13,8 @@
 //                        equalise residents + spawns per bucket, remade every step from the last tail's counts
 //                        (bk_next_block, bucket_partition.h).
 //   k_anneal_bucket      one block per bucket: gathers its children from every partition block (two dependent loads), sorts
-//                        them in LDS -- one stable counting pass on the GAP between residents a child falls into, then a
-//                        ranking inside the gap: the order of merge_sort2_up_dn (do_walk.f90:5411-5614), residents first on
+//                        them in LDS -- one counting pass on the GAP between residents a child falls into, then a
+//                        ranking inside the gap by (key, slot): the order of merge_sort2_up_dn (do_walk.f90:5411-5614), residents first on
 //                        equal keys, spawns in creation order --, folds every run of equal determinants with the rules of
 //                        merge_original_with_spawned2 (5866-6083), rounds small weights (reduce_my_walker, 7196-7254), and
 //                        compacts into the other walker buffer through one decoupled look-back over the buckets --
@@ -182,6 +182,9 @@ __global__ void __launch_bounds__(BK_AT, BK_PER_CU * (BK_AT / 64) / 4) k_anneal_
   const bool pre = ba.kb != nullptr && B <= BK_REBAL_MAXB;
   if (tid == 0) { s_tile = atomicAdd(ba.ticket, 1u); s_hqn = 0; }
   if (pre) for (int j = tid; j <= B; j += BK_AT) { s_bpos[j] = ba.pos[j]; s_bkb[j] = ba.kb[j]; }
+  u32 *gcnt = (u32 *)s_w;                                 // the gap sort's counters, one per gap: the weights arrive behind the sort.  Zeroed while the ticket is in flight
+  static_assert(BK_CAP_T * 2 >= 1024, "the gap counters fit the idle weights");
+  for (int d = tid; d < 1024; d += BK_AT) gcnt[d] = 0;
   __syncthreads();
   const int b = (int)s_tile;
   const long long r_lo = pre ? (b <= 0 ? 0ll : (b >= B ? n0 : (long long)s_bpos[b])) : bk_bound(ba, b, n0);
@@ -259,68 +262,54 @@ __global__ void __launch_bounds__(BK_AT, BK_PER_CU * (BK_AT / 64) / 4) k_anneal_
   __syncthreads();
   BPROF(2); BPROF_VAL(12, S); BPROF_VAL(13, R);
   if (tid == 0 && ba.scount) { ba.scount[b] = (u32)S; if (b == 0) ba.scount[B] = (u32)n0; }
-  // ---- sort of the spawn words.  Short resident lists (always, at the sizes the host picks): ONE stable counting pass on the GAP of
+  // ---- sort of the spawn words.  Short resident lists (always, at the sizes the host picks): ONE counting pass on the GAP of
   //      a spawn -- the number of residents with key <= its own, found by binary search -- then every spawn ranks itself among the
-  //      spawns of its gap by (key, creation order).  A gap holds a handful of spawns (those between two neighbouring residents), or
-  //      many with one key (the heavy determinants: the loop below reads LDS at one address per step, a broadcast).  The time does
-  //      not depend on how wide the bucket's key range is (the key-digit sort took 2-4 passes), and the gap IS the merge position.
+  //      spawns of its gap by its whole word, (key, slot).  The counting pass is NOT stable and need not be: a slot occurs once, so
+  //      the words are distinct, the rank inside the gap is total, and a word's final place is gst[gap] + #(smaller words of the gap)
+  //      in whatever order the pass left the gap.  So the pass is one histogram over the gaps (one counter each), whose atomic add
+  //      hands every spawn a free place in its gap; spawn, gap and place stay in registers across the scan of the counters.
+  //      One add per spawn, also where a heavy determinant sends hundreds of spawns to ONE counter: issuing the add once per group
+  //      of equal gaps of a wavefront (ballot match, the first lane adds the group's size) was built and measured slower on both
+  //      bench systems, the 4x4 Hubbard lattice with its 10^3 spawns on the Neel state included.  A gap holds a
+  //      handful of spawns (those between two neighbouring residents), or many with one key (the heavy determinants: the ranking
+  //      loop reads LDS at one address per step, a broadcast).  The time does not depend on how wide the bucket's key range is
+  //      (the key-digit sort took 2-4 passes), and the gap IS the merge position.
   u64 *sa = sw, *sb = sw2;
   const bool gap_sort = R <= 1023;
   unsigned short *gs = (unsigned short *)m2s, *gst = gs + BK_CAP_S;     // gap of the spawn at a sorted position; first sorted position of a gap (R + 2 entries) -- m2s is idle until the merged order is written
   static_assert((BK_CAP_S + 1026) * 2 <= BK_CAP_T * 4, "gap tables fit the merged-order array");
   if (gap_sort) {
-    unsigned short *gp = s_hq;                            // gap by creation order (the H_ii queue is idle until the compaction)
-    bk_cnt_t(*wcnt)[1024] = (bk_cnt_t(*)[1024])scratch;
-    const u64 lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    const int chunk = ((S + BK_AT - 1) / BK_AT) * 64;
-    for (int d = tid; d < BK_SCR_CNT; d += BK_AT) scratch[d] = 0;
-    for (int j = tid; j < S; j += BK_AT) {
-      const u32 k = (u32)(sa[j] >> 32);
-      int lo = 0, hi = R;
-      while (lo < hi) { const int mid = (lo + hi) >> 1; if (rk[mid] <= k) lo = mid + 1; else hi = mid; }
-      gp[j] = (unsigned short)lo;
-    }
-    __syncthreads();
-    {
-      const int beg = wv * chunk, end = (beg + chunk < S) ? beg + chunk : S;
-      for (int base = beg; base < end; base += 64) {
-        const int idx = base + lane; const bool valid = idx < end;
-        const u32 dig = valid ? (u32)gp[idx] : 0u;
-        u64 same = __ballot(valid);
+    u64 wd_[BK_PER_S]; u32 gp_[BK_PER_S], pl_[BK_PER_S];
 #pragma unroll
-        for (int q = 0; q < 10; q++) { const u64 m = __ballot((dig >> q) & 1); same &= ((dig >> q) & 1) ? m : ~m; }
-        const u32 rank = (u32)__popcll(same & lt), cnt = (u32)__popcll(same);
-        u32 prev = 0;
-        if (valid) prev = wcnt[wv][dig];
-        __builtin_amdgcn_wave_barrier();
-        if (valid && rank == 0) wcnt[wv][dig] = (bk_cnt_t)(prev + cnt);
-        __builtin_amdgcn_wave_barrier();
-        if (valid) rnk[idx] = (unsigned short)(prev + rank);
+    for (int q = 0; q < BK_PER_S; q++) {
+      const int j = tid + q * BK_AT;
+      wd_[q] = 0; gp_[q] = 0; pl_[q] = 0;
+      if (j < S) {
+        wd_[q] = sa[j];
+        const u32 k = (u32)(wd_[q] >> 32);
+        int lo = 0, hi = R;
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (rk[mid] <= k) lo = mid + 1; else hi = mid; }
+        gp_[q] = (u32)lo; pl_[q] = atomicAdd(&gcnt[lo], 1u);
       }
     }
     __syncthreads();
-    {   // (BK_DIG consecutive digits per thread: the first 1024 / BK_DIG threads cover the 1024 counters of a wave, the others hold nothing)
+    {   // first sorted position of every gap (BK_DIG consecutive gaps per thread: the first 1024 / BK_DIG threads cover the counters, the others hold nothing)
       u32 t2[BK_DIG]; u64 sum = 0;
 #pragma unroll
-      for (int q = 0; q < BK_DIG; q++) { const int d = tid * BK_DIG + q; u32 s2 = 0; if (d < 1024) for (int v = 0; v < BK_AT / 64; v++) s2 += wcnt[v][d]; t2[q] = s2; sum += s2; }
+      for (int q = 0; q < BK_DIG; q++) { const int d = tid * BK_DIG + q; t2[q] = (d <= R) ? gcnt[d] : 0u; sum += t2[q]; }
       u64 tt; u32 ex = (u32)bk_block_excl_scan(sum, &tt);
 #pragma unroll
-      for (int q = 0; q < BK_DIG; q++) {
-        const int d = tid * BK_DIG + q; u32 a2 = ex;
-        if (d <= R) gst[d] = (unsigned short)ex;
-        if (d < 1024) for (int v = 0; v < BK_AT / 64; v++) { const u32 cn = wcnt[v][d]; wcnt[v][d] = (bk_cnt_t)a2; a2 += cn; }
-        ex += t2[q];
-      }
+      for (int q = 0; q < BK_DIG; q++) { const int d = tid * BK_DIG + q; if (d <= R) gst[d] = (unsigned short)ex; ex += t2[q]; }
       if (tid == 0) gst[R + 1] = (unsigned short)S;
     }
     __syncthreads();
-    for (int idx = tid; idx < S; idx += BK_AT) {
-      const u32 dig = (u32)gp[idx];
-      const u32 pos = wcnt[idx / chunk][dig] + rnk[idx];
-      sb[pos] = sa[idx]; gs[pos] = (unsigned short)dig;
+#pragma unroll
+    for (int q = 0; q < BK_PER_S; q++) {
+      const int j = tid + q * BK_AT;
+      if (j < S) { const u32 pos = (u32)gst[gp_[q]] + pl_[q]; sb[pos] = wd_[q]; gs[pos] = (unsigned short)gp_[q]; }
     }
     __syncthreads();
-    for (int j = tid; j < S; j += BK_AT) {              // inside the gap: by key, then by creation order (the word's low half)
+    for (int j = tid; j < S; j += BK_AT) {              // inside the gap: by the whole word, i.e. by key, then by slot (= creation order)
       const u64 mine = sb[j];
       const int g0 = (int)gs[j], a2 = (int)gst[g0], e2 = (int)gst[g0 + 1];
       int less = 0;
