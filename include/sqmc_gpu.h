@@ -610,6 +610,36 @@ int sqmc_gpu_hci_pt2_stochastic_sample(sqmc_pt2s_plan *plan, int64_t n_distinct,
 int sqmc_gpu_hci_pt2_stochastic_stats(sqmc_pt2s_plan *plan, int64_t *n_alloc, int64_t *capacity, int64_t *last_raw, int64_t *n_samples);
 /* replaces: the deallocations at the end of second_order_pt_alias (hci.f90:1642-1660) */
 int sqmc_gpu_hci_pt2_stochastic_free(sqmc_pt2s_plan *plan);
+/* replaces: get_1rdm (hci.f90:3198-3398), the one-body reduced density matrix of a variational wavefunction, spin-traced:
+ *   rdm[p + norb r] = sum_sigma sum_i c_i c_k sign,   orbitals 0-based,
+ * k = determinant i with the sigma electron moved p -> r (p occupied in i; r empty or r = p), sign = (-1)^(occupied sigma orbitals
+ * strictly between p and r) = permutation_factor of the two sigma strings (tools.f90:1294-1396).  The diagonal is sum_i c_i^2 over
+ * the determinants with p occupied, both spins added; the matrix is symmetric up to the order of its additions and its trace is
+ * nelec sum c^2.  The list may come in any order: the library forms and sorts the determinant ranks itself (merge_sort2_up_dn at
+ * :3328), and the result has the same bits for every order and from run to run (no floating-point atomics; a fixed tree).
+ * A repeated determinant, a determinant with other electron numbers than the context's, or an orbital beyond norb: SQMC_ERR_BAD_ARG.
+ * orbital_symmetries: norb labels (0..255) or NULL.  Given, pairs p, r of different label are skipped (:3351) and those entries are
+ * exactly 0.0, the others the bits of the unfiltered call.  Every system type.  Contexts initialised with time_sym = 1 and hubbardk
+ * with space_sym are refused (SQMC_ERR_UNSUPPORTED): pass the determinant-basis expansion (:3293-3308), the convention of
+ * sqmc_gpu_hci_pt2.  A refused call leaves rdm untouched. */
+int sqmc_gpu_hci_1rdm(sqmc_gpu_ctx *ctx, int64_t n_var, const uint64_t *var_up, const uint64_t *var_dn, const double *coeffs,
+                      const int32_t *orbital_symmetries, double *rdm);
+/* replaces: get_1rdm_with_pt (hci.f90:3400-3551): <0|rho|0> + <0|rho|1> + <1|rho|0>, |0> the variational wavefunction and |1> its
+ * first-order correction.  The variational part is sqmc_gpu_hci_1rdm without a symmetry filter (:3483: the reference has none
+ * there).  For every single excitation a of a variational determinant i that lies outside the variational space and inside the
+ * connected space generated at eps_pt_big, sign c_i psi1_a is added to both rdm(p, r) and rdm(r, p);
+ * psi1_a = (sum_j H_aj c_j) / (E_var - H_aa), the inner sum screened as the generator screens it (find_doubly_excited, :3471),
+ * H_aa from scratch.  No <1|rho|1> term and no renormalisation: the trace stays nelec sum c^2.  The reference searches the
+ * connected list first and the variational list second (:3488-3491); a variational determinant with c != 0 always occupies its own
+ * slot of the connected list and one with c = 0 contributes nothing, so searching the variational list first gives the same matrix.
+ * The connected space stays on the device (the generator of sqmc_gpu_hci_pt2); n_slices as there: every connected determinant
+ * lives in one slice, so the slices' contributions add (in slice order).  n_connections = connected determinants visited.
+ * The generator is handed the list in rank order, so the matrix has the same bits for every order of the caller's list.
+ * Accepts the contexts sqmc_gpu_hci_pt2 accepts (chem after sqmc_gpu_set_hb_tables, heg, hubbard2, hubbardk without space_sym)
+ * except that time_sym = 1 is refused as in sqmc_gpu_hci_1rdm.  Active-space masks (sqmc_gpu_hci_set_active_space) are generator
+ * state of the context and apply as they stand.  Same bits run to run; a refused call leaves rdm and n_connections untouched. */
+int sqmc_gpu_hci_1rdm_pt(sqmc_gpu_ctx *ctx, int64_t n_var, const uint64_t *var_up, const uint64_t *var_dn, const double *coeffs, double e_var,
+                         double eps_pt_big, int32_t n_slices, double *rdm, int64_t *n_connections);
 /* replaces: the off-diagonal histograms and weight ratios every walk of the reference keeps (off_diag_histograms = .true.,
  * do_walk.f90:104; gen_hist at 1420-1429; filled at 3619-3640 and in add_walker, 7603-7636; max_wt_ratio / min_wt_ratio at 3649-3661,
  * 7610-7622).  Context state, off by default: with it off a step launches exactly the kernels it launches without this entry.  On,

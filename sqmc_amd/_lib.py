@@ -28,7 +28,7 @@ EXPORTS = [
     "sqmc_gpu_shard_begin", "sqmc_gpu_shard_pack", "sqmc_gpu_shard_finish", "sqmc_gpu_shard_finish_psit", "sqmc_gpu_comm_unique_id", "sqmc_gpu_comm_init", "sqmc_gpu_comm_size",
     "sqmc_gpu_shard_step", "sqmc_gpu_shard_run", "sqmc_gpu_shard_time_split", "sqmc_gpu_get_rng", "sqmc_gpu_set_rng", "sqmc_gpu_tail_stats", "sqmc_gpu_last_tail", "sqmc_gpu_slowest_steps", "sqmc_gpu_set_chained_runs", "sqmc_gpu_spmv_prepare", "sqmc_gpu_davidson",
     "sqmc_gpu_spmv_apply", "sqmc_gpu_spmv_free", "sqmc_gpu_build_spmv_plan", "sqmc_gpu_spmv_sym_upper", "sqmc_gpu_hamiltonian_batch",
-    "sqmc_gpu_propose_batch", "sqmc_gpu_hamiltonian_chem_batch", "sqmc_gpu_build_sparse_ham", "sqmc_gpu_hci_connections", "sqmc_gpu_hci_connections_slice", "sqmc_gpu_hci_pt2", "sqmc_gpu_hci_pt2_stochastic_prepare", "sqmc_gpu_hci_pt2_stochastic_sample", "sqmc_gpu_hci_pt2_stochastic_stats", "sqmc_gpu_hci_pt2_stochastic_free", "sqmc_gpu_hci_set_active_space", "sqmc_gpu_diag_update_batch", "sqmc_gpu_hci_set_diag_update", "sqmc_gpu_hci_connections_record", "sqmc_gpu_free", "sqmc_gpu_set_timing", "sqmc_gpu_get_timing",
+    "sqmc_gpu_propose_batch", "sqmc_gpu_hamiltonian_chem_batch", "sqmc_gpu_build_sparse_ham", "sqmc_gpu_hci_connections", "sqmc_gpu_hci_connections_slice", "sqmc_gpu_hci_pt2", "sqmc_gpu_hci_pt2_stochastic_prepare", "sqmc_gpu_hci_pt2_stochastic_sample", "sqmc_gpu_hci_pt2_stochastic_stats", "sqmc_gpu_hci_pt2_stochastic_free", "sqmc_gpu_hci_set_active_space", "sqmc_gpu_diag_update_batch", "sqmc_gpu_hci_set_diag_update", "sqmc_gpu_hci_connections_record", "sqmc_gpu_hci_1rdm", "sqmc_gpu_hci_1rdm_pt", "sqmc_gpu_free", "sqmc_gpu_set_timing", "sqmc_gpu_get_timing",
     "sqmc_gpu_set_spawn_diagnostics", "sqmc_gpu_reset_spawn_diagnostics", "sqmc_gpu_get_spawn_diagnostics", "sqmc_gpu_debug_bucket_boundaries",
 ]
 
@@ -659,6 +659,34 @@ def _gpuchem_hci_pt2(self, up, dn, coeffs, e_var, eps_pt, n_slices=1):
     return de.value, nc.value
 
 
+def _gpuchem_one_rdm(self, up, dn, coeffs, orbital_symmetries=None):
+    """sqmc_gpu_hci_1rdm (get_1rdm, hci.f90:3198-3398): the spin-traced one-body density matrix of a determinant list in any order as
+    an (norb, norb) array, a[p, r] = sum_sigma <psi| a+_r a_p |psi> (the electron moves p -> r; 0-based).  orbital_symmetries: norb
+    labels, pairs of different label are skipped and exactly 0.0"""
+    u, d, c = _u64(up), _u64(dn), _f64(coeffs)
+    if not (len(u) == len(d) == len(c)):
+        raise ValueError("up, dn and coeffs differ in length")
+    sym = None if orbital_symmetries is None else np.ascontiguousarray(orbital_symmetries, np.int32)
+    if sym is not None and len(sym) != self.norb:
+        raise ValueError("orbital_symmetries must hold norb labels")
+    out = np.zeros(self.norb * self.norb)
+    self.L.sqmc_gpu_hci_1rdm.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 5
+    _chk(self.L.sqmc_gpu_hci_1rdm(self.h, len(u), _p(u), _p(d), _p(c), None if sym is None else _p(sym), _p(out)))
+    return np.ascontiguousarray(out.reshape(self.norb, self.norb).T)          # flat index p + norb r
+
+
+def _gpuchem_one_rdm_pt(self, up, dn, coeffs, e_var, eps_pt_big, n_slices=1):
+    """sqmc_gpu_hci_1rdm_pt (get_1rdm_with_pt, hci.f90:3400-3551): (<0|rho|0> + <0|rho|1> + <1|rho|0> as an (norb, norb) array indexed
+    as one_rdm's, connected determinants visited)"""
+    u, d, c = _u64(up), _u64(dn), _f64(coeffs)
+    if not (len(u) == len(d) == len(c)):
+        raise ValueError("up, dn and coeffs differ in length")
+    out, nc = np.zeros(self.norb * self.norb), C.c_int64()
+    self.L.sqmc_gpu_hci_1rdm_pt.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p]
+    _chk(self.L.sqmc_gpu_hci_1rdm_pt(self.h, len(u), _p(u), _p(d), _p(c), float(e_var), float(eps_pt_big), int(n_slices), _p(out), C.byref(nc)))
+    return np.ascontiguousarray(out.reshape(self.norb, self.norb).T), nc.value
+
+
 class HeatbathTables(C.Structure):
     """sqmc_heatbath_tables of include/sqmc_gpu.h"""
     _fields_ = [("norb", C.c_int32), ("reserved", C.c_int32), ("one", C.c_void_p), ("two", C.c_void_p), ("three_same", C.c_void_p), ("three_opp", C.c_void_p),
@@ -812,3 +840,5 @@ GpuChem.hci_set_active_space = _gpuchem_hci_set_active_space
 GpuChem.diag_update_batch = _gpuchem_diag_update_batch
 GpuChem.hci_set_diag_update = _gpuchem_hci_set_diag_update
 GpuChem.hci_connections_record = _gpuchem_hci_connections_record
+GpuChem.one_rdm = _gpuchem_one_rdm
+GpuChem.one_rdm_pt = _gpuchem_one_rdm_pt

@@ -24,6 +24,7 @@ module sqmc_gpu_mod
   public :: sqmc_gpu_hci_pt2_stochastic_prepare, sqmc_gpu_hci_pt2_stochastic_sample, sqmc_gpu_hci_pt2_stochastic_stats, sqmc_gpu_hci_pt2_stochastic_free
   public :: sqmc_gpu_set_spawn_diagnostics, sqmc_gpu_reset_spawn_diagnostics, sqmc_gpu_get_spawn_diagnostics
   public :: sqmc_gpu_set_hubbardk_space_sym, sqmc_gpu_hubbardk_sym_images, sqmc_gpu_debug_bucket_boundaries
+  public :: sqmc_gpu_hci_1rdm, sqmc_gpu_hci_1rdm_pt
   public :: sqmc_gpu_check
 
   integer(c_int), parameter, public :: SQMC_RNG_REPLAY = 0, SQMC_RNG_COUNTER = 1
@@ -186,6 +187,19 @@ module sqmc_gpu_mod
       import; type(c_ptr), value :: ctx; integer(c_int64_t), value :: n_var; integer(c_int64_t), intent(in) :: var_up(*), var_dn(*)
       real(c_double), intent(in) :: coeffs(*); real(c_double), value :: e_var, eps_pt; integer(c_int32_t), value :: n_slices
       real(c_double), intent(out) :: delta_e; integer(c_int64_t), intent(out) :: n_connections
+    end function
+    ! get_1rdm (hci.f90:3198-3398): rdm(norb, norb) of a determinant list in any order; orbital_symmetries = c_loc of norb
+    ! integer(c_int32_t) labels (pairs of different label are skipped, :3351) or c_null_ptr
+    integer(c_int) function sqmc_gpu_hci_1rdm(ctx, n_var, var_up, var_dn, coeffs, orbital_symmetries, rdm) bind(C, name='sqmc_gpu_hci_1rdm')
+      import; type(c_ptr), value :: ctx; integer(c_int64_t), value :: n_var; integer(c_int64_t), intent(in) :: var_up(*), var_dn(*)
+      real(c_double), intent(in) :: coeffs(*); type(c_ptr), value :: orbital_symmetries; real(c_double), intent(out) :: rdm(*)
+    end function
+    ! get_1rdm_with_pt (hci.f90:3400-3551): <0|rho|0> + <0|rho|1> + <1|rho|0>, the connected space at eps_pt_big in n_slices parts
+    integer(c_int) function sqmc_gpu_hci_1rdm_pt(ctx, n_var, var_up, var_dn, coeffs, e_var, eps_pt_big, n_slices, rdm, n_connections) &
+        bind(C, name='sqmc_gpu_hci_1rdm_pt')
+      import; type(c_ptr), value :: ctx; integer(c_int64_t), value :: n_var; integer(c_int64_t), intent(in) :: var_up(*), var_dn(*)
+      real(c_double), intent(in) :: coeffs(*); real(c_double), value :: e_var, eps_pt_big; integer(c_int32_t), value :: n_slices
+      real(c_double), intent(out) :: rdm(*); integer(c_int64_t), intent(out) :: n_connections
     end function
     ! second_order_pt_alias (hci.f90:1314-1660): the variational wavefunction and the work buffers stay on the device (prepare),
     ! one call per sample with the merged draws (0-based ids, ascending, and their counts), free at the end; chem and heg contexts

@@ -1603,6 +1603,73 @@ def hci_pt2_determinant_basis(host, up, dn, coeffs, e_var, eps_pt, n_slices=1, d
         g.close()
 
 
+# ------------------------------------------------------------------------- 1-RDM and natural orbitals
+def hci_one_rdm(host, up, dn, wts, energies=None, use_pt=False, eps_pt_big=None, n_slices=1):
+    """The 1-RDM of an HCI wavefunction as perform_hci forms it (hci.f90:683-736), an (norb, norb) array indexed [p, r] as
+    GpuChem.one_rdm's.  wts: [n] or [n, n_states].  Without PT the matrices of all states are averaged (:714-728) and, for chem, pairs
+    of orbitals of different symmetry are skipped (:3351); with PT state 1 alone is used (:710), energies[0] is its variational
+    energy and the connected space is generated at eps_pt_big in n_slices parts.  A time-symmetrised wavefunction is expanded
+    in determinants first (:3293-3308) and the context is one with time_sym off, as in hci_pt2_determinant_basis.
+    Returns the matrix, or (matrix, connected determinants visited) with use_pt."""
+    import copy
+    w = np.asarray(wts, float)
+    w = w.reshape(len(w), -1)
+    plain, z = host, getattr(host, "z", 1)
+    ts = bool(getattr(host, "time_sym", False))
+    if ts:
+        plain = copy.copy(host)
+        plain.time_sym = False
+    chem = isinstance(host, ChemHost)
+    sym = np.asarray(host.orbsym[1:host.norb + 1], np.int32) if chem and not use_pt else None
+    g = plain.gpu()
+    try:
+        if use_pt:
+            if energies is None or eps_pt_big is None:
+                raise ValueError("hci_one_rdm: use_pt needs energies and eps_pt_big")
+            if chem:
+                g.set_hb_tables(*plain.hb_tables(g))
+            du, dd, dc = time_symmetrized_to_dets(up, dn, w[:, 0], z) if ts else (up, dn, w[:, 0])
+            return g.one_rdm_pt(du, dd, dc, float(np.atleast_1d(energies)[0]), eps_pt_big, n_slices)
+        total = None
+        for i in range(w.shape[1]):
+            du, dd, dc = time_symmetrized_to_dets(up, dn, w[:, i], z) if ts else (up, dn, w[:, i])
+            m = g.one_rdm(du, dd, dc, sym)
+            total = m if total is None else total + m
+        return total / w.shape[1] if w.shape[1] > 1 else total
+    finally:
+        g.close()
+
+
+def natural_orbitals(rdm, orbital_symmetries):
+    """The diagonalisation of generate_natorb_integrals (hci.f90:3591-3632) and nothing after it: one eigh per irrep on the block of
+    that irrep's orbitals, eigenvalues (occupation numbers) in decreasing order within the irrep at that irrep's orbital positions,
+    eigenvectors in the corresponding columns (zero outside the block).  Returns (occupations[norb], vectors[norb, norb])."""
+    m = np.asarray(rdm, float)
+    sym = np.asarray(orbital_symmetries).reshape(-1)
+    n = m.shape[0]
+    if m.shape != (n, n) or len(sym) != n:
+        raise ValueError("natural_orbitals: rdm must be (norb, norb) and orbital_symmetries hold norb labels")
+    occ, vec = np.zeros(n), np.zeros((n, n))
+    for irrep in sorted(set(sym.tolist())):
+        ix = np.nonzero(sym == irrep)[0]
+        blk = m[np.ix_(ix, ix)]
+        ev, v = np.linalg.eigh(np.triu(blk) + np.triu(blk, 1).T)       # dsyev('V', 'U'): the upper triangle is what is read
+        occ[ix] = ev[::-1]
+        vec[np.ix_(ix, ix)] = v[:, ::-1]
+    return occ, vec
+
+
+def format_real_matrix(m):
+    """print_real_matrix (more_tools.f90:945-975): one row per line in '(1000f10.3)'"""
+    return "\n".join("".join(_f(float(x), 10, 3) for x in row) for row in np.asarray(m, float))
+
+
+def format_eigenvalues(v):
+    """'(10es11.4)': ten to a line"""
+    v = [float(x) for x in np.asarray(v, float).reshape(-1)]
+    return "\n".join("".join(_fortran_es(x, 11, 4) for x in v[k:k + 10]) for k in range(0, len(v), 10))
+
+
 # ------------------------------------------------------------------------- Fortran host deck
 def dump_walk_deck(path, host, setup, walkers, w_target, e_trial, seed=(1346, 5634, 6635, 4361), mwalk=400000, rng_mode=RNG_COUNTER):
     """Everything a compiled host needs to start the same walk through the C ABI, as one

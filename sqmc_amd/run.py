@@ -7,7 +7,9 @@ dump_wf_var, the chem Hamiltonian block of chemistry.f90:119-245, then the namel
 &selected_ci and &hf_det) and the result lines of perform_hci (hci.f90:323, 487, 833-841), so the
 shipped decks (C2_v2z_curve/*/i_1sigma_g) run unchanged next to their FCIDUMP and the same
 `grep 'Total energy(1)'` post-processing applies.  PT: deterministic, or with `n_mc > 0` and
-`eps_pt_big` in &selected_ci the semistochastic scheme of second_order_pt_alias.  Host-side
+`eps_pt_big` in &selected_ci the semistochastic scheme of second_order_pt_alias.  `&natorb get_natorbs=t [use_pt=t] /`
+(hci.f90:683-745): the 1-RDM of the variational wavefunction (or its lowest-order PT correction) and its natural orbitals by
+irrep, printed as the reference prints them; the run stops there, the rotation of the integrals is not built.  Host-side
 plumbing: every piece that scales with the number of determinants runs in libsqmc_gpu."""
 import argparse
 import os
@@ -85,6 +87,9 @@ def parse_hci_deck(text):
     deck["eps_var_sched"] = [float(v.lower().replace("d", "e")) for v in sci.get("eps_var_sched", [])]
     deck["n_mc"] = int(float(sci.get("n_mc", ["0"])[0]))
     deck["eps_pt_big"] = float(sci["eps_pt_big"][0].lower().replace("d", "e")) if "eps_pt_big" in sci else 0.0
+    nat = nl.get("natorb", {})               # hci.f90:683-745
+    deck["get_natorbs"] = _logical(nat["get_natorbs"][0]) if "get_natorbs" in nat else False
+    deck["use_pt"] = _logical(nat["use_pt"][0]) if "use_pt" in nat else False
     if deck["hamiltonian_type"] == "heg":              # read_heg, heg.f90:102-170
         deck["n_dim"] = int(_numbers(lines[5], 1)[0]); deck["r_s"] = _numbers(lines[6], 1)[0]
         ne, nu = _numbers(lines[7], 2)
@@ -107,6 +112,8 @@ def parse_hci_deck(text):
 def run_hci_heg(deck, out=sys.stdout, pt_on_device=False, pt_diag_update=0):
     """HEG decks: no integral file; result lines as hci.f90 prints them for 'heg' (no state index in the
     older output format the e2e fixtures were produced with; Madelung total, correlation energy)."""
+    if deck.get("get_natorbs"):
+        raise SystemExit("Natural orbitals only implemented for chem so far")          # hci.f90:684
     import torch            # noqa: F401
     import sqmc_amd
     from . import host as H
@@ -149,9 +156,55 @@ def run_hci_heg(deck, out=sys.stdout, pt_on_device=False, pt_diag_update=0):
     return res
 
 
-def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False, pt_diag_update=0):
+NATORB_STOP = "sqmc_amd: rotating the integrals into FCIDUMP.natorb (generate_natorb_integrals, hci.f90:3681-3846) is not built; stopping after the natural orbitals"
+
+
+def run_natorbs(deck, h, up, dn, wts, energy, p, one_rdm_path=None):
+    """&natorb get_natorbs = t (hci.f90:683-745): the 1-RDM of the variational wavefunction, or with use_pt its lowest-order PT
+    correction, its natural orbitals by irrep, printed as the reference prints them; the run stops there (the reference stops at :745
+    after rotating the integrals, which is not built)"""
+    from . import host as H
+    from ._lib import SqmcGpuError
+    n_states = deck["n_states"]
+    if deck["use_pt"]:
+        p("\nGetting natural orbitals from the lowest-order perturbative correction to the variational 1-RDM")
+        eps_big = deck["eps_pt_big"] if deck["eps_pt_big"] > 0 else deck["eps_pt"]            # :688-689
+        p("\nComputing 1-RDM to lowest nonzero order in PT\n")
+        try:
+            rdm, nconn = H.hci_one_rdm(h, up, dn, wts, energies=energy, use_pt=True, eps_pt_big=eps_big)
+        except SqmcGpuError as e:
+            if "2^31" in str(e) or "out of memory" in str(e).lower():
+                raise SystemExit("sqmc_amd: the connected space at eps_pt_big =%11.4E does not fit (%s); the reference would raise eps_pt_big by its "
+                                 "connection estimate here (hci.f90:692-703), which is not built: give an explicit, larger eps_pt_big in &selected_ci" % (eps_big, e))
+            raise
+        p("\nActual ndets_connected in get_1rdm_with_pt%13d =%9.2E" % (nconn, float(nconn)))
+        p("\nPT-corrected 1-RDM:")
+    else:
+        p(" Getting natural orbitals from the variational 1-RDM")
+        if n_states > 1:
+            p(" Using state-averaged 1-RDM from the lowest%12d states" % n_states)
+            for i in range(n_states):
+                p(" Computing 1-RDM of state%12d" % (i + 1))
+        p("\nComputing 1-RDM")
+        rdm = H.hci_one_rdm(h, up, dn, wts[:, :n_states])
+        p("\n1-RDM:")
+    p(H.format_real_matrix(rdm))
+    p("Done generating rdm")
+    occ, vec = H.natural_orbitals(rdm, h.orbsym[1:h.norb + 1])
+    p("\nEigenvectors of 1RDM:")
+    p(H.format_real_matrix(vec))
+    p("Eigenvalues of 1RDM:")
+    p(H.format_eigenvalues(occ))
+    if one_rdm_path:
+        np.save(one_rdm_path, rdm)
+    p("\n" + NATORB_STOP)
+    return dict(ndets=len(up), up=up, dn=dn, wts=wts, energy=energy, rdm=rdm, occupations=occ, vectors=vec)
+
+
+def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False, pt_diag_update=0, one_rdm_path=None):
     """pt_on_device: the samples of the semistochastic PT are evaluated by the library (host.hci_pt2_stochastic on_device);
-    pt_diag_update: 0 / 1 / 2, how the PT stage forms H_aa (host.hci_pt2)"""
+    pt_diag_update: 0 / 1 / 2, how the PT stage forms H_aa (host.hci_pt2); one_rdm_path: with &natorb get_natorbs = t, also save the
+    1-RDM there as .npy"""
     if deck["hamiltonian_type"] == "heg":
         return run_hci_heg(deck, out, pt_on_device, pt_diag_update)
     import torch            # noqa: F401  one libamdhip64 per process
@@ -187,6 +240,8 @@ def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False, pt_diag
             H.write_wf_var(wf, up, dn, wts, energy)
     g.close()
     t1 = time.perf_counter()
+    if deck.get("get_natorbs"):
+        return run_natorbs(deck, h, up, dn, wts, energy, p, one_rdm_path)
     results = []
     for i in range(n_states):
         if deck["n_mc"] > 0 and deck["eps_pt_big"] > deck["eps_pt"]:
@@ -243,6 +298,7 @@ def main(argv=None):
                     "of get_new_diag_elem on one lane (1) or by 16-lane groups (2); with n_mc > 0 it needs --pt-on-device")
     ap.add_argument("--spawn-histograms", action="store_true", help="walk decks: keep and print the reference's histograms of abs(weight_j)/tau = |H_ij|/p "
                     "(off_diag_histograms, do_walk.f90:3295-3311) and, at ipr >= 1, its max / min weight-ratio line; steps run un-pipelined")
+    ap.add_argument("--one-rdm", default=None, metavar="PATH", help="HCI decks with &natorb get_natorbs = t: also save the (norb, norb) 1-RDM as a .npy file")
     a = ap.parse_args(argv)
     text = open(a.input).read() if a.input else sys.stdin.read()
     lines = [l for l in text.splitlines() if l.strip() and not l.lstrip().startswith("!")]
@@ -252,7 +308,7 @@ def main(argv=None):
         return run_walk(parse_walk_deck(text), a.fcidump, walkalize=a.walkalize, psit_con_in=a.psit_con_in, psit_con_out=a.psit_con_out,
                         dtm_elems_in=a.dtm_elems_in, dtm_elems_out=a.dtm_elems_out, spawn_histograms=a.spawn_histograms)
     deck = parse_hci_deck(text)
-    return run_hci(deck, a.fcidump, pt_on_device=a.pt_on_device, pt_diag_update=a.pt_diag_update)
+    return run_hci(deck, a.fcidump, pt_on_device=a.pt_on_device, pt_diag_update=a.pt_diag_update, one_rdm_path=a.one_rdm)
 
 
 if __name__ == "__main__":
