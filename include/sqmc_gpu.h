@@ -640,6 +640,20 @@ int sqmc_gpu_hci_1rdm(sqmc_gpu_ctx *ctx, int64_t n_var, const uint64_t *var_up, 
  * state of the context and apply as they stand.  Same bits run to run; a refused call leaves rdm and n_connections untouched. */
 int sqmc_gpu_hci_1rdm_pt(sqmc_gpu_ctx *ctx, int64_t n_var, const uint64_t *var_up, const uint64_t *var_dn, const double *coeffs, double e_var,
                          double eps_pt_big, int32_t n_slices, double *rdm, int64_t *n_connections);
+/* replaces: the integral rotation of generate_natorb_integrals (hci.f90:3683-3791): the context's one- and two-body integrals in
+ * the orbitals  new_p = sum_k rot[k norb + p] old_k  (k, p 0-based, in the context's orbital order; row-major: the C-order memory of
+ * the eigenvector matrix the 1-RDM is diagonalised into, the transpose of a column-major host's rdm(k, p)):
+ *   (PQ|RS)' = sum_abcd U_aP U_bQ U_cR U_dS (ab|cd),   h'_PQ = sum_ab U_aP U_bQ h_ab,   E_nuc' = E_nuc,   U_kp = rot[k norb + p].
+ * integrals_out: n_integrals + 1 doubles in the layout of sqmc_chem_cfg::integrals, addressed by the context's combine_2, so that a
+ * new context can be initialised from it; every slot combine_2 does not address is 0.0.  The reference makes four passes over the
+ * full norb^4 tensor; this makes two half transformations over orbital pairs and forms the packed (canonical) entries only, so the
+ * result agrees with the reference's to rounding, not bit for bit.  rot may be any finite real matrix: orthogonality is not checked
+ * (:3683-3791 does not check it either).  Same bits call to call (no atomics, a fixed summation order); a 0 or +-1 entry of rot
+ * multiplies exactly, so the identity returns the input.  The context's own integrals stay as they are.
+ * Chem contexts only, time_sym and n_core_orb do not matter: heg, hubbard2 and hubbardk return SQMC_ERR_UNSUPPORTED, as does a
+ * combine_2 that is not a symmetric one-to-one pair index.  A null pointer or a non-finite entry of rot: SQMC_ERR_BAD_ARG.
+ * A refused or failed call leaves integrals_out untouched.  Device memory: (norb (norb + 1) / 2)^2 doubles of work space. */
+int sqmc_gpu_rotate_integrals(sqmc_gpu_ctx *ctx, const double *rot, double *integrals_out);
 /* replaces: the off-diagonal histograms and weight ratios every walk of the reference keeps (off_diag_histograms = .true.,
  * do_walk.f90:104; gen_hist at 1420-1429; filled at 3619-3640 and in add_walker, 7603-7636; max_wt_ratio / min_wt_ratio at 3649-3661,
  * 7610-7622).  Context state, off by default: with it off a step launches exactly the kernels it launches without this entry.  On,

@@ -28,7 +28,7 @@ EXPORTS = [
     "sqmc_gpu_shard_begin", "sqmc_gpu_shard_pack", "sqmc_gpu_shard_finish", "sqmc_gpu_shard_finish_psit", "sqmc_gpu_comm_unique_id", "sqmc_gpu_comm_init", "sqmc_gpu_comm_size",
     "sqmc_gpu_shard_step", "sqmc_gpu_shard_run", "sqmc_gpu_shard_time_split", "sqmc_gpu_get_rng", "sqmc_gpu_set_rng", "sqmc_gpu_tail_stats", "sqmc_gpu_last_tail", "sqmc_gpu_slowest_steps", "sqmc_gpu_set_chained_runs", "sqmc_gpu_spmv_prepare", "sqmc_gpu_davidson",
     "sqmc_gpu_spmv_apply", "sqmc_gpu_spmv_free", "sqmc_gpu_build_spmv_plan", "sqmc_gpu_spmv_sym_upper", "sqmc_gpu_hamiltonian_batch",
-    "sqmc_gpu_propose_batch", "sqmc_gpu_hamiltonian_chem_batch", "sqmc_gpu_build_sparse_ham", "sqmc_gpu_hci_connections", "sqmc_gpu_hci_connections_slice", "sqmc_gpu_hci_pt2", "sqmc_gpu_hci_pt2_stochastic_prepare", "sqmc_gpu_hci_pt2_stochastic_sample", "sqmc_gpu_hci_pt2_stochastic_stats", "sqmc_gpu_hci_pt2_stochastic_free", "sqmc_gpu_hci_set_active_space", "sqmc_gpu_diag_update_batch", "sqmc_gpu_hci_set_diag_update", "sqmc_gpu_hci_connections_record", "sqmc_gpu_hci_1rdm", "sqmc_gpu_hci_1rdm_pt", "sqmc_gpu_free", "sqmc_gpu_set_timing", "sqmc_gpu_get_timing",
+    "sqmc_gpu_propose_batch", "sqmc_gpu_hamiltonian_chem_batch", "sqmc_gpu_build_sparse_ham", "sqmc_gpu_hci_connections", "sqmc_gpu_hci_connections_slice", "sqmc_gpu_hci_pt2", "sqmc_gpu_hci_pt2_stochastic_prepare", "sqmc_gpu_hci_pt2_stochastic_sample", "sqmc_gpu_hci_pt2_stochastic_stats", "sqmc_gpu_hci_pt2_stochastic_free", "sqmc_gpu_hci_set_active_space", "sqmc_gpu_diag_update_batch", "sqmc_gpu_hci_set_diag_update", "sqmc_gpu_hci_connections_record", "sqmc_gpu_hci_1rdm", "sqmc_gpu_hci_1rdm_pt", "sqmc_gpu_rotate_integrals", "sqmc_gpu_free", "sqmc_gpu_set_timing", "sqmc_gpu_get_timing",
     "sqmc_gpu_set_spawn_diagnostics", "sqmc_gpu_reset_spawn_diagnostics", "sqmc_gpu_get_spawn_diagnostics", "sqmc_gpu_debug_bucket_boundaries",
 ]
 
@@ -687,6 +687,19 @@ def _gpuchem_one_rdm_pt(self, up, dn, coeffs, e_var, eps_pt_big, n_slices=1):
     return np.ascontiguousarray(out.reshape(self.norb, self.norb).T), nc.value
 
 
+def _gpuchem_rotate_integrals(self, rot):
+    """sqmc_gpu_rotate_integrals (the rotation of generate_natorb_integrals, hci.f90:3683-3791): the context's integrals in the orbitals
+    new_p = sum_k rot[k, p] old_k, as a new packed array of n_integrals + 1 doubles addressed by the same combine_2.  rot: (norb, norb),
+    the `vectors` of host.natural_orbitals; any finite real matrix."""
+    u = _f64(rot)
+    if u.shape != (self.norb, self.norb):
+        raise ValueError("rotate_integrals: rot must be (norb, norb) = (%d, %d), got %r" % (self.norb, self.norb, u.shape))
+    out = np.zeros(len(self._tabs[3]) if len(self._tabs) > 3 else 1)      # (the library refuses a context without an integral table)
+    self.L.sqmc_gpu_rotate_integrals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    _chk(self.L.sqmc_gpu_rotate_integrals(self.h, _p(u), _p(out)))
+    return out
+
+
 class HeatbathTables(C.Structure):
     """sqmc_heatbath_tables of include/sqmc_gpu.h"""
     _fields_ = [("norb", C.c_int32), ("reserved", C.c_int32), ("one", C.c_void_p), ("two", C.c_void_p), ("three_same", C.c_void_p), ("three_opp", C.c_void_p),
@@ -842,3 +855,4 @@ GpuChem.hci_set_diag_update = _gpuchem_hci_set_diag_update
 GpuChem.hci_connections_record = _gpuchem_hci_connections_record
 GpuChem.one_rdm = _gpuchem_one_rdm
 GpuChem.one_rdm_pt = _gpuchem_one_rdm_pt
+GpuChem.rotate_integrals = _gpuchem_rotate_integrals

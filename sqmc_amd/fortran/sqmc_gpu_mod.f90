@@ -24,7 +24,7 @@ module sqmc_gpu_mod
   public :: sqmc_gpu_hci_pt2_stochastic_prepare, sqmc_gpu_hci_pt2_stochastic_sample, sqmc_gpu_hci_pt2_stochastic_stats, sqmc_gpu_hci_pt2_stochastic_free
   public :: sqmc_gpu_set_spawn_diagnostics, sqmc_gpu_reset_spawn_diagnostics, sqmc_gpu_get_spawn_diagnostics
   public :: sqmc_gpu_set_hubbardk_space_sym, sqmc_gpu_hubbardk_sym_images, sqmc_gpu_debug_bucket_boundaries
-  public :: sqmc_gpu_hci_1rdm, sqmc_gpu_hci_1rdm_pt
+  public :: sqmc_gpu_hci_1rdm, sqmc_gpu_hci_1rdm_pt, sqmc_gpu_rotate_integrals
   public :: sqmc_gpu_check
 
   integer(c_int), parameter, public :: SQMC_RNG_REPLAY = 0, SQMC_RNG_COUNTER = 1
@@ -200,6 +200,12 @@ module sqmc_gpu_mod
       import; type(c_ptr), value :: ctx; integer(c_int64_t), value :: n_var; integer(c_int64_t), intent(in) :: var_up(*), var_dn(*)
       real(c_double), intent(in) :: coeffs(*); real(c_double), value :: e_var, eps_pt_big; integer(c_int32_t), value :: n_slices
       real(c_double), intent(out) :: rdm(*); integer(c_int64_t), intent(out) :: n_connections
+    end function
+    ! the integral rotation of generate_natorb_integrals (hci.f90:3683-3791): rot(norb, norb) with rot(p, k) = component on the
+    ! context's orbital k of new orbital p (column-major; the C side reads rot[k norb + p], 0-based); integrals_out(0:n_integrals)
+    ! in the layout of sqmc_chem_cfg%integrals.  Chem contexts only
+    integer(c_int) function sqmc_gpu_rotate_integrals(ctx, rot, integrals_out) bind(C, name='sqmc_gpu_rotate_integrals')
+      import; type(c_ptr), value :: ctx; real(c_double), intent(in) :: rot(*); real(c_double), intent(out) :: integrals_out(*)
     end function
     ! second_order_pt_alias (hci.f90:1314-1660): the variational wavefunction and the work buffers stay on the device (prepare),
     ! one call per sample with the merged draws (0-based ids, ascending, and their counts), free at the end; chem and heg contexts

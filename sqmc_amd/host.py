@@ -34,7 +34,8 @@ def read_fcidump(path):
     import re
     norb = int(re.search(r"NORB\s*=\s*(\d+)", hdr).group(1))
     m = re.search(r"ORBSYM\s*=\s*([\d,\s]+)", hdr)
-    orbsym = [int(x) for x in m.group(1).replace("\n", " ").split(",") if x.strip()][:norb] if m else [1] * norb
+    # comma-separated as most programs write it, or the bare '(100000i3)' fields of generate_natorb_integrals (hci.f90:3802)
+    orbsym = [int(x) for x in re.split(r"[,\s]+", m.group(1)) if x][:norb] if m else [1] * norb
     return norb, orbsym, data[:, 0].copy(), data[:, 1:5].astype(np.int64)
 
 
@@ -206,6 +207,19 @@ class ChemHost:
         c2[1:n1, 1:n1] = (hi * (hi - 1)) // 2 + lo
         c2[n1, n1] = (n1 * n) // 2 + n1
         self.combine_2 = c2
+
+    def with_integrals(self, packed):
+        """A shallow copy of this host that holds other integrals in the same orbital order -- GpuChem.rotate_integrals' result:
+        same combine_2, orbsym, orb_order and starting determinant (the orbitals are not re-sorted by energy); the heat-bath table
+        of the old integrals is dropped, so that gpu() / hb_tables() build from the new values."""
+        import copy
+        a = np.array(packed, np.float64)
+        if a.shape != self.integrals.shape:
+            raise ValueError("with_integrals: %r values, this host's packed table holds %r" % (a.shape, self.integrals.shape))
+        h = copy.copy(self)
+        h.integrals = a
+        h.__dict__.pop("hb", None)
+        return h
 
     def gpu(self, proposal="uniform", **kw):
         """a context for this molecule.  proposal="cauchyschwarz": proposal_method CauchySchwarz -- the exchange integrals are
@@ -1668,6 +1682,44 @@ def format_eigenvalues(v):
     """'(10es11.4)': ten to a line"""
     v = [float(x) for x in np.asarray(v, float).reshape(-1)]
     return "\n".join("".join(_fortran_es(x, 11, 4) for x in v[k:k + 10]) for k in range(0, len(v), 10))
+
+
+def natorb_fcidump_name(eps):
+    """hci.f90:3795-3796: write(fmt,'(es7.2e1)') minval(eps_var_sched) ; filename = 'FCIDUMP_eps_var=' // fmt"""
+    m, e = ("%.2e" % eps).split("e")
+    return "FCIDUMP_eps_var=%sE%s%d" % (m, "-" if int(e) < 0 else "+", abs(int(e)))
+
+
+def write_natorb_fcidump(path, host, packed):
+    """The integral file generate_natorb_integrals writes (hci.f90:3794-3841) from a packed table in host's orbital order and
+    combine_2 (GpuChem.rotate_integrals): the header '&FCI NORB=' i5 ', NELEC=' i5 ', MS2=0', 'ORBSYM=' with the symmetries in file
+    order as bare i3 fields (a rotation within irreps leaves them as they were: new_orbital_symmetries(orb_order_inv(1:norb))),
+    'ISYM=1', '&END'; the two-body values over p, q <= p, r <= p, s <= r without p == r and q < s, then the one-body values over
+    q <= p with trailing 0 0, each only where abs > 1e-8, in '(es19.12e2,4i4)' with the file's labels orb_order(p); the nuclear
+    energy with 0 0 0 0 last.  Like the reference's status='new' it does not overwrite: FileExistsError.  The 'dih' relabelling
+    (:3651-3671) does not exist here: ChemHost has no such point group."""
+    n, n1, c2, order = host.norb, host.norb + 1, host.combine_2, host.orb_order
+    v = np.asarray(packed, np.float64)
+    if v.shape != host.integrals.shape:
+        raise ValueError("write_natorb_fcidump: %r values, the host's packed table holds %r" % (v.shape, host.integrals.shape))
+    rec = "%19.12E%4d%4d%4d%4d\n"
+    with open(path, "x") as f:
+        f.write("&FCI NORB=%5d, NELEC=%5d, MS2=0\n" % (n, host.nelec))
+        f.write("ORBSYM=" + "".join("%3d" % int(x) for x in host.orbsym_file[1:n1]) + "\n")
+        f.write("ISYM=1\n&END\n")
+        for p in range(1, n1):
+            q, r, s = (a.reshape(-1) for a in np.meshgrid(np.arange(1, p + 1), np.arange(1, p + 1), np.arange(1, p + 1), indexing="ij"))
+            keep = (s <= r) & ~((r == p) & (q < s))
+            q, r, s = q[keep], r[keep], s[keep]
+            val = v[ChemHost._index(c2, np.full(len(q), p), q, r, s)]
+            for k in np.nonzero(np.abs(val) > 1e-8)[0]:
+                f.write(rec % (val[k], order[p], order[q[k]], order[r[k]], order[s[k]]))
+        for p in range(1, n1):
+            for q in range(1, p + 1):
+                x = v[ChemHost._index(c2, p, q, n1, n1)]
+                if abs(x) > 1e-8:
+                    f.write(rec % (x, order[p], order[q], 0, 0))
+        f.write(rec % (v[ChemHost._index(c2, n1, n1, n1, n1)], 0, 0, 0, 0))
 
 
 # ------------------------------------------------------------------------- Fortran host deck

@@ -9,8 +9,9 @@ shipped decks (C2_v2z_curve/*/i_1sigma_g) run unchanged next to their FCIDUMP an
 `grep 'Total energy(1)'` post-processing applies.  PT: deterministic, or with `n_mc > 0` and
 `eps_pt_big` in &selected_ci the semistochastic scheme of second_order_pt_alias.  `&natorb get_natorbs=t [use_pt=t] /`
 (hci.f90:683-745): the 1-RDM of the variational wavefunction (or its lowest-order PT correction) and its natural orbitals by
-irrep, printed as the reference prints them; the run stops there, the rotation of the integrals is not built.  Host-side
-plumbing: every piece that scales with the number of determinants runs in libsqmc_gpu."""
+irrep, printed as the reference prints them; without --rotate-integrals the run stops there, with it the library rotates the
+integrals into the natural orbitals (sqmc_gpu_rotate_integrals) and the run writes them as FCIDUMP_eps_var=... for the next HCI
+run, where the reference stops too (:745).  Host-side plumbing: every piece that scales with the number of determinants runs in libsqmc_gpu."""
 import argparse
 import os
 import re
@@ -159,10 +160,13 @@ def run_hci_heg(deck, out=sys.stdout, pt_on_device=False, pt_diag_update=0):
 NATORB_STOP = "sqmc_amd: rotating the integrals into FCIDUMP.natorb (generate_natorb_integrals, hci.f90:3681-3846) is not built; stopping after the natural orbitals"
 
 
-def run_natorbs(deck, h, up, dn, wts, energy, p, one_rdm_path=None):
+def run_natorbs(deck, h, up, dn, wts, energy, p, one_rdm_path=None, natorb_fcidump=None):
     """&natorb get_natorbs = t (hci.f90:683-745): the 1-RDM of the variational wavefunction, or with use_pt its lowest-order PT
-    correction, its natural orbitals by irrep, printed as the reference prints them; the run stops there (the reference stops at :745
-    after rotating the integrals, which is not built)"""
+    correction, its natural orbitals by irrep, printed as the reference prints them.  natorb_fcidump = None: the run stops there with
+    NATORB_STOP.  A path: the second half of generate_natorb_integrals (hci.f90:3681-3846) -- the integrals rotated into the natural
+    orbitals on the device, written to that file (which must not exist) between the reference's two lines, and the run stops where
+    the reference stops (:745).  The reference's list-directed 'New orbital symmetries:' lines (:3649, :3679) are left out: their
+    spacing is the compiler's choice, and a rotation within irreps leaves the symmetries as the deck gives them."""
     from . import host as H
     from ._lib import SqmcGpuError
     n_states = deck["n_states"]
@@ -197,14 +201,30 @@ def run_natorbs(deck, h, up, dn, wts, energy, p, one_rdm_path=None):
     p(H.format_eigenvalues(occ))
     if one_rdm_path:
         np.save(one_rdm_path, rdm)
-    p("\n" + NATORB_STOP)
-    return dict(ndets=len(up), up=up, dn=dn, wts=wts, energy=energy, rdm=rdm, occupations=occ, vectors=vec)
+    res = dict(ndets=len(up), up=up, dn=dn, wts=wts, energy=energy, rdm=rdm, occupations=occ, vectors=vec)
+    if natorb_fcidump is None:
+        p("\n" + NATORB_STOP)
+        return res
+    if os.path.exists(natorb_fcidump):               # open(88, file=filename, status='new'), before any work is done
+        raise FileExistsError("sqmc_amd: %s exists; the rotated integrals are written to a new file only" % natorb_fcidump)
+    p("\nRotating integrals to new natural orbitals")
+    g = h.gpu()
+    try:
+        packed = g.rotate_integrals(vec)
+    finally:
+        g.close()
+    p("Done computing new integrals. Dumping new integrals into file " + natorb_fcidump)
+    H.write_natorb_fcidump(natorb_fcidump, h, packed)
+    res.update(natorb_integrals=packed, natorb_fcidump=natorb_fcidump)
+    return res
 
 
-def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False, pt_diag_update=0, one_rdm_path=None):
+def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False, pt_diag_update=0, one_rdm_path=None, natorb_fcidump=None):
     """pt_on_device: the samples of the semistochastic PT are evaluated by the library (host.hci_pt2_stochastic on_device);
     pt_diag_update: 0 / 1 / 2, how the PT stage forms H_aa (host.hci_pt2); one_rdm_path: with &natorb get_natorbs = t, also save the
-    1-RDM there as .npy"""
+    1-RDM there as .npy; natorb_fcidump: with &natorb get_natorbs = t, rotate the integrals into the natural orbitals and write them
+    to this new file (True: the reference's name, FCIDUMP_eps_var=<smallest eps_var>, in the working directory); the result then
+    holds natorb_integrals (packed, the host's combine_2) and natorb_fcidump (the path).  None: the run ends on NATORB_STOP."""
     if deck["hamiltonian_type"] == "heg":
         return run_hci_heg(deck, out, pt_on_device, pt_diag_update)
     import torch            # noqa: F401  one libamdhip64 per process
@@ -241,7 +261,9 @@ def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False, pt_diag
     g.close()
     t1 = time.perf_counter()
     if deck.get("get_natorbs"):
-        return run_natorbs(deck, h, up, dn, wts, energy, p, one_rdm_path)
+        if natorb_fcidump is True:
+            natorb_fcidump = H.natorb_fcidump_name(min([eps_var] + deck["eps_var_sched"]))
+        return run_natorbs(deck, h, up, dn, wts, energy, p, one_rdm_path, natorb_fcidump)
     results = []
     for i in range(n_states):
         if deck["n_mc"] > 0 and deck["eps_pt_big"] > deck["eps_pt"]:
@@ -299,6 +321,8 @@ def main(argv=None):
     ap.add_argument("--spawn-histograms", action="store_true", help="walk decks: keep and print the reference's histograms of abs(weight_j)/tau = |H_ij|/p "
                     "(off_diag_histograms, do_walk.f90:3295-3311) and, at ipr >= 1, its max / min weight-ratio line; steps run un-pipelined")
     ap.add_argument("--one-rdm", default=None, metavar="PATH", help="HCI decks with &natorb get_natorbs = t: also save the (norb, norb) 1-RDM as a .npy file")
+    ap.add_argument("--rotate-integrals", nargs="?", const=True, default=None, metavar="PATH", help="HCI decks with &natorb get_natorbs = t: rotate the integrals "
+                    "into the natural orbitals on the device and write them to PATH, a new file (default: FCIDUMP_eps_var=<smallest eps_var>, the reference's name)")
     a = ap.parse_args(argv)
     text = open(a.input).read() if a.input else sys.stdin.read()
     lines = [l for l in text.splitlines() if l.strip() and not l.lstrip().startswith("!")]
@@ -308,7 +332,7 @@ def main(argv=None):
         return run_walk(parse_walk_deck(text), a.fcidump, walkalize=a.walkalize, psit_con_in=a.psit_con_in, psit_con_out=a.psit_con_out,
                         dtm_elems_in=a.dtm_elems_in, dtm_elems_out=a.dtm_elems_out, spawn_histograms=a.spawn_histograms)
     deck = parse_hci_deck(text)
-    return run_hci(deck, a.fcidump, pt_on_device=a.pt_on_device, pt_diag_update=a.pt_diag_update, one_rdm_path=a.one_rdm)
+    return run_hci(deck, a.fcidump, pt_on_device=a.pt_on_device, pt_diag_update=a.pt_diag_update, one_rdm_path=a.one_rdm, natorb_fcidump=a.rotate_integrals)
 
 
 if __name__ == "__main__":
