@@ -11,6 +11,11 @@ Two arithmetics: `exact=True` adds weights as fractions.Fraction (any order give
 use), `exact=False` adds doubles one after the other as the reference's loop does (bit-comparable with any faithful
 restatement on arbitrary weights).  The sums of a generation are math.fsum's, correctly rounded.
 
+A step with semistochastic = f (`params["semistochastic"] == 0`) takes the same fold -- reduce_my_walker is not called, so no
+rounding draw is ever asked for -- then join_walker2 (6990-7103) over the merged list, which drops every zero weight, then the
+reweighting: plain_step.  Its draws come from the caller, draw(index of the later walker in the merged list); chain_layer states
+what holds of the result for any draws.
+
 What the model leaves to the caller: the stochastic rounding of reduce_my_walker needs a random number per small weight; pass
 `draw(up, dn)`, or none -- then an input that would need one raises NeedsDraw (the RNG-free cases assert exactly that).
 """
@@ -38,15 +43,13 @@ def default_params(**kw):
 
 def _records(residents, spawns):
     """(up, dn, wt, imp_distance, initiator, perm_sign) in arrival order; a spawn of weight 0 is no walker (do_walk.f90:3676)"""
-    out = []
-    ps = residents.get("perm_sign")
-    for i in range(len(residents["up"])):
-        out.append((int(residents["up"][i]), int(residents["dn"][i]), float(residents["wt"][i]), int(residents["imp_distance"][i]),
-                    int(residents["initiator"][i]), int(ps[i]) if ps is not None else 0))
-    for i in range(len(spawns["up"])):
-        if float(spawns["wt"][i]) != 0.0:
-            out.append((int(spawns["up"][i]), int(spawns["dn"][i]), float(spawns["wt"][i]), int(spawns["imp_distance"][i]),
-                        int(spawns["initiator"][i]), 0))
+    col = lambda d, k: np.asarray(d[k]).tolist()
+    n0 = len(residents["up"])
+    ps = col(residents, "perm_sign") if residents.get("perm_sign") is not None else [0] * n0
+    out = [(int(u), int(d), float(w), int(a), int(b), int(s)) for u, d, w, a, b, s in
+           zip(col(residents, "up"), col(residents, "dn"), col(residents, "wt"), col(residents, "imp_distance"), col(residents, "initiator"), ps)]
+    out += [(int(u), int(d), float(w), int(a), int(b), 0) for u, d, w, a, b in
+            zip(col(spawns, "up"), col(spawns, "dn"), col(spawns, "wt"), col(spawns, "imp_distance"), col(spawns, "initiator")) if w != 0.0]
     return out
 
 
@@ -74,6 +77,7 @@ def fold(residents, spawns, params, exact=True, draw=None, no_exception=False, o
     5995 replaced; rounded: determinants whose weight reduce_my_walker drew for).
     no_exception / order_blind: two deliberate mistakes, for showing that the twin test notices them."""
     p = params
+    plain = not p.get("semistochastic", 1)
     num = Fraction if exact else float
     recs = _records(residents, spawns)
     groups = {}
@@ -128,16 +132,19 @@ def fold(residents, spawns, params, exact=True, draw=None, no_exception=False, o
         if drop:
             discarded.append(key)
             continue
-        # reduce_my_walker, 7222-7249
-        if imp >= 1 and abs(wt) < p["min_wt"]:
-            if wt != 0:
-                if draw is None:
-                    raise NeedsDraw("determinant %r: |w| = %r < min_wt = %r" % (key, float(abs(wt)), p["min_wt"]))
-                rounded.append(key)
-                wt = num(math.copysign(p["min_wt"], wt)) if draw(key[0], key[1]) < float(abs(wt)) / p["min_wt"] else num(0)
-            if wt == 0:
-                continue
-        wt = wt * num(p["reweight_factor_inv"])      # 2487
+        if plain:                            # semistochastic = f: join_walker2 (2475) and the reweighting come behind the whole list, in plain_step
+            assert not exact or Fraction(float(wt)) == wt, "a weight of an exact case is a double"
+        else:
+            # reduce_my_walker, 7222-7249
+            if imp >= 1 and abs(wt) < p["min_wt"]:
+                if wt != 0:
+                    if draw is None:
+                        raise NeedsDraw("determinant %r: |w| = %r < min_wt = %r" % (key, float(abs(wt)), p["min_wt"]))
+                    rounded.append(key)
+                    wt = num(math.copysign(p["min_wt"], wt)) if draw(key[0], key[1]) < float(abs(wt)) / p["min_wt"] else num(0)
+                if wt == 0:
+                    continue
+            wt = wt * num(p["reweight_factor_inv"])      # 2487
         out["up"].append(key[0]); out["dn"].append(key[1]); out["wt"].append(float(wt))
         out["imp_distance"].append(imp); out["initiator"].append(init)
     res = dict(up=np.array(out["up"], np.uint64), dn=np.array(out["dn"], np.uint64), wt=np.array(out["wt"], np.float64),
@@ -153,6 +160,103 @@ def fold(residents, spawns, params, exact=True, draw=None, no_exception=False, o
     return res
 
 
+# ------------------------------------------------------------------------------------------------ semistochastic = f: the joins
+def join_walker2(wt, initiator, min_wt, draw, exact=True, close_at_ge=False, carrier_inverted=False, perm_initiator_joins=False):
+    """join_walker2 (do_walk.f90:6990-7069) on a merged list, before its zeros are dropped: the positive pass, then the negative
+    one.  A candidate has the pass's sign, |wt| < min_wt (strict) and initiator < 3.  The first candidate opens a chain; each later
+    one is joined to the chain's carrier: wttot = |w_i| + |w_carrier|, and if draw(i) > |w_i| / wttot the earlier walker keeps
+    wttot, otherwise the later one takes it; the chain closes when wttot > min_wt (strict).  draw(i): the random number of the
+    join whose later walker has index i (0-based) in this list.
+
+    Returns (weights, chains, joins): chains[+1 / -1] = [(member indices, exact total, closed)] in list order -- where a chain
+    begins and ends depends on the running sums alone, not on the draws.
+    close_at_ge / carrier_inverted / perm_initiator_joins: three deliberate mistakes."""
+    num = Fraction if exact else float
+    w = [num(float(x)) for x in wt]
+    chains, joins = {1: [], -1: []}, 0
+    for sign in (1, -1):
+        carrier, members, total = None, [], num(0)
+        for i in range(len(w)):
+            wi = w[i]
+            if not ((wi > 0 if sign > 0 else wi < 0) and abs(wi) < min_wt and (int(initiator[i]) < 3 or perm_initiator_joins)):
+                continue
+            if carrier is None:                               # 7007-7009
+                carrier, members, total = i, [i], abs(wi)
+                continue
+            wttot = abs(wi) + abs(w[carrier])                 # 7011
+            joins += 1
+            earlier_keeps = draw(i) > float(abs(wi)) / float(wttot)      # 7012
+            if carrier_inverted:
+                earlier_keeps = not earlier_keeps
+            if earlier_keeps:
+                w[carrier] = wttot if w[carrier] > 0 else -wttot; w[i] = num(0)
+            else:
+                w[i] = wttot if wi > 0 else -wttot; w[carrier] = num(0); carrier = i
+            members.append(i); total = wttot
+            if (wttot >= min_wt) if close_at_ge else (wttot > min_wt):   # 7030
+                chains[sign].append((members, total, True)); carrier = None
+        if carrier is not None:
+            chains[sign].append((members, total, False))
+    return w, chains, joins
+
+
+def plain_step(residents, spawns, params, draw, exact=True, **mistakes):
+    """What a step with semistochastic = f leaves of a list (do_walk.f90:2373-2487): merge_original_with_spawned2, join_walker2,
+    every zero weight dropped -- the deterministic space included (7075) -- then the reweighting.  Returns fold()'s dict for the
+    new list, plus heads (the merged list the joins saw: up, dn, wt, imp_distance, initiator), chains, joins."""
+    assert not params["semistochastic"]
+    m = fold(residents, spawns, params, exact=exact)
+    w, chains, joins = join_walker2(m["wt"], m["initiator"], params["min_wt"], draw, exact=exact, **mistakes)
+    keep = np.array([i for i in range(len(w)) if w[i] != 0], np.int64)   # 7071-7092
+    rfi = (Fraction if exact else float)(params["reweight_factor_inv"])
+    out = dict(m)
+    out["heads"] = {k: m[k] for k in ("up", "dn", "wt", "imp_distance", "initiator")}
+    for k in ("up", "dn", "imp_distance", "initiator", "perm_sign"):
+        out[k] = m[k][keep]
+    out["wt"] = np.array([float(w[i] * rfi) for i in keep], np.float64)  # 2487
+    out["chains"], out["joins"] = chains, joins
+    return out
+
+
+def chain_layer(heads, chains, params, got):
+    """The statements about an output list `got` (up, dn, wt, imp_distance, initiator) that hold for ANY draws: every non-member
+    of a chain is unchanged (dropped if its weight is zero); a chain of one is untouched; a chain of two or more leaves exactly
+    one survivor, one of its members, with that member's flags and weight sign x total (x reweight_factor_inv).  Returns a list
+    of violations."""
+    bad = []
+    rfi = Fraction(params["reweight_factor_inv"])
+    have = {(int(u), int(d)): (float(w), int(a), int(b)) for u, d, w, a, b in zip(got["up"], got["dn"], got["wt"], got["imp_distance"], got["initiator"])}
+    if len(have) != len(got["up"]):
+        bad.append(("a determinant twice",))
+    key = lambda i: (int(heads["up"][i]), int(heads["dn"][i]))
+    flags = lambda i: (int(heads["imp_distance"][i]), int(heads["initiator"][i]))
+    member = set()
+    for sign in (1, -1):
+        for mem, total, closed in chains[sign]:
+            member.update(mem)
+            if len(mem) == 1:
+                i = mem[0]
+                if have.pop(key(i), None) != (float(Fraction(float(heads["wt"][i])) * rfi),) + flags(i):
+                    bad.append(("chain of one changed", i))
+                continue
+            alive = [(i, have.pop(key(i))) for i in mem if key(i) in have]
+            if len(alive) != 1:
+                bad.append(("chain with %d survivors" % len(alive), mem[0], mem[-1])); continue
+            i, rec = alive[0]
+            if rec != (float(sign * Fraction(total) * rfi),) + flags(i):
+                bad.append(("survivor", i, rec, float(sign * Fraction(total) * rfi)))
+    for i in range(len(heads["up"])):
+        if i in member:
+            continue
+        w = float(heads["wt"][i])
+        rec = have.pop(key(i), None)
+        if (rec is not None) if w == 0.0 else (rec != (float(Fraction(w) * rfi),) + flags(i)):
+            bad.append(("non-candidate changed", i, rec))
+    if have:
+        bad.append(("determinants nobody had", sorted(have)[:3]))
+    return bad
+
+
 def check_precondition(residents, spawns, params):
     """What makes a case exact and RNG-free: weights multiples of 0.25 with |w| <= 4, min_wt = cutoff = 0.25, reweight_factor_inv 1 or
     0.5.  Raises AssertionError (NeedsDraw if the fold would consume a draw): a case that breaks it fails, it is not skipped."""
@@ -160,7 +264,9 @@ def check_precondition(residents, spawns, params):
         assert abs(w) <= 4.0 and float(w) * 4.0 == math.floor(float(w) * 4.0), "weight %r is no multiple of 0.25 within [-4, 4]" % w
     assert params["min_wt"] == 0.25 and params["always_spawn_cutoff_wt"] == 0.25, "min_wt and the cutoff are 0.25"
     assert params["reweight_factor_inv"] in (1.0, 0.5), "reweight_factor_inv is 1 or 0.5"
-    fold(residents, spawns, params, exact=True, draw=None)
+    m = fold(residents, spawns, params, exact=True, draw=None)
+    if not params["semistochastic"]:         # a plain step of such a list makes no join either: no head has 0 < |w| < min_wt
+        assert not any(0 < abs(float(w)) < params["min_wt"] for w in m["wt"]), "a head below min_wt: the plain step would join it"
 
 
 def sums(merged, params, ct, n_before=0, w_abs_before=0.0):

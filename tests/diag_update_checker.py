@@ -160,18 +160,26 @@ def update(ints, norb, old_diag, pqrs, new_up, new_dn, doctor=None):
 
 
 # ---------------------------------------------------------------------------------------------- brute force and records
-_DIAG = {}
+_CACHES = {}
+
+
+def _cache(H):
+    """the tables and diagonal elements already worked out for this very Hamiltonian.  The entry holds H itself: while it is
+    there H cannot be collected, so its id cannot pass to another object, and the identity test says so outright (an entry keyed
+    by a bare id() once served a new Hamiltonian the tables of a collected one)."""
+    e = _CACHES.get(id(H))
+    if e is None or e[0] is not H:
+        e = _CACHES[id(H)] = (H, {}, {})
+    return e
 
 
 def brute(H, det):
     """H_aa from scratch by second quantisation: (value, number of terms, sum |terms|); cached per (H, det)"""
-    key = (id(H), int(det[0]), int(det[1]))
-    if key not in _DIAG:
-        _DIAG[key] = HC.diagonal(H, (int(det[0]), int(det[1])))
-    return _DIAG[key]
-
-
-_TABLES = {}
+    diag = _cache(H)[1]
+    key = (int(det[0]), int(det[1]))
+    if key not in diag:
+        diag[key] = HC.diagonal(H, key)
+    return diag[key]
 
 
 def brute_many(H, dets):
@@ -183,12 +191,13 @@ def brute_many(H, dets):
     once, so the result is the correctly rounded sum up to a part in 2^11 of an ulp, as brute()'s math.fsum is; the CPU tests
     compare the two.  (brute() costs about 1 ms per determinant, the C2 records of the GPU test are 84 000.)"""
     assert np.finfo(np.longdouble).eps < 2e-19, "needs the 80-bit long double"
-    if id(H) not in _TABLES:
+    tables = _cache(H)[2]
+    if "TG" not in tables:
         m = 2 * H.norb
         T = np.array([H.t(P, P) for P in range(m)], np.longdouble)
         G = np.array([[0.0 if Q == S else H.v(Q, Q, S, S) - H.v(S, Q, Q, S) for S in range(m)] for Q in range(m)], np.longdouble)
-        _TABLES[id(H)] = (T, G)
-    T, G = _TABLES[id(H)]
+        tables["TG"] = (T, G)
+    T, G = tables["TG"]
     m = 2 * H.norb
     out = np.empty(len(dets))
     for a in range(0, len(dets), 4096):

@@ -10,7 +10,11 @@ weight sums bit for bit on dyadic weights; every sum within proposal_checker.rou
 otherwise (the oracle adds left to right, the model with math.fsum).  Neither had to be changed to follow the reference's text.
 The model with the imp_distance 0 / -1 exception taken out, or with the fold made blind to the order inside a run, fails
 test_model_equals_oracle_on_door_inputs (tried once on a scratch copy: flags fold(..., no_exception=True / order_blind=True),
-kept as test_a_broken_model_is_noticed)."""
+kept as test_a_broken_model_is_noticed).
+
+The plain step (semistochastic = f: the same fold, join_walker2, every zero dropped, the reweighting -- anneal_checker.plain_step)
+against orc_merge_sort_walkers + orc_merge_original_with_spawned2 + orc_join_walker2 on random non-dyadic lists with the same
+draws, both disciplines, bit for bit: test_plain_model_equals_oracle."""
 import ctypes as C
 
 import numpy as np
@@ -204,6 +208,68 @@ def test_a_broken_model_is_noticed(oracle, c2_walk, c2_setup):
     assert AC.invariants(main, sp, prm, no_exc, no_exc["discarded"], no_exc["reset"])          # invariant (b) sees it without any flag rule
     blind = AC.fold(main, sp, prm, order_blind=True)
     assert not (len(blind["up"]) == len(ref["up"]) and np.array_equal(blind["initiator"], ref["initiator"]))
+
+
+# ------------------------------------------------------------------------------------------------ semistochastic = f
+def _oracle_plain_step(oracle, c2_walk, c2_setup, main, sp, prm, rng_mode):
+    """sort, merge, join_walker2 and the reweighting through the oracle's routines; also the generator its joins drew from, as a
+    draw(index of the later walker) for the model: COUNTER stage 2 keyed by that index, REPLAY the stream in join order"""
+    n0 = len(main["up"])
+    ow = oracle.OracleWalk(c2_walk, c2_setup, main, n0 + len(sp["up"]) + 16, list(SEED), rng_mode=rng_mode)
+    L = oracle.lib()
+    L.orc_rng_seek.argtypes = [C.c_void_p, C.c_int, C.c_uint64]
+    L.orc_rannyu.restype = C.c_double
+    L.orc_rannyu.argtypes = [C.c_void_p]
+    rng = oracle.Rng.from_buffer_copy(ow.w.rng)
+
+    def draw(i):
+        L.orc_rng_seek(C.byref(rng), 2, int(i))          # does nothing in the REPLAY discipline
+        return L.orc_rannyu(C.byref(rng))
+    w, nz = ow.w, np.nonzero(sp["wt"])[0]
+    for k, j in enumerate(nz):
+        i = n0 + k
+        w.up[i], w.dn[i], w.wt[i] = int(sp["up"][j]), int(sp["dn"][j]), float(sp["wt"][j])
+        w.imp_distance[i], w.initiator[i] = int(sp["imp_distance"][j]), int(sp["initiator"][j])
+        w.matrix_elements[i] = w.e_num_walker[i] = w.e_den_walker[i] = 1e51
+    n = n0 + len(nz)
+    p = oracle.StepParams(**prm)
+    L.orc_merge_original_with_spawned2.restype = C.c_int64
+    L.orc_join_walker2.restype = C.c_int64
+    L.orc_join_walker2.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+    L.orc_merge_sort_walkers(ow.h, n)
+    n = L.orc_merge_original_with_spawned2(ow.h, n, C.byref(p))
+    n_merged = n
+    n = L.orc_join_walker2(ow.h, n, C.byref(p))
+    ow.w.nwalk = n
+    for i in range(n):
+        w.wt[i] = w.wt[i] * prm["reweight_factor_inv"]
+    ref = ow.walkers(); ow.close()
+    return ref, n_merged, draw
+
+
+@pytest.mark.parametrize("trial", range(8))
+def test_plain_model_equals_oracle(oracle, c2_walk, c2_setup, trial):
+    """random non-dyadic lists, the reference's left-to-right arithmetic, the same draws, both disciplines (odd trials COUNTER)"""
+    main, sp, prm, rng_mode = _inputs_random(oracle, c2_setup, trial)
+    prm = dict(prm, semistochastic=0)
+    if trial >= 4:          # residents of the stochastic space too, some of them small
+        main = {k: v.copy() for k, v in main.items()}
+        rs = np.random.RandomState(trial)
+        out = rs.rand(len(main["up"])) < 0.5
+        main["imp_distance"] = np.where(out & (main["initiator"] < 3), 2, main["imp_distance"]).astype(np.int8)
+        main["wt"] = np.where(out & (main["initiator"] < 3), rs.choice([-0.07, 0.13, 0.2, -0.45, 1.1], len(out)), main["wt"])
+    rs = np.random.RandomState(50 + trial)          # 600 lone children below min_wt on determinants of their own: the joins' candidates
+    ix = rs.choice(len(c2_setup.ct_up), 600, replace=False)
+    sp = dict(up=np.concatenate([sp["up"], c2_setup.ct_up[ix].astype(np.uint64)]), dn=np.concatenate([sp["dn"], c2_setup.ct_dn[ix].astype(np.uint64)]),
+              wt=np.concatenate([sp["wt"], rs.uniform(-0.29, 0.29, 600)]), imp_distance=np.concatenate([sp["imp_distance"], rs.choice([1, 2, 3], 600).astype(np.int8)]),
+              initiator=np.concatenate([sp["initiator"], np.ones(600, np.int8)]))
+    ref, n_merged, draw = _oracle_plain_step(oracle, c2_walk, c2_setup, main, sp, prm, rng_mode)
+    got = AC.plain_step(main, sp, prm, draw, exact=False)
+    assert len(got["heads"]["up"]) == n_merged and got["joins"] > 300
+    assert len(got["up"]) == len(ref["up"])
+    for k in ("up", "dn", "wt", "imp_distance", "initiator"):
+        assert np.array_equal(got[k], ref[k]), k
+    assert not (got["wt"] == 0).any()
 
 
 def test_precondition_refuses_an_input_that_needs_a_draw():

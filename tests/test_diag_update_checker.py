@@ -67,6 +67,27 @@ def test_degenerate_spin_sectors(request, nup, ndn):
         assert all(DU.update(ints, H.norb, 0.0, pqrs, new[0], new[1])[2] == 6 for _, pqrs, new in rec)      # 4 + 2, no exchange, empty loops
 
 
+def test_caches_belong_to_the_hamiltonian_not_to_its_id(heg14):
+    """Hamiltonians built one after the other, each dropped before the next: an address is handed out again once its object is
+    collected, and a cache keyed by id(H) then serves the new Hamiltonian the old one's tables.  Every one gets its own values;
+    and an entry planted under a live Hamiltonian's id for another object is not believed."""
+    from tests import hci_checker as HC
+    dets = DU.seeded_sources((heg14.hf_up, heg14.hf_dn), heg14.norb, heg14.nup, heg14.ndn, 3)
+    seen = set()
+    for k in range(6):
+        H = PC.HegH(heg14.k_vectors() / (1.0 + 0.25 * k), heg14.length_cell * (1.0 + 0.25 * k))          # the same gas in a larger cell
+        own = [HC.diagonal(H, d)[0] for d in dets]
+        seen.add(own[0])
+        assert [DU.brute(H, d)[0] for d in dets] == own, k
+        many = DU.brute_many(H, dets)
+        assert all(abs(float(a) - b) <= 2.0 * DU.U * abs(b) for a, b in zip(many, own)), k
+        del H
+    assert len(seen) == 6          # the six cells really have different elements
+    H = PC.HegH(heg14.k_vectors(), heg14.length_cell)
+    DU._CACHES[id(H)] = (object(), {d: (1e9, 0, 0.0) for d in dets}, {})
+    assert DU.brute(H, dets[0])[0] == HC.diagonal(H, dets[0])[0]
+
+
 def test_bound_is_the_formula():
     assert DU.n_additions(8) == 72 and DU.n_additions(14) == 120
     assert DU.gamma(72) == 72 * DU.U / (1 - 72 * DU.U)
