@@ -654,6 +654,27 @@ int sqmc_gpu_hci_1rdm_pt(sqmc_gpu_ctx *ctx, int64_t n_var, const uint64_t *var_u
  * combine_2 that is not a symmetric one-to-one pair index.  A null pointer or a non-finite entry of rot: SQMC_ERR_BAD_ARG.
  * A refused or failed call leaves integrals_out untouched.  Device memory: (norb (norb + 1) / 2)^2 doubles of work space. */
 int sqmc_gpu_rotate_integrals(sqmc_gpu_ctx *ctx, const double *rot, double *integrals_out);
+/* replaces: get_zeroth_order_variational_greens_function (hci.f90:3849-4050) without its file output: the Green's function of a
+ * variational wavefunction sum c_i |i> of energy e0 with the diagonal of H as the zeroth-order Hamiltonian of the N+-1 electron
+ * spaces, spin-summed, at the frequencies w[0 .. n_w - 1]:
+ *   g_np1[i_w + n_w (p + norb q)] = sum_sigma sum_i c_i c_k / (w - (H_mm - e0)),  m = i + q sigma (q empty in i), k = m - p sigma
+ *   g_nm1[i_w + n_w (p + norb q)] = sum_sigma sum_i c_i c_k / (w - (e0 - H_mm)),  m = i - q sigma (q occupied in i), k = m + p sigma
+ * orbitals 0-based, k in the list, H_mm = hamiltonian_chem of the N+-1 electron determinant m from scratch: the memory of the
+ * reference's G0(n_w, norb, norb).  A term is the rounded product c_i c_k divided by the rounded denominator, as at :3944; only
+ * the order of the additions differs from the reference's.  fermi_sign = 0: no fermionic sign, as the reference (:3944, :3963,
+ * :3984, :4002).  fermi_sign = 1: the matrix elements <a_p (w - (H0 - E0))^-1 a+_q> and <a+_p (w - (E0 - H0))^-1 a_q> of its header
+ * comment (:3859-3860): for p != q a term is multiplied by -(-1)^b (N+1) or (-1)^b (N-1), b = the sigma electrons strictly between
+ * p and q; the diagonals, and the density of states sum_p g(w, p, p), are the same bits in both modes.
+ * The list may be in any order and is sorted by rank here; no floating-point atomics and a fixed order of additions: the same bits
+ * run to run, for every order of the caller's list, and for a frequency whatever other frequencies the call holds.
+ * One of g_np1, g_nm1 may be NULL: that half is not computed.  A frequency on a pole gives what IEEE division gives.
+ * SQMC_ERR_BAD_ARG: both outputs NULL, n_var <= 0, n_w <= 0, a non-finite e0 or w, fermi_sign not 0 or 1, a repeated determinant,
+ * a determinant with other electron numbers than the context's or an orbital beyond norb.  SQMC_ERR_UNSUPPORTED: a context with
+ * time_sym = 1 (pass the determinant-basis expansion, as to sqmc_gpu_hci_1rdm; :3895 stops there too) and every system other than
+ * chem.  A refused call leaves the outputs untouched.  Work memory on the device does not grow with n_var * n_w. */
+int sqmc_gpu_hci_greens_function(sqmc_gpu_ctx *ctx, int64_t n_var, const uint64_t *var_up, const uint64_t *var_dn,
+                                 const double *coeffs, double e0, int32_t n_w, const double *w, int32_t fermi_sign,
+                                 double *g_np1, double *g_nm1);
 /* replaces: the off-diagonal histograms and weight ratios every walk of the reference keeps (off_diag_histograms = .true.,
  * do_walk.f90:104; gen_hist at 1420-1429; filled at 3619-3640 and in add_walker, 7603-7636; max_wt_ratio / min_wt_ratio at 3649-3661,
  * 7610-7622).  Context state, off by default: with it off a step launches exactly the kernels it launches without this entry.  On,

@@ -28,7 +28,7 @@ EXPORTS = [
     "sqmc_gpu_shard_begin", "sqmc_gpu_shard_pack", "sqmc_gpu_shard_finish", "sqmc_gpu_shard_finish_psit", "sqmc_gpu_comm_unique_id", "sqmc_gpu_comm_init", "sqmc_gpu_comm_size",
     "sqmc_gpu_shard_step", "sqmc_gpu_shard_run", "sqmc_gpu_shard_time_split", "sqmc_gpu_get_rng", "sqmc_gpu_set_rng", "sqmc_gpu_tail_stats", "sqmc_gpu_last_tail", "sqmc_gpu_slowest_steps", "sqmc_gpu_set_chained_runs", "sqmc_gpu_spmv_prepare", "sqmc_gpu_davidson",
     "sqmc_gpu_spmv_apply", "sqmc_gpu_spmv_free", "sqmc_gpu_build_spmv_plan", "sqmc_gpu_spmv_sym_upper", "sqmc_gpu_hamiltonian_batch",
-    "sqmc_gpu_propose_batch", "sqmc_gpu_hamiltonian_chem_batch", "sqmc_gpu_build_sparse_ham", "sqmc_gpu_hci_connections", "sqmc_gpu_hci_connections_slice", "sqmc_gpu_hci_pt2", "sqmc_gpu_hci_pt2_stochastic_prepare", "sqmc_gpu_hci_pt2_stochastic_sample", "sqmc_gpu_hci_pt2_stochastic_stats", "sqmc_gpu_hci_pt2_stochastic_free", "sqmc_gpu_hci_set_active_space", "sqmc_gpu_diag_update_batch", "sqmc_gpu_hci_set_diag_update", "sqmc_gpu_hci_connections_record", "sqmc_gpu_hci_1rdm", "sqmc_gpu_hci_1rdm_pt", "sqmc_gpu_rotate_integrals", "sqmc_gpu_free", "sqmc_gpu_set_timing", "sqmc_gpu_get_timing",
+    "sqmc_gpu_propose_batch", "sqmc_gpu_hamiltonian_chem_batch", "sqmc_gpu_build_sparse_ham", "sqmc_gpu_hci_connections", "sqmc_gpu_hci_connections_slice", "sqmc_gpu_hci_pt2", "sqmc_gpu_hci_pt2_stochastic_prepare", "sqmc_gpu_hci_pt2_stochastic_sample", "sqmc_gpu_hci_pt2_stochastic_stats", "sqmc_gpu_hci_pt2_stochastic_free", "sqmc_gpu_hci_set_active_space", "sqmc_gpu_diag_update_batch", "sqmc_gpu_hci_set_diag_update", "sqmc_gpu_hci_connections_record", "sqmc_gpu_hci_1rdm", "sqmc_gpu_hci_1rdm_pt", "sqmc_gpu_rotate_integrals", "sqmc_gpu_hci_greens_function", "sqmc_gpu_free", "sqmc_gpu_set_timing", "sqmc_gpu_get_timing",
     "sqmc_gpu_set_spawn_diagnostics", "sqmc_gpu_reset_spawn_diagnostics", "sqmc_gpu_get_spawn_diagnostics", "sqmc_gpu_debug_bucket_boundaries",
 ]
 
@@ -700,6 +700,27 @@ def _gpuchem_rotate_integrals(self, rot):
     return out
 
 
+def _gpuchem_greens_function(self, up, dn, coeffs, e0, w, fermi_sign=False, parts="both"):
+    """sqmc_gpu_hci_greens_function (get_zeroth_order_variational_greens_function, hci.f90:3849-4050): (G_np1, G_nm1) of a determinant
+    list in any order at the frequencies w, each an (n_w, norb, norb) array indexed [i_w, p, q] (0-based), spin-summed.  fermi_sign
+    False: no fermionic sign, as the reference; True: the matrix elements of a_p .. a+_q and a+_p .. a_q.  parts: "both", "np1" or
+    "nm1"; the half that is not asked for is not computed and comes back as None."""
+    u, d, c, ww = _u64(up), _u64(dn), _f64(coeffs), np.ascontiguousarray(np.atleast_1d(w), np.float64)
+    if not (len(u) == len(d) == len(c)):
+        raise ValueError("up, dn and coeffs differ in length")
+    if parts not in ("both", "np1", "nm1"):
+        raise ValueError("parts must be 'both', 'np1' or 'nm1'")
+    n = self.norb
+    gp = np.zeros(len(ww) * n * n) if parts != "nm1" else None
+    gm = np.zeros(len(ww) * n * n) if parts != "np1" else None
+    self.L.sqmc_gpu_hci_greens_function.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_int32,
+                                                    C.c_void_p, C.c_void_p]
+    _chk(self.L.sqmc_gpu_hci_greens_function(self.h, len(u), _p(u), _p(d), _p(c), float(e0), len(ww), _p(ww), int(fermi_sign),
+                                             None if gp is None else _p(gp), None if gm is None else _p(gm)))
+    shape = lambda a: None if a is None else np.ascontiguousarray(a.reshape(n, n, len(ww)).transpose(2, 1, 0))      # flat index i_w + n_w (p + norb q)
+    return shape(gp), shape(gm)
+
+
 class HeatbathTables(C.Structure):
     """sqmc_heatbath_tables of include/sqmc_gpu.h"""
     _fields_ = [("norb", C.c_int32), ("reserved", C.c_int32), ("one", C.c_void_p), ("two", C.c_void_p), ("three_same", C.c_void_p), ("three_opp", C.c_void_p),
@@ -855,4 +876,5 @@ GpuChem.hci_set_diag_update = _gpuchem_hci_set_diag_update
 GpuChem.hci_connections_record = _gpuchem_hci_connections_record
 GpuChem.one_rdm = _gpuchem_one_rdm
 GpuChem.one_rdm_pt = _gpuchem_one_rdm_pt
+GpuChem.greens_function = _gpuchem_greens_function
 GpuChem.rotate_integrals = _gpuchem_rotate_integrals

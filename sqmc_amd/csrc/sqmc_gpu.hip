@@ -220,6 +220,7 @@ struct sqmc_gpu_ctx {
   ActiveSpace as;             // masks of the HCI generator (sqmc_gpu_hci_set_active_space); mode 0 = none
   double pt2_terms_ms;        // HIP-event time of the last sqmc_gpu_hci_pt2's term kernel (sqmc_gpu_debug_pt2_terms_ms)
   double rdm_var_ms, rdm_pt_ms;      // HIP-event times of the last 1-RDM call: its variational kernels, its PT kernels over all slices (sqmc_gpu_debug_rdm_ms)
+  double gf_ms[2];                   // HIP-event times of the last sqmc_gpu_hci_greens_function: the pole passes, the term passes (sqmc_gpu_debug_greens_ms)
   double rot_ms[3];                  // HIP-event times of the last sqmc_gpu_rotate_integrals: half 1, half 2, the one-body block (sqmc_gpu_debug_rotate_ms)
   u64 *d_sdiag; bool sdiag_on;      // spawn diagnostics (sqmc_gpu_set_spawn_diagnostics): SDIAG_REPL + 1 sets of SDIAG_WORDS words, allocated at first use; on: steps launch k_spawn's diagnostic form and enqueue no head ahead
   int du_mode;                // H_aa of the PT2 stages (sqmc_gpu_hci_set_diag_update): 0 from scratch, 1 / 2 get_new_diag_elem on one lane / 16 lanes
@@ -277,6 +278,7 @@ static inline u64 *spawn_diag(const sqmc_gpu_ctx *c) { return c->sdiag_on ? c->d
 #include "spmv_kernels.h"
 #include "rdm_kernels.h"
 #include "rotate_kernels.h"
+#include "greens_kernels.h"
 
 // ================================================================================ ABI
 extern "C" {
@@ -1756,6 +1758,7 @@ int sqmc_gpu_debug_premerge(sqmc_gpu_ctx *c, int64_t cap, int64_t *n0, int64_t *
 #include "abi_shard.inc"
 #include "abi_doors.inc"
 #include "abi_rdm.inc"
+#include "abi_greens.inc"
 #include "abi_rotate.inc"
 #include "abi_spawn_diag.inc"
 #include "davidson.inc"

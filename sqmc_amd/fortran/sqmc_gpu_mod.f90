@@ -24,7 +24,7 @@ module sqmc_gpu_mod
   public :: sqmc_gpu_hci_pt2_stochastic_prepare, sqmc_gpu_hci_pt2_stochastic_sample, sqmc_gpu_hci_pt2_stochastic_stats, sqmc_gpu_hci_pt2_stochastic_free
   public :: sqmc_gpu_set_spawn_diagnostics, sqmc_gpu_reset_spawn_diagnostics, sqmc_gpu_get_spawn_diagnostics
   public :: sqmc_gpu_set_hubbardk_space_sym, sqmc_gpu_hubbardk_sym_images, sqmc_gpu_debug_bucket_boundaries
-  public :: sqmc_gpu_hci_1rdm, sqmc_gpu_hci_1rdm_pt, sqmc_gpu_rotate_integrals
+  public :: sqmc_gpu_hci_1rdm, sqmc_gpu_hci_1rdm_pt, sqmc_gpu_rotate_integrals, sqmc_gpu_hci_greens_function
   public :: sqmc_gpu_check
 
   integer(c_int), parameter, public :: SQMC_RNG_REPLAY = 0, SQMC_RNG_COUNTER = 1
@@ -206,6 +206,14 @@ module sqmc_gpu_mod
     ! in the layout of sqmc_chem_cfg%integrals.  Chem contexts only
     integer(c_int) function sqmc_gpu_rotate_integrals(ctx, rot, integrals_out) bind(C, name='sqmc_gpu_rotate_integrals')
       import; type(c_ptr), value :: ctx; real(c_double), intent(in) :: rot(*); real(c_double), intent(out) :: integrals_out(*)
+    end function
+    ! get_zeroth_order_variational_greens_function (hci.f90:3849-4050) without its files: g_np1(n_w, norb, norb) and
+    ! g_nm1(n_w, norb, norb) = c_loc of the arrays, or c_null_ptr for a half that is not wanted; fermi_sign = 0 is the reference
+    integer(c_int) function sqmc_gpu_hci_greens_function(ctx, n_var, var_up, var_dn, coeffs, e0, n_w, w, fermi_sign, g_np1, g_nm1) &
+        bind(C, name='sqmc_gpu_hci_greens_function')
+      import; type(c_ptr), value :: ctx; integer(c_int64_t), value :: n_var; integer(c_int64_t), intent(in) :: var_up(*), var_dn(*)
+      real(c_double), intent(in) :: coeffs(*); real(c_double), value :: e0; integer(c_int32_t), value :: n_w
+      real(c_double), intent(in) :: w(*); integer(c_int32_t), value :: fermi_sign; type(c_ptr), value :: g_np1, g_nm1
     end function
     ! second_order_pt_alias (hci.f90:1314-1660): the variational wavefunction and the work buffers stay on the device (prepare),
     ! one call per sample with the merged draws (0-based ids, ascending, and their counts), free at the end; chem and heg contexts

@@ -13,6 +13,8 @@ Mirrors (file:line relative to the reference's src/):
   tau ramp, e_trial, reweight factor     do_walk.f90:2171-2184, 2880-2923
   davidson_sparse                        more_tools.f90:2018-2244
 """
+import os
+
 import numpy as np
 
 from ._lib import GpuChem, SpmvPlan, PopCtl, RNG_COUNTER
@@ -1720,6 +1722,171 @@ def write_natorb_fcidump(path, host, packed):
                 if abs(x) > 1e-8:
                     f.write(rec % (x, order[p], order[q], 0, 0))
         f.write(rec % (v[ChemHost._index(c2, n1, n1, n1, n1)], 0, 0, 0, 0))
+
+
+# ------------------------------------------------------------------------- Green's function and density of states
+GREENS_HEADERS = {"G0_N+1": " w,p,q,G0_{N+1}(w,p,q)", "G0_N-1": " w,p,q,G0_{N-1}(w,p,q)", "rho": " Density of states: w, rho_{N+1}(w),rho_{N-1}(w),rho_tot(w)"}
+GREENS_CUT = 1e-8
+
+
+def greens_grid(n_w, w_min, w_max):
+    """hci.f90:750-752: w(i) = w_min + (w_max - w_min) * (i - 1) / (n_w - 1), i = 1 .. n_w.  n_w < 2 is refused: the reference divides
+    0 by 0 there."""
+    n_w = int(n_w)
+    if n_w < 2:
+        raise ValueError("greens_grid: n_w = %d; the grid needs two frequencies at least" % n_w)
+    w_min, w_max = float(w_min), float(w_max)
+    return np.array([w_min + (w_max - w_min) * float(i) / float(n_w - 1) for i in range(n_w)])
+
+
+def hci_greens_function(host, up, dn, wts, e0, w, fermi_sign=False):
+    """get_zeroth_order_variational_greens_function as perform_hci calls it (hci.f90:748-759): state 1 of wts ([n] or [n, n_states])
+    at energy e0 and the frequencies w; (G_np1, G_nm1) indexed [i_w, p, q] as GpuChem.greens_function's.  The reference stops on a
+    time-symmetrised wavefunction (:3895); here it is expanded in determinants first and the context is one with time_sym off, as in
+    hci_one_rdm.  fermi_sign False: the reference's sums (no fermionic sign); True: the matrix elements of its header comment."""
+    import copy
+    c = np.asarray(wts, float)
+    c = c.reshape(len(c), -1)[:, 0]
+    plain = host
+    if bool(getattr(host, "time_sym", False)):
+        plain = copy.copy(host)
+        plain.time_sym = False
+        up, dn, c = time_symmetrized_to_dets(up, dn, c, getattr(host, "z", 1))
+    g = plain.gpu()
+    try:
+        return g.greens_function(up, dn, c, float(e0), w, fermi_sign)
+    finally:
+        g.close()
+
+
+def greens_function_host(host, up, dn, coeffs, e0, w, fermi_sign=False):
+    """The sums of GpuChem.greens_function in numpy on the host, determinant basis, for a ChemHost: kept as the yardstick the device
+    call is timed against (tools/greens_time.py).  One vectorised pass over the list per (sigma, q, p): bit tests, the partner's place by
+    searchsorted in the sorted list, the terms' quotients added up per frequency.  H_mm = H_ii +- (h_q + sum_j (J - K)_qj n_j sigma +
+    sum_j J_qj n_j sigma'), in an order of additions of its own: it agrees with the library to rounding, not bit for bit."""
+    n, n1, c2 = host.norb, host.norb + 1, host.combine_2
+    idx = np.arange(1, n1)
+    ints = np.asarray(host.integrals, float)
+    h1 = ints[ChemHost._index(c2, idx, idx, np.full(n, n1), np.full(n, n1))]
+    P, Q = np.meshgrid(idx, idx, indexing="ij")
+    J = ints[ChemHost._index(c2, P.ravel(), P.ravel(), Q.ravel(), Q.ravel())].reshape(n, n)
+    K = ints[ChemHost._index(c2, P.ravel(), Q.ravel(), Q.ravel(), P.ravel())].reshape(n, n)
+    JK, nuc = J - K, float(ints[ChemHost._index(c2, n1, n1, n1, n1)])
+    up, dn, c = np.asarray(up, np.uint64), np.asarray(dn, np.uint64), np.asarray(coeffs, float)
+    w = np.atleast_1d(np.asarray(w, float))
+    nd = len(up)
+    shifts = np.arange(n, dtype=np.uint64)
+    occ = [((s[:, None] >> shifts) & np.uint64(1)).astype(float) for s in (up, dn)]
+    h_i = (occ[0] + occ[1]) @ h1 + 0.5 * (np.einsum("ip,pq,iq->i", occ[0], JK, occ[0]) + np.einsum("ip,pq,iq->i", occ[1], JK, occ[1])) \
+        + np.einsum("ip,pq,iq->i", occ[0], J, occ[1]) + nuc
+    step = [h1[None, :] + occ[0] @ JK + occ[1] @ J, h1[None, :] + occ[1] @ JK + occ[0] @ J]      # H(i + q sigma) - H(i) = H(i) - H(i - q sigma)
+    uniq = [np.unique(up), np.unique(dn)]
+    place = [np.searchsorted(uniq[0], up), np.searchsorted(uniq[1], dn)]
+    key = place[0].astype(np.int64) * len(uniq[1]) + place[1]
+    order = np.argsort(key, kind="stable")
+    skey = key[order]
+    if nd > 1 and np.any(skey[1:] == skey[:-1]):
+        raise ValueError("greens_function_host: a determinant appears twice")
+    out = {True: np.zeros((len(w), n, n)), False: np.zeros((len(w), n, n))}
+    one = np.uint64(1)
+
+    def add(np1, p, q, i, k, sigma, s):
+        a = c[i] * c[k]
+        if fermi_sign and p != q:
+            lo, hi = min(p, q), max(p, q)
+            between = np.uint64(((1 << hi) - 1) & ~((1 << (lo + 1)) - 1))
+            par = np.zeros(len(i), np.int64)
+            v = s & between
+            while np.any(v):
+                par += (v & one).astype(np.int64); v = v >> one
+            a = np.where((par & 1) != (1 if np1 else 0), -a, a)
+        x = (h_i[i] + step[sigma][i, q] - e0) if np1 else (e0 - (h_i[i] - step[sigma][i, q]))
+        for b0 in range(0, len(i), 16384):
+            out[np1][:, p, q] += (a[None, b0:b0 + 16384] / (w[:, None] - x[None, b0:b0 + 16384])).sum(axis=1)
+
+    for sigma in (0, 1):
+        s_all = dn if sigma else up
+        for q in range(n):
+            has_q = (s_all >> np.uint64(q)) & one == one
+            for p in range(n):
+                has_p = (s_all >> np.uint64(p)) & one == one
+                for np1 in (True, False):
+                    ok = (~has_q if np1 else has_q) & ((has_p if np1 else ~has_p) if p != q else True)
+                    i = np.nonzero(ok)[0]
+                    if not len(i):
+                        continue
+                    if p == q:
+                        add(np1, p, q, i, i, sigma, s_all[i])
+                        continue
+                    s2 = s_all[i] ^ (one << np.uint64(q)) ^ (one << np.uint64(p))
+                    at = np.searchsorted(uniq[sigma], s2)
+                    good = at < len(uniq[sigma])
+                    good[good] = uniq[sigma][at[good]] == s2[good]
+                    i, at = i[good], at[good]
+                    k2 = (place[0][i].astype(np.int64) * len(uniq[1]) + at) if sigma else (at.astype(np.int64) * len(uniq[1]) + place[1][i])
+                    j = np.searchsorted(skey, k2)
+                    hit = j < nd
+                    hit[hit] = skey[j[hit]] == k2[hit]
+                    if np.any(hit):
+                        add(np1, p, q, i[hit], order[j[hit]], sigma, s_all[i[hit]])
+    return out[True], out[False]
+
+
+def density_of_states(G_np1, G_nm1):
+    """hci.f90:4010-4046: (n_w, 3) = rho_{N+1}(w) = sum_p G0_np1(w, p, p) added in the order p = 1 .. norb, rho_{N-1}(w) likewise, and
+    their sum"""
+    gp, gm = np.asarray(G_np1, float), np.asarray(G_nm1, float)
+    out = np.zeros((gp.shape[0], 3))
+    for p in range(gp.shape[1]):
+        out[:, 0] = out[:, 0] + gp[:, p, p]
+        out[:, 1] = out[:, 1] + gm[:, p, p]
+    out[:, 2] = out[:, 0] + out[:, 1]
+    return out
+
+
+def _es24(x):
+    """Fortran es24.16e3"""
+    m, e = ("%.16e" % x).split("e")
+    return ("%sE%+04d" % (m, int(e))).rjust(24)
+
+
+def write_greens_function(directory, w, G_np1, G_nm1):
+    """The three files of get_zeroth_order_variational_greens_function (hci.f90:4013-4047) in `directory`: G0_N+1 and G0_N-1 with the
+    reference's header line and one record (w, p, q, G) per entry with abs > 1e-8, in the reference's order (i_w, then q, then p;
+    p and q 1-based in the program's orbital order), and rho with (w, rho_{N+1}, rho_{N-1}, rho_tot) per frequency.  The reference's
+    records are list-directed, their spacing the compiler's choice; here reals are es24.16e3 and labels i5.  Like the reference's
+    status='new' nothing is overwritten: FileExistsError if any of the three exists, before anything is written."""
+    w, gp, gm = np.asarray(w, float), np.asarray(G_np1, float), np.asarray(G_nm1, float)
+    if gp.shape != gm.shape or gp.ndim != 3 or gp.shape[0] != len(w) or gp.shape[1] != gp.shape[2]:
+        raise ValueError("write_greens_function: G_np1 %r, G_nm1 %r, %d frequencies" % (gp.shape, gm.shape, len(w)))
+    paths = {name: os.path.join(directory, name) for name in GREENS_HEADERS}
+    for path in paths.values():
+        if os.path.exists(path):
+            raise FileExistsError("sqmc_amd: %s exists; the Green's function is written to new files only" % path)
+    rho = density_of_states(gp, gm)
+    for name, g in (("G0_N+1", gp), ("G0_N-1", gm)):
+        with open(paths[name], "x") as f:
+            f.write(GREENS_HEADERS[name] + "\n")
+            for i_w in range(len(w)):
+                blk = g[i_w].T                                     # [q, p]
+                for q, p in zip(*np.nonzero(np.abs(blk) > GREENS_CUT)):
+                    f.write("%s%5d%5d%s\n" % (_es24(w[i_w]), p + 1, q + 1, _es24(blk[q, p])))
+    with open(paths["rho"], "x") as f:
+        f.write(GREENS_HEADERS["rho"] + "\n")
+        for i_w in range(len(w)):
+            f.write(_es24(w[i_w]) + "".join(_es24(x) for x in rho[i_w]) + "\n")
+    return paths
+
+
+def read_greens_function(path):
+    """A file of write_greens_function.  G0_N+1 / G0_N-1: (header, [(w, p, q, value)]) with p and q as written (1-based), in file
+    order; rho: (header, array (n_w, 4))"""
+    with open(path) as f:
+        header = f.readline().rstrip("\n")
+        rows = [l.rstrip("\n") for l in f if l.strip()]
+    if "Density of states" in header:                # fixed columns: an es24.16e3 field of a negative number touches its left neighbour
+        return header, np.array([[float(r[24 * k:24 * k + 24]) for k in range(4)] for r in rows]).reshape(-1, 4)
+    return header, [(float(r[0:24]), int(r[24:29]), int(r[29:34]), float(r[34:58])) for r in rows]
 
 
 # ------------------------------------------------------------------------- Fortran host deck

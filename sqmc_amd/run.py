@@ -11,7 +11,10 @@ shipped decks (C2_v2z_curve/*/i_1sigma_g) run unchanged next to their FCIDUMP an
 (hci.f90:683-745): the 1-RDM of the variational wavefunction (or its lowest-order PT correction) and its natural orbitals by
 irrep, printed as the reference prints them; without --rotate-integrals the run stops there, with it the library rotates the
 integrals into the natural orbitals (sqmc_gpu_rotate_integrals) and the run writes them as FCIDUMP_eps_var=... for the next HCI
-run, where the reference stops too (:745).  Host-side plumbing: every piece that scales with the number of determinants runs in libsqmc_gpu."""
+run, where the reference stops too (:745).  `&greens_function get_greens_function=t n_w=... w_min=... w_max=... /` (hci.f90:748-759): the
+zeroth-order Green's function of state 1 on the device (sqmc_gpu_hci_greens_function), written as G0_N+1, G0_N-1 and rho into the
+working directory, after which the run goes on to the PT stage as the reference does; --greens-signed selects the matrix elements
+with their fermionic sign (the reference applies none).  Host-side plumbing: every piece that scales with the number of determinants runs in libsqmc_gpu."""
 import argparse
 import os
 import re
@@ -91,6 +94,12 @@ def parse_hci_deck(text):
     nat = nl.get("natorb", {})               # hci.f90:683-745
     deck["get_natorbs"] = _logical(nat["get_natorbs"][0]) if "get_natorbs" in nat else False
     deck["use_pt"] = _logical(nat["use_pt"][0]) if "use_pt" in nat else False
+    gf = nl.get("greens_function", {})       # hci.f90:748-759; n_w = 20 unless given
+    real = lambda v: float(v.lower().replace("d", "e"))
+    deck["get_greens_function"] = _logical(gf["get_greens_function"][0]) if "get_greens_function" in gf else False
+    deck["n_w"] = int(real(gf["n_w"][0])) if "n_w" in gf else 20
+    deck["w_min"] = real(gf["w_min"][0]) if "w_min" in gf else None
+    deck["w_max"] = real(gf["w_max"][0]) if "w_max" in gf else None
     if deck["hamiltonian_type"] == "heg":              # read_heg, heg.f90:102-170
         deck["n_dim"] = int(_numbers(lines[5], 1)[0]); deck["r_s"] = _numbers(lines[6], 1)[0]
         ne, nu = _numbers(lines[7], 2)
@@ -115,6 +124,8 @@ def run_hci_heg(deck, out=sys.stdout, pt_on_device=False, pt_diag_update=0):
     older output format the e2e fixtures were produced with; Madelung total, correlation energy)."""
     if deck.get("get_natorbs"):
         raise SystemExit("Natural orbitals only implemented for chem so far")          # hci.f90:684
+    if deck.get("get_greens_function"):
+        raise SystemExit("sqmc_amd: &greens_function is built for chem only (the reference calls hamiltonian_chem there, hci.f90:3936)")
     import torch            # noqa: F401
     import sqmc_amd
     from . import host as H
@@ -219,14 +230,44 @@ def run_natorbs(deck, h, up, dn, wts, energy, p, one_rdm_path=None, natorb_fcidu
     return res
 
 
-def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False, pt_diag_update=0, one_rdm_path=None, natorb_fcidump=None):
+def _greens_checks(deck):
+    """what stops a run with &greens_function get_greens_function = t before any work is done"""
+    from . import host as H
+    if deck["w_min"] is None or deck["w_max"] is None:
+        raise SystemExit("sqmc_amd: &greens_function needs w_min and w_max")
+    if deck["n_w"] < 2:
+        raise SystemExit("sqmc_amd: &greens_function n_w =%d; the frequency grid needs two points at least (hci.f90:751 divides by n_w - 1)" % deck["n_w"])
+    for name in H.GREENS_HEADERS:                    # open(60, file='G0_N+1', status='new') and its two neighbours
+        if os.path.exists(os.path.join(os.getcwd(), name)):
+            raise FileExistsError("sqmc_amd: %s exists; the Green's function is written to new files only" % os.path.join(os.getcwd(), name))
+
+
+def run_greens(deck, h, up, dn, wts, energy, p, signed=False):
+    """&greens_function get_greens_function = t (hci.f90:748-759): the reference's three list-directed lines in fixed formats (i12,
+    es24.16e3), the Green's function of state 1 on the device, its three files in the working directory"""
+    from . import host as H
+    w = H.greens_grid(deck["n_w"], deck["w_min"], deck["w_max"])
+    p(" About to compute Green's function for%12d frequencies:" % len(w))
+    p("".join(H._es24(x) for x in w))
+    p(" E_0 =" + H._es24(float(energy[0])))
+    gp, gm = H.hci_greens_function(h, up, dn, wts, float(energy[0]), w, fermi_sign=signed)
+    H.write_greens_function(os.getcwd(), w, gp, gm)
+    return w, gp, gm
+
+
+def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False, pt_diag_update=0, one_rdm_path=None, natorb_fcidump=None, greens_signed=False):
     """pt_on_device: the samples of the semistochastic PT are evaluated by the library (host.hci_pt2_stochastic on_device);
     pt_diag_update: 0 / 1 / 2, how the PT stage forms H_aa (host.hci_pt2); one_rdm_path: with &natorb get_natorbs = t, also save the
     1-RDM there as .npy; natorb_fcidump: with &natorb get_natorbs = t, rotate the integrals into the natural orbitals and write them
     to this new file (True: the reference's name, FCIDUMP_eps_var=<smallest eps_var>, in the working directory); the result then
-    holds natorb_integrals (packed, the host's combine_2) and natorb_fcidump (the path).  None: the run ends on NATORB_STOP."""
+    holds natorb_integrals (packed, the host's combine_2) and natorb_fcidump (the path).  None: the run ends on NATORB_STOP.
+    greens_signed: with &greens_function get_greens_function = t, fermi_sign = 1 instead of the reference's sums; the result then holds
+    greens = (w, G_np1, G_nm1)."""
     if deck["hamiltonian_type"] == "heg":
         return run_hci_heg(deck, out, pt_on_device, pt_diag_update)
+    want_greens = bool(deck.get("get_greens_function")) and not deck.get("get_natorbs")      # get_natorbs stops first (hci.f90:745)
+    if want_greens:
+        _greens_checks(deck)
     import torch            # noqa: F401  one libamdhip64 per process
     import sqmc_amd
     from . import host as H
@@ -264,6 +305,7 @@ def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False, pt_diag
         if natorb_fcidump is True:
             natorb_fcidump = H.natorb_fcidump_name(min([eps_var] + deck["eps_var_sched"]))
         return run_natorbs(deck, h, up, dn, wts, energy, p, one_rdm_path, natorb_fcidump)
+    greens = run_greens(deck, h, up, dn, wts, energy, p, greens_signed) if want_greens else None
     results = []
     for i in range(n_states):
         if deck["n_mc"] > 0 and deck["eps_pt_big"] > deck["eps_pt"]:
@@ -296,7 +338,10 @@ def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False, pt_diag
           % (i + 1, eps_var, deck["eps_pt"], len(up), nconn, energy[i], de, de, energy[i] + de))
         results.append((float(energy[i]), float(de), int(nconn)))
     p("\nsqmc_amd: variational stage %.2f s, PT stage %.2f s on the GPU path" % (t1 - t0, time.perf_counter() - t1))
-    return dict(ndets=len(up), states=results)
+    res = dict(ndets=len(up), states=results)
+    if greens is not None:
+        res["greens"] = greens
+    return res
 
 
 def _es71(x):
@@ -323,6 +368,8 @@ def main(argv=None):
     ap.add_argument("--one-rdm", default=None, metavar="PATH", help="HCI decks with &natorb get_natorbs = t: also save the (norb, norb) 1-RDM as a .npy file")
     ap.add_argument("--rotate-integrals", nargs="?", const=True, default=None, metavar="PATH", help="HCI decks with &natorb get_natorbs = t: rotate the integrals "
                     "into the natural orbitals on the device and write them to PATH, a new file (default: FCIDUMP_eps_var=<smallest eps_var>, the reference's name)")
+    ap.add_argument("--greens-signed", action="store_true", help="HCI decks with &greens_function get_greens_function = t: the matrix elements with their "
+                    "fermionic sign (fermi_sign = 1) instead of the reference's sums, which apply none")
     a = ap.parse_args(argv)
     text = open(a.input).read() if a.input else sys.stdin.read()
     lines = [l for l in text.splitlines() if l.strip() and not l.lstrip().startswith("!")]
@@ -332,7 +379,8 @@ def main(argv=None):
         return run_walk(parse_walk_deck(text), a.fcidump, walkalize=a.walkalize, psit_con_in=a.psit_con_in, psit_con_out=a.psit_con_out,
                         dtm_elems_in=a.dtm_elems_in, dtm_elems_out=a.dtm_elems_out, spawn_histograms=a.spawn_histograms)
     deck = parse_hci_deck(text)
-    return run_hci(deck, a.fcidump, pt_on_device=a.pt_on_device, pt_diag_update=a.pt_diag_update, one_rdm_path=a.one_rdm, natorb_fcidump=a.rotate_integrals)
+    return run_hci(deck, a.fcidump, pt_on_device=a.pt_on_device, pt_diag_update=a.pt_diag_update, one_rdm_path=a.one_rdm, natorb_fcidump=a.rotate_integrals,
+                   greens_signed=a.greens_signed)
 
 
 if __name__ == "__main__":
