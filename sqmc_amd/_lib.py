@@ -324,6 +324,21 @@ class GpuChem:
         _chk(self.L.sqmc_gpu_annihilate(self.h, C.byref(p), len(arrs[0]), *[_p(a) for a in arrs], _p(out)))
         return out
 
+    def debug_premerge(self):
+        """sqmc_gpu_debug_premerge (debugging aid, not part of the ABI in include/): the list the last semistochastic radix-tail step or
+        sqmc_gpu_annihilate call stood on in front of its merge, as dict(res_wt: the residents' weights after death/clone and the
+        projection; up, dn, wt, imp_distance, initiator: the spawn records in creation order, weight 0 meaning no walker)"""
+        f = self.L.sqmc_gpu_debug_premerge
+        f.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8
+        n0, ns = C.c_int64(), C.c_int64()
+        _chk(f(self.h, 0, C.byref(n0), C.byref(ns), None, None, None, None, None, None))
+        n0, ns = n0.value, ns.value
+        out = dict(res_wt=np.zeros(n0), up=np.zeros(ns, np.uint64), dn=np.zeros(ns, np.uint64), wt=np.zeros(ns), imp_distance=np.zeros(ns, np.int8),
+                   initiator=np.zeros(ns, np.int8))
+        a, b = C.c_int64(), C.c_int64()
+        _chk(f(self.h, n0 + ns, C.byref(a), C.byref(b), *[_p(out[k]) for k in ("res_wt", "up", "dn", "wt", "imp_distance", "initiator")]))
+        return out
+
     def run(self, pc, nsteps, keep_stats=True):
         """sqmc_gpu_run: nsteps steps with the population control done inside the library."""
         stats = np.zeros((nsteps, 16)) if keep_stats else None

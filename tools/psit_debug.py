@@ -1,7 +1,6 @@
 """Lock-step run of the hf_to_psit step on the GPU and in the oracle that, at the first step whose sums differ, compares the two lists
 in front of the merge (residents, spawn records): where a difference comes from.  Debugging aid.
 usage: python tools/psit_debug.py [nsteps] [rng_mode] [w_begin] [target]"""
-import ctypes as C
 import os
 import sys
 import numpy as np
@@ -35,18 +34,8 @@ n_ct = len(s.ct_up)
 
 
 def gpu_premerge():
-    f = g.L.sqmc_gpu_debug_premerge
-    f.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8
-    n0, ns = C.c_int64(), C.c_int64()
-    z = np.zeros(1)
-    f(g.h, 0, C.byref(n0), C.byref(ns), None, None, None, None, None, None)
-    n0, ns = n0.value, ns.value
-    rw, su, sd, sw = np.zeros(n0), np.zeros(ns, np.uint64), np.zeros(ns, np.uint64), np.zeros(ns)
-    sdd, si = np.zeros(ns, np.int8), np.zeros(ns, np.int8)
-    a, b = C.c_int64(), C.c_int64()
-    p = lambda x: x.ctypes.data_as(C.c_void_p)
-    f(g.h, n0 + ns, C.byref(a), C.byref(b), p(rw), p(su), p(sd), p(sw), p(sdd), p(si))
-    return n0, rw, su, sd, sw, sdd, si
+    pm = g.debug_premerge()
+    return len(pm["res_wt"]), pm["res_wt"], pm["up"], pm["dn"], pm["wt"], pm["imp_distance"], pm["initiator"]
 
 
 for it in range(nsteps):
