@@ -3,42 +3,39 @@
 // image, the walker SoA types and the launch helpers defined there); not a standalone header.
 
 // ---------------------------------------------------------------- batch doors
-int sqmc_gpu_hamiltonian_batch(sqmc_gpu_ctx *c, int64_t n, const uint64_t *iu, const uint64_t *id, const uint64_t *ju, const uint64_t *jd, double *h) {
+extern "C++" {
+template <class K>
+static int ham_batch(K kern, const char *who, sqmc_gpu_ctx *c, int64_t n, const uint64_t *iu, const uint64_t *id, const uint64_t *ju, const uint64_t *jd, double *h) {
   if (!c) return fail(SQMC_ERR_BAD_ARG, "null ctx");
   if (n <= 0) return SQMC_OK;
-  u64 *d[4]; double *dh;
-  const uint64_t *src[4] = {iu, id, ju, jd};
-  for (int k = 0; k < 4; k++) { HIPCHK(hipMalloc(&d[k], n * 8)); HIPCHK(hipMemcpy(d[k], src[k], n * 8, hipMemcpyHostToDevice)); }
-  HIPCHK(hipMalloc(&dh, n * 8));
-  hipLaunchKernelGGL(k_ham_batch, dim3(nblk(n)), dim3(TPB), 0, c->st, c->dev, d[0], d[1], d[2], d[3], dh, (long long)n);
+  DevScratch s(c->st);
+  u64 *d[4]; const uint64_t *src[4] = {iu, id, ju, jd};
+  for (int k = 0; k < 4; k++) d[k] = s.take<u64>(n);
+  double *dh = s.take<double>(n);
+  if (!s.ok()) return hip_fail(who, s.err());
+  for (int k = 0; k < 4; k++) HIPCHK(hipMemcpy(d[k], src[k], n * 8, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(kern, dim3(nblk(n)), dim3(TPB), 0, c->st, c->dev, d[0], d[1], d[2], d[3], dh, (long long)n);
   HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(c->st));
   HIPCHK(hipMemcpy(h, dh, n * 8, hipMemcpyDeviceToHost));
-  for (int k = 0; k < 4; k++) hipFree(d[k]);
-  hipFree(dh);
   return SQMC_OK;
 }
-
+}
+int sqmc_gpu_hamiltonian_batch(sqmc_gpu_ctx *c, int64_t n, const uint64_t *iu, const uint64_t *id, const uint64_t *ju, const uint64_t *jd, double *h) {
+  return ham_batch(k_ham_batch, "sqmc_gpu_hamiltonian_batch", c, n, iu, id, ju, jd, h);
+}
 int sqmc_gpu_hamiltonian_chem_batch(sqmc_gpu_ctx *c, int64_t n, const uint64_t *iu, const uint64_t *id, const uint64_t *ju, const uint64_t *jd, double *h) {
-  if (!c) return fail(SQMC_ERR_BAD_ARG, "null ctx");
-  if (n <= 0) return SQMC_OK;
-  u64 *d[4]; double *dh;
-  const uint64_t *src[4] = {iu, id, ju, jd};
-  for (int k = 0; k < 4; k++) { HIPCHK(hipMalloc(&d[k], n * 8)); HIPCHK(hipMemcpy(d[k], src[k], n * 8, hipMemcpyHostToDevice)); }
-  HIPCHK(hipMalloc(&dh, n * 8));
-  hipLaunchKernelGGL(k_ham_chem_batch, dim3(nblk(n)), dim3(TPB), 0, c->st, c->dev, d[0], d[1], d[2], d[3], dh, (long long)n);
-  HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(c->st));
-  HIPCHK(hipMemcpy(h, dh, n * 8, hipMemcpyDeviceToHost));
-  for (int k = 0; k < 4; k++) hipFree(d[k]);
-  hipFree(dh);
-  return SQMC_OK;
+  return ham_batch(k_ham_chem_batch, "sqmc_gpu_hamiltonian_chem_batch", c, n, iu, id, ju, jd, h);
 }
 
 // Rows of the sparse Hamiltonian of a sorted determinant list on the device, as generate_sparse_ham_chem_upper_triangular stores
 // them (diagonal first, then the columns j < i ascending; 1-based indices): counts, offsets, indices, values and the total.
 // Default: candidates from string groups (hbuild_kernels.h), cost ~ sum of group sizes; SQMC_HAM_ALLPAIRS=1: every pair tested
 // (k_build_ham), the cross-check of the tests.  du, dd: the list on the device; up, dn: the same on the host.
+// The rows go to `out` (didx, dval); every other buffer allocated here is released before returning.
+static ScanWork scan_work(u64 *state, long long tiles) { ScanWork sw; sw.state = state; sw.ticket = (u32 *)(state + tiles); sw.cap_tiles = tiles; sw.self_clear = true; return sw; }
 static int ham_rows_dev(sqmc_gpu_ctx *c, int64_t n, const uint64_t *up, const uint64_t *dn, const u64 *du, const u64 *dd, u64 *dcnt, u64 *doff, u64 *dtot,
-                        ScanWork &sw, u64 *total_out, long long **didx_out, double **dval_out) {
+                        ScanWork &sw, DevScratch &out, u64 *total_out, long long **didx_out, double **dval_out) {
+  const char *who = "sparse Hamiltonian rows";
   hipStream_t st = c->st;
   static const bool allpairs = getenv("SQMC_HAM_ALLPAIRS") != nullptr;
   if (allpairs || c->htab.sys_type != 0 || n < 64) {
@@ -46,8 +43,8 @@ static int ham_rows_dev(sqmc_gpu_ctx *c, int64_t n, const uint64_t *up, const ui
     device_excl_scan_u64(dcnt, doff, n, dtot, sw, st);
     u64 total = 0;
     HIPCHK(hipMemcpyAsync(&total, dtot, 8, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st));
-    long long *didx; double *dval;
-    HIPCHK(hipMalloc(&didx, (total + 1) * 8)); HIPCHK(hipMalloc(&dval, (total + 1) * 8));
+    long long *didx = out.take<long long>(total + 1); double *dval = out.take<double>(total + 1);
+    if (!out.ok()) return hip_fail(who, out.err());
     hipLaunchKernelGGL(k_build_ham, dim3(nblk(n)), dim3(TPB), 0, st, c->dev, du, dd, (long long)n, 1, dcnt, doff, didx, dval);
     HIPCHK(hipGetLastError());
     *total_out = total; *didx_out = didx; *dval_out = dval;
@@ -69,36 +66,41 @@ static int ham_rows_dev(sqmc_gpu_ctx *c, int64_t n, const uint64_t *up, const ui
   }
   { u32 acc = 0; for (int s2 = 0; s2 < NS; s2++) { const u32 cn = dhi[s2]; dlo[s2] = acc; acc += cn; dhi[s2] = dlo[s2]; } }
   for (int64_t i = 0; i < n; i++) perm_d[dhi[sid_dn[i]]++] = (u32)i;      // ascending inside every beta group
-  u64 *dS, *ncnt, *nptr; u32 *dsu, *dsd, *dulo, *duhi, *ddlo, *ddhi, *dperm, *dnbr;
-  HIPCHK(hipMalloc(&dS, NS * 8)); HIPCHK(hipMalloc(&ncnt, (NS + 1) * 8)); HIPCHK(hipMalloc(&nptr, (NS + 1) * 8));
-  HIPCHK(hipMalloc(&dsu, n * 4)); HIPCHK(hipMalloc(&dsd, n * 4)); HIPCHK(hipMalloc(&dulo, NS * 4)); HIPCHK(hipMalloc(&duhi, NS * 4));
-  HIPCHK(hipMalloc(&ddlo, NS * 4)); HIPCHK(hipMalloc(&ddhi, NS * 4)); HIPCHK(hipMalloc(&dperm, n * 4));
+  DevScratch s(st);
+  u64 *dS = s.take<u64>(NS), *ncnt = s.take<u64>(NS + 1), *nptr = s.take<u64>(NS + 1);
+  u32 *dsu = s.take<u32>(n), *dsd = s.take<u32>(n), *dulo = s.take<u32>(NS), *duhi = s.take<u32>(NS), *ddlo = s.take<u32>(NS), *ddhi = s.take<u32>(NS), *dperm = s.take<u32>(n);
+  // ---- strings one excitation away
+  const long long tiles_s = (NS + SCAN_TILE - 1) / SCAN_TILE + 1;
+  u64 *dts_s = s.take<u64>(tiles_s + 1);
+  if (!s.ok()) return hip_fail(who, s.err());
   HIPCHK(hipMemcpy(dS, S.data(), NS * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dsu, sid_up.data(), n * 4, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(dsd, sid_dn.data(), n * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dulo, ulo.data(), NS * 4, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(duhi, uhi.data(), NS * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(ddlo, dlo.data(), NS * 4, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(ddhi, dhi.data(), NS * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dperm, perm_d.data(), n * 4, hipMemcpyHostToDevice));
-  // ---- strings one excitation away
-  const long long tiles_s = (NS + SCAN_TILE - 1) / SCAN_TILE + 1;
-  u64 *dts_s; HIPCHK(hipMalloc(&dts_s, (tiles_s + 1) * 8)); HIPCHK(hipMemsetAsync(dts_s, 0, (tiles_s + 1) * 8, st));
-  ScanWork sws; sws.state = dts_s; sws.ticket = (u32 *)(dts_s + tiles_s); sws.cap_tiles = tiles_s; sws.self_clear = true;
+  HIPCHK(hipMemsetAsync(dts_s, 0, (tiles_s + 1) * 8, st));
+  ScanWork sws = scan_work(dts_s, tiles_s);
   hipLaunchKernelGGL(k_str_nbr, dim3(nblk(NS)), dim3(TPB), 0, st, (const u64 *)dS, NS, 0, ncnt, (const u64 *)nptr, (u32 *)nullptr);
   device_excl_scan_u64(ncnt, nptr, NS, nptr + NS, sws, st);
   u64 nn = 0; HIPCHK(hipMemcpyAsync(&nn, nptr + NS, 8, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st));
-  HIPCHK(hipMalloc(&dnbr, (nn + 1) * 4));
+  u32 *dnbr = s.take<u32>(nn + 1);
+  // ---- candidates: count, offsets, words
+  u64 *ccnt = s.take<u64>(n), *coff = s.take<u64>(n);
+  if (!s.ok()) return hip_fail(who, s.err());
   hipLaunchKernelGGL(k_str_nbr, dim3(nblk(NS)), dim3(TPB), 0, st, (const u64 *)dS, NS, 1, ncnt, (const u64 *)nptr, dnbr);
   HamIdx x; x.S = dS; x.NS = NS; x.sid_up = dsu; x.sid_dn = dsd; x.ulo = dulo; x.uhi = duhi; x.dlo = ddlo; x.dhi = ddhi; x.perm_d = dperm; x.nptr = nptr; x.nbr = dnbr;
-  // ---- candidates: count, offsets, words
-  u64 *ccnt, *coff; HIPCHK(hipMalloc(&ccnt, n * 8)); HIPCHK(hipMalloc(&coff, n * 8));
   hipLaunchKernelGGL(k_ham_candidates, dim3(nblk(n)), dim3(TPB), 0, st, x, du, dd, (long long)n, c->htab.time_sym, 0, ccnt, (const u64 *)coff, (u64 *)nullptr);
   device_excl_scan_u64(ccnt, coff, n, dtot, sw, st);
   u64 m = 0; HIPCHK(hipMemcpyAsync(&m, dtot, 8, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st));
-  u64 *words = nullptr, *walt = nullptr, *keep = nullptr, *P = nullptr; double *hv = nullptr; u32 *hist = nullptr, *rowtot = nullptr; u64 *dts_m = nullptr;
+  u64 *keep = nullptr, *P = nullptr; double *hv = nullptr;
   u64 ptotal = 0;
   u64 *sorted = nullptr;
   if (m > 0) {
-    HIPCHK(hipMalloc(&words, m * 8)); HIPCHK(hipMalloc(&walt, m * 8)); HIPCHK(hipMalloc(&keep, m * 8)); HIPCHK(hipMalloc(&P, m * 8)); HIPCHK(hipMalloc(&hv, m * 8));
+    u64 *words = s.take<u64>(m), *walt = s.take<u64>(m); keep = s.take<u64>(m); P = s.take<u64>(m); hv = s.take<double>(m);
     const long long nt = (long long)((m + RS_TILE - 1) / RS_TILE);
-    HIPCHK(hipMalloc(&hist, (size_t)RS_MAX_RADIX * (nt + 1) * 4)); HIPCHK(hipMalloc(&rowtot, RS_MAX_RADIX * 4));
+    u32 *hist = s.take<u32>((size_t)RS_MAX_RADIX * (nt + 1)), *rowtot = s.take<u32>(RS_MAX_RADIX);
+    const long long tiles_m = (long long)((m + SCAN_TILE - 1) / SCAN_TILE + 1);
+    u64 *dts_m = s.take<u64>(tiles_m + 1);
+    if (!s.ok()) return hip_fail(who, s.err());
     hipLaunchKernelGGL(k_ham_candidates, dim3(nblk(n)), dim3(TPB), 0, st, x, du, dd, (long long)n, c->htab.time_sym, 1, ccnt, (const u64 *)coff, words);
     int kb = 1; while ((1ll << kb) < n) kb++;                       // row and column: 32 + kb bits, rows are contiguous already but the digits of a column pass scramble them
     SortWork so; so.k_alt = walt; so.v_alt = nullptr; so.hist = hist; so.rowtot = rowtot; so.cap = (long long)m;
@@ -107,21 +109,32 @@ static int ham_rows_dev(sqmc_gpu_ctx *c, int64_t n, const uint64_t *up, const ui
     device_radix_sort(sorted, nov, (long long)m, kb, so, st, 0);
     device_radix_sort(sorted, nov, (long long)m, kb, so, st, 32);
     hipLaunchKernelGGL(k_ham_eval, dim3(nblk((long long)m)), dim3(TPB), 0, st, c->dev, du, dd, (const u64 *)sorted, (long long)m, hv, keep);
-    const long long tiles_m = (long long)((m + SCAN_TILE - 1) / SCAN_TILE + 1);
-    HIPCHK(hipMalloc(&dts_m, (tiles_m + 1) * 8)); HIPCHK(hipMemsetAsync(dts_m, 0, (tiles_m + 1) * 8, st));
-    ScanWork swm; swm.state = dts_m; swm.ticket = (u32 *)(dts_m + tiles_m); swm.cap_tiles = tiles_m; swm.self_clear = true;
+    HIPCHK(hipMemsetAsync(dts_m, 0, (tiles_m + 1) * 8, st));
+    ScanWork swm = scan_work(dts_m, tiles_m);
     device_excl_scan_u64(keep, P, (long long)m, dtot, swm, st);
     HIPCHK(hipMemcpyAsync(&ptotal, dtot, 8, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st));
   }
   const u64 total = (u64)n + ptotal;
-  long long *didx; double *dval;
-  HIPCHK(hipMalloc(&didx, (total + 1) * 8)); HIPCHK(hipMalloc(&dval, (total + 1) * 8));
+  long long *didx = out.take<long long>(total + 1); double *dval = out.take<double>(total + 1);
+  if (!out.ok()) return hip_fail(who, out.err());
   hipLaunchKernelGGL(k_ham_rows, dim3(nblk(n)), dim3(TPB), 0, st, c->dev, du, dd, (long long)n, (const u64 *)coff, (const u64 *)P, (long long)m, ptotal, dcnt, doff, didx, dval);
   if (m > 0) hipLaunchKernelGGL(k_ham_place, dim3(nblk((long long)m)), dim3(TPB), 0, st, (const u64 *)sorted, (const double *)hv, (const u64 *)keep, (const u64 *)P, (long long)m, didx, dval);
   HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(st));
-  void *fr[] = {dS, ncnt, nptr, dsu, dsd, dulo, duhi, ddlo, ddhi, dperm, dnbr, dts_s, ccnt, coff, words, walt, keep, P, hv, hist, rowtot, dts_m};
-  for (void *q : fr) if (q) hipFree(q);
   *total_out = total; *didx_out = didx; *dval_out = dval;
+  return SQMC_OK;
+}
+
+// the sorted determinant list, its row counts / offsets and the scan state that both sparse-Hamiltonian doors hand to ham_rows_dev
+struct HamListDev { u64 *du, *dd, *dcnt, *doff, *dtot; ScanWork sw; };
+static int ham_list_dev(sqmc_gpu_ctx *c, const char *who, int64_t n, const uint64_t *up, const uint64_t *dn, int n_tot, DevScratch &s, HamListDev &L) {
+  for (long long i = 1; i < n; i++)
+    if (!(up[i - 1] < up[i] || (up[i - 1] == up[i] && dn[i - 1] < dn[i]))) return fail(SQMC_ERR_BAD_ARG, "determinant list must be strictly sorted by (up,dn)");
+  const long long tiles = (n + SCAN_TILE - 1) / SCAN_TILE + 1;
+  L.du = s.take<u64>(n); L.dd = s.take<u64>(n); L.dcnt = s.take<u64>(n); L.doff = s.take<u64>(n); L.dtot = s.take<u64>(n_tot);
+  u64 *dts = s.take<u64>(tiles + 1);
+  if (!s.ok()) return hip_fail(who, s.err());
+  HIPCHK(hipMemcpy(L.du, up, n * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(L.dd, dn, n * 8, hipMemcpyHostToDevice));
+  L.sw = scan_work(dts, tiles);
   return SQMC_OK;
 }
 
@@ -130,27 +143,33 @@ int sqmc_gpu_build_sparse_ham(sqmc_gpu_ctx *c, int64_t n, const uint64_t *up, co
   if (!c || !out_nnz || !out_row_counts || !out_indices || !out_values || n <= 0) return fail(SQMC_ERR_BAD_ARG, "bad argument");
   if (c->htab.sys_type == 3 && c->htab.hk_sym)
     return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_build_sparse_ham is not built for hubbardk with space_sym: the matrix among representatives is assembled from sqmc_gpu_hci_connections in raw mode");
-  for (long long i = 1; i < n; i++)
-    if (!(up[i - 1] < up[i] || (up[i - 1] == up[i] && dn[i - 1] < dn[i]))) return fail(SQMC_ERR_BAD_ARG, "determinant list must be strictly sorted by (up,dn)");
   hipStream_t st = c->st;
-  u64 *du, *dd, *dcnt, *doff, *dtot, *dts;
-  HIPCHK(hipMalloc(&du, n * 8)); HIPCHK(hipMalloc(&dd, n * 8)); HIPCHK(hipMalloc(&dcnt, n * 8)); HIPCHK(hipMalloc(&doff, n * 8)); HIPCHK(hipMalloc(&dtot, 8));
-  long long tiles = (n + SCAN_TILE - 1) / SCAN_TILE + 1;
-  HIPCHK(hipMalloc(&dts, (tiles + 1) * 8));
-  HIPCHK(hipMemcpy(du, up, n * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dd, dn, n * 8, hipMemcpyHostToDevice));
-  ScanWork sw; sw.state = dts; sw.ticket = (u32 *)(dts + tiles); sw.cap_tiles = tiles; sw.self_clear = true;
+  DevScratch s(st); HamListDev L;
+  int rh = ham_list_dev(c, "sqmc_gpu_build_sparse_ham", n, up, dn, 1, s, L);
+  if (rh) return rh;
   u64 total = 0; long long *didx; double *dval;
-  { int rh = ham_rows_dev(c, n, up, dn, du, dd, dcnt, doff, dtot, sw, &total, &didx, &dval); if (rh) return rh; }
+  if ((rh = ham_rows_dev(c, n, up, dn, L.du, L.dd, L.dcnt, L.doff, L.dtot, L.sw, s, &total, &didx, &dval))) return rh;
   HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(st));
-  int64_t *rc = (int64_t *)malloc(n * 8), *ix = (int64_t *)malloc((total + 1) * 8); double *vl = (double *)malloc((total + 1) * 8);
-  HIPCHK(hipMemcpy(rc, dcnt, n * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(ix, didx, total * 8, hipMemcpyDeviceToHost));
+  HostOut h;
+  int64_t *rc = h.take<int64_t>(n), *ix = h.take<int64_t>(total + 1); double *vl = h.take<double>(total + 1);
+  HIPCHK(hipMemcpy(rc, L.dcnt, n * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(ix, didx, total * 8, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(vl, dval, total * 8, hipMemcpyDeviceToHost));
-  *out_nnz = (int64_t)total; *out_row_counts = rc; *out_indices = ix; *out_values = vl;
-  void *fr[] = {du, dd, dcnt, doff, dtot, dts, didx, dval};
-  for (void *q : fr) hipFree(q);
+  *out_nnz = (int64_t)total; h.commit(rc, out_row_counts); h.commit(ix, out_indices); h.commit(vl, out_values);
   return SQMC_OK;
 }
 
+// the matvec plan with its device buffers: those live in `mem` until sqmc_gpu_spmv_free
+struct SpmvPlanOwned : sqmc_spmv_plan { DevScratch mem; };
+static int spmv_plan_new(int64_t n, long long nnz_full, SpmvPlanOwned **out) {
+  SpmvPlanOwned *p = new SpmvPlanOwned(); p->n = n; p->nnz_full = nnz_full;
+  if (hipError_t e = hipStreamCreate(&p->st)) { delete p; return hip_fail("spmv plan", e); }
+  p->mem.stream = p->st;
+  p->d_ptr = p->mem.take<int>(n + 1); p->d_col = p->mem.take<int>(nnz_full + 1); p->d_val = p->mem.take<double>(nnz_full + 1);
+  p->d_x = p->mem.take<double>(n); p->d_y = p->mem.take<double>(n);
+  if (!p->mem.ok()) { const hipError_t e = p->mem.err(); sqmc_gpu_spmv_free(p); return hip_fail("spmv plan", e); }
+  *out = p;
+  return SQMC_OK;
+}
 
 // The sparse Hamiltonian of a sorted determinant list built on the device AND left there as a
 // matvec plan: what generate_sparse_ham_chem_upper_triangular + davidson_sparse's matvec need,
@@ -159,70 +178,74 @@ int sqmc_gpu_build_sparse_ham(sqmc_gpu_ctx *c, int64_t n, const uint64_t *up, co
 int sqmc_gpu_build_spmv_plan(sqmc_gpu_ctx *c, int64_t n, const uint64_t *up, const uint64_t *dn, sqmc_spmv_plan **plan, double *diag, int64_t *out_nnz) {
   if (!c || !plan || !diag || !out_nnz || n <= 0) return fail(SQMC_ERR_BAD_ARG, "bad argument");
   if (c->htab.sys_type == 3 && c->htab.hk_sym) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_build_spmv_plan is not built for hubbardk with space_sym (see sqmc_gpu_build_sparse_ham)");
-  for (long long i = 1; i < n; i++)
-    if (!(up[i - 1] < up[i] || (up[i - 1] == up[i] && dn[i - 1] < dn[i]))) return fail(SQMC_ERR_BAD_ARG, "determinant list must be strictly sorted by (up,dn)");
+  const char *who = "sqmc_gpu_build_spmv_plan";
   hipStream_t st = c->st;
-  u64 *du, *dd, *dcnt, *doff, *dtot, *dts;
-  HIPCHK(hipMalloc(&du, n * 8)); HIPCHK(hipMalloc(&dd, n * 8)); HIPCHK(hipMalloc(&dcnt, n * 8)); HIPCHK(hipMalloc(&doff, n * 8)); HIPCHK(hipMalloc(&dtot, 16));
-  long long tiles = (n + SCAN_TILE - 1) / SCAN_TILE + 1;
-  HIPCHK(hipMalloc(&dts, (tiles + 1) * 8));
-  HIPCHK(hipMemcpy(du, up, n * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dd, dn, n * 8, hipMemcpyHostToDevice));
-  ScanWork sw; sw.state = dts; sw.ticket = (u32 *)(dts + tiles); sw.cap_tiles = tiles; sw.self_clear = true;
+  std::unique_ptr<sqmc_spmv_plan, int (*)(sqmc_spmv_plan *)> guard(nullptr, sqmc_gpu_spmv_free);      // freed behind s, whose destructor waits for the kernels that write the plan
+  DevScratch s(st); HamListDev L;
+  int rh = ham_list_dev(c, who, n, up, dn, 2, s, L);
+  if (rh) return rh;
+  u64 *dcnt = L.dcnt, *doff = L.doff, *dtot = L.dtot;
   u64 total = 0; long long *didx; double *dval;
-  { int rh = ham_rows_dev(c, n, up, dn, du, dd, dcnt, doff, dtot, sw, &total, &didx, &dval); if (rh) return rh; }
+  if ((rh = ham_rows_dev(c, n, up, dn, L.du, L.dd, dcnt, doff, dtot, L.sw, s, &total, &didx, &dval))) return rh;
   const long long n_strict = (long long)total - n, nnz_full = (long long)total + n_strict;
-  if (nnz_full >= (1ll << 31)) { hipFree(didx); hipFree(dval); return fail(SQMC_ERR_UNSUPPORTED, "more than 2^31 expanded nonzeros"); }
+  if (nnz_full >= (1ll << 31)) return fail(SQMC_ERR_UNSUPPORTED, "more than 2^31 expanded nonzeros");
   // transpose bookkeeping
-  u64 *dkeys, *dkeys_alt, *drowlen, *dptr64, *dcolc, *dcolstart; u32 *dvals, *dvals_alt, *drowof, *dcolcount, *dhist, *drowtot;
   const long long ntile_sort = (long long)((total + RS_TILE - 1) / RS_TILE);
-  HIPCHK(hipMalloc(&dkeys, total * 8)); HIPCHK(hipMalloc(&dkeys_alt, total * 8)); HIPCHK(hipMalloc(&dvals, total * 4)); HIPCHK(hipMalloc(&dvals_alt, total * 4));
-  HIPCHK(hipMalloc(&drowof, total * 4)); HIPCHK(hipMalloc(&dcolcount, (n + 1) * 4)); HIPCHK(hipMalloc(&drowlen, n * 8)); HIPCHK(hipMalloc(&dptr64, n * 8));
-  HIPCHK(hipMalloc(&dcolc, n * 8)); HIPCHK(hipMalloc(&dcolstart, n * 8));
-  HIPCHK(hipMalloc(&dhist, (size_t)RS_MAX_RADIX * (ntile_sort + 1) * 4)); HIPCHK(hipMalloc(&drowtot, RS_MAX_RADIX * 4));
+  u64 *dkeys = s.take<u64>(total), *dkeys_alt = s.take<u64>(total); u32 *dvals = s.take<u32>(total), *dvals_alt = s.take<u32>(total);
+  u32 *drowof = s.take<u32>(total), *dcolcount = s.take<u32>(n + 1); u64 *drowlen = s.take<u64>(n), *dptr64 = s.take<u64>(n);
+  u64 *dcolc = s.take<u64>(n), *dcolstart = s.take<u64>(n);
+  u32 *dhist = s.take<u32>((size_t)RS_MAX_RADIX * (ntile_sort + 1)), *drowtot = s.take<u32>(RS_MAX_RADIX);
+  if (!s.ok()) return hip_fail(who, s.err());
   HIPCHK(hipMemsetAsync(dcolcount, 0, (n + 1) * 4, st));
   hipLaunchKernelGGL(k_csr_keys, dim3(nblk(n)), dim3(TPB), 0, st, dcnt, doff, didx, dkeys, dvals, drowof, dcolcount, (long long)n);
   hipLaunchKernelGGL(k_csr_rowlen, dim3(nblk(n)), dim3(TPB), 0, st, dcnt, dcolcount, drowlen, dcolc, (long long)n);
-  device_excl_scan_u64(drowlen, dptr64, n, dtot, sw, st);
-  device_excl_scan_u64(dcolc, dcolstart, n, dtot + 1, sw, st);
+  device_excl_scan_u64(drowlen, dptr64, n, dtot, L.sw, st);
+  device_excl_scan_u64(dcolc, dcolstart, n, dtot + 1, L.sw, st);
   int kb = 1; while ((1ll << kb) <= n) kb++;                      // keys are column indices 0..n (n = the diagonal marker)
   SortWork so; so.k_alt = dkeys_alt; so.v_alt = dvals_alt; so.hist = dhist; so.rowtot = drowtot; so.cap = (long long)total;
   u64 *sk = dkeys; u32 *sv = dvals;
   device_radix_sort(sk, sv, (long long)total, kb, so, st);
-  sqmc_spmv_plan *p = new sqmc_spmv_plan(); p->n = n; p->nnz_full = nnz_full;
-  HIPCHK(hipStreamCreate(&p->st));
-  HIPCHK(hipMalloc(&p->d_ptr, (n + 1) * 4)); HIPCHK(hipMalloc(&p->d_col, (nnz_full + 1) * 4)); HIPCHK(hipMalloc(&p->d_val, (nnz_full + 1) * 8));
-  HIPCHK(hipMalloc(&p->d_x, n * 8)); HIPCHK(hipMalloc(&p->d_y, n * 8));
-  double *ddiag; HIPCHK(hipMalloc(&ddiag, n * 8));
+  SpmvPlanOwned *p = nullptr;
+  if ((rh = spmv_plan_new(n, nnz_full, &p))) return rh;
+  guard.reset(p);
+  double *ddiag = s.take<double>(n);
+  if (!s.ok()) return hip_fail(who, s.err());
   hipLaunchKernelGGL(k_csr_fill_stored, dim3(nblk(n + 1)), dim3(TPB), 0, st, dcnt, doff, didx, dval, dptr64, p->d_ptr, p->d_col, p->d_val, ddiag, (long long)n, nnz_full);
   if (n_strict > 0)
     hipLaunchKernelGGL(k_csr_fill_transposed, dim3(nblk(n_strict)), dim3(TPB), 0, st, sk, sv, drowof, dval, dcnt, dptr64, dcolstart, p->d_col, p->d_val, (long long)n, n_strict);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(diag, ddiag, n * 8, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st));
-  *out_nnz = (int64_t)total; *plan = p;
-  void *fr[] = {du, dd, dcnt, doff, dtot, dts, didx, dval, dkeys, dkeys_alt, dvals, dvals_alt, drowof, dcolcount, drowlen, dptr64, dcolc, dcolstart, dhist, drowtot, ddiag};
-  for (void *q : fr) hipFree(q);
+  *out_nnz = (int64_t)total; *plan = guard.release();
   return SQMC_OK;
 }
 
-int sqmc_gpu_propose_batch(sqmc_gpu_ctx *c, int64_t n, double tau, const uint64_t *up, const uint64_t *dn, const int32_t *seeds,
-                           uint64_t *ju, uint64_t *jd, double *wj, int32_t *seeds_after) {
-  if (!c) return fail(SQMC_ERR_BAD_ARG, "null ctx");
+// the three proposal doors: `width` children per walker (the heat-bath kernel proposes two)
+extern "C++" {
+template <class K>
+static int propose_batch(K kern, const char *who, int width, sqmc_gpu_ctx *c, int64_t n, double tau, const uint64_t *up, const uint64_t *dn, const int32_t *seeds,
+                         uint64_t *ju, uint64_t *jd, double *wj, int32_t *seeds_after) {
   if (n <= 0) return SQMC_OK;
   std::vector<u64> s(n);
   for (long long i = 0; i < n; i++) s[i] = (((u64)seeds[4 * i] << 36) + ((u64)seeds[4 * i + 1] << 24) + ((u64)seeds[4 * i + 2] << 12) + (u64)seeds[4 * i + 3]) & SQ_MASK48;
-  u64 *du, *dd, *ds, *dju, *djd, *dso; double *dw;
-  HIPCHK(hipMalloc(&du, n * 8)); HIPCHK(hipMalloc(&dd, n * 8)); HIPCHK(hipMalloc(&ds, n * 8)); HIPCHK(hipMalloc(&dju, n * 8));
-  HIPCHK(hipMalloc(&djd, n * 8)); HIPCHK(hipMalloc(&dso, n * 8)); HIPCHK(hipMalloc(&dw, n * 8));
+  const long long nw = width * n;
+  DevScratch m(c->st);
+  u64 *du = m.take<u64>(n), *dd = m.take<u64>(n), *ds = m.take<u64>(n), *dju = m.take<u64>(nw), *djd = m.take<u64>(nw), *dso = m.take<u64>(n); double *dw = m.take<double>(nw);
+  if (!m.ok()) return hip_fail(who, m.err());
   HIPCHK(hipMemcpy(du, up, n * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dd, dn, n * 8, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(ds, s.data(), n * 8, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_propose_batch, dim3(nblk(n)), dim3(TPB), 0, c->st, c->dev, du, dd, ds, dju, djd, dw, dso, (long long)n, tau);
+  hipLaunchKernelGGL(kern, dim3(nblk(n)), dim3(TPB), 0, c->st, c->dev, du, dd, ds, dju, djd, dw, dso, (long long)n, tau);
   HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(c->st));
-  HIPCHK(hipMemcpy(ju, dju, n * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(jd, djd, n * 8, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(wj, dw, n * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(s.data(), dso, n * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(ju, dju, nw * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(jd, djd, nw * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(wj, dw, nw * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(s.data(), dso, n * 8, hipMemcpyDeviceToHost));
   for (long long i = 0; i < n; i++) { u64 x = s[i]; seeds_after[4 * i] = (int)((x >> 36) & 4095); seeds_after[4 * i + 1] = (int)((x >> 24) & 4095);
     seeds_after[4 * i + 2] = (int)((x >> 12) & 4095); seeds_after[4 * i + 3] = (int)(x & 4095); }
-  hipFree(du); hipFree(dd); hipFree(ds); hipFree(dju); hipFree(djd); hipFree(dso); hipFree(dw);
   return SQMC_OK;
+}
+}
+int sqmc_gpu_propose_batch(sqmc_gpu_ctx *c, int64_t n, double tau, const uint64_t *up, const uint64_t *dn, const int32_t *seeds,
+                           uint64_t *ju, uint64_t *jd, double *wj, int32_t *seeds_after) {
+  if (!c) return fail(SQMC_ERR_BAD_ARG, "null ctx");
+  return propose_batch(k_propose_batch, "sqmc_gpu_propose_batch", 1, c, n, tau, up, dn, seeds, ju, jd, wj, seeds_after);
 }
 
 int sqmc_gpu_set_heatbath_tables(sqmc_gpu_ctx *c, const sqmc_heatbath_tables *t) {
@@ -267,22 +290,7 @@ int sqmc_gpu_propose_heatbath_batch(sqmc_gpu_ctx *c, int64_t n, double tau, cons
                                     uint64_t *ju, uint64_t *jd, double *wj, int32_t *seeds_after) {
   if (!c) return fail(SQMC_ERR_BAD_ARG, "null ctx");
   if (!c->dev.hb.on) return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_set_heatbath_tables not called");
-  if (n <= 0) return SQMC_OK;
-  std::vector<u64> s(n);
-  for (long long i = 0; i < n; i++) s[i] = (((u64)seeds[4 * i] << 36) + ((u64)seeds[4 * i + 1] << 24) + ((u64)seeds[4 * i + 2] << 12) + (u64)seeds[4 * i + 3]) & SQ_MASK48;
-  u64 *du, *dd, *ds, *dju, *djd, *dso; double *dw;
-  HIPCHK(hipMalloc(&du, n * 8)); HIPCHK(hipMalloc(&dd, n * 8)); HIPCHK(hipMalloc(&ds, n * 8)); HIPCHK(hipMalloc(&dju, 2 * n * 8));
-  HIPCHK(hipMalloc(&djd, 2 * n * 8)); HIPCHK(hipMalloc(&dso, n * 8)); HIPCHK(hipMalloc(&dw, 2 * n * 8));
-  HIPCHK(hipMemcpy(du, up, n * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dd, dn, n * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(ds, s.data(), n * 8, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_propose_heatbath_batch, dim3(nblk(n)), dim3(TPB), 0, c->st, c->dev, du, dd, ds, dju, djd, dw, dso, (long long)n, tau);
-  HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(c->st));
-  HIPCHK(hipMemcpy(ju, dju, 2 * n * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(jd, djd, 2 * n * 8, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(wj, dw, 2 * n * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(s.data(), dso, n * 8, hipMemcpyDeviceToHost));
-  for (long long i = 0; i < n; i++) { u64 x = s[i]; seeds_after[4 * i] = (int)((x >> 36) & 4095); seeds_after[4 * i + 1] = (int)((x >> 24) & 4095);
-    seeds_after[4 * i + 2] = (int)((x >> 12) & 4095); seeds_after[4 * i + 3] = (int)(x & 4095); }
-  hipFree(du); hipFree(dd); hipFree(ds); hipFree(dju); hipFree(djd); hipFree(dso); hipFree(dw);
-  return SQMC_OK;
+  return propose_batch(k_propose_heatbath_batch, "sqmc_gpu_propose_heatbath_batch", 2, c, n, tau, up, dn, seeds, ju, jd, wj, seeds_after);
 }
 
 // setup_orb_by_symm, chemistry.f90:2505-2523, with proposal_method = 'CauchySchwarz'
@@ -340,22 +348,7 @@ int sqmc_gpu_propose_cauchy_schwarz_batch(sqmc_gpu_ctx *c, int64_t n, double tau
                                           uint64_t *ju, uint64_t *jd, double *wj, int32_t *seeds_after) {
   if (!c) return fail(SQMC_ERR_BAD_ARG, "null ctx");
   if (!c->dev.cs.on) return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_setup_cauchy_schwarz not called");
-  if (n <= 0) return SQMC_OK;
-  std::vector<u64> s(n);
-  for (long long i = 0; i < n; i++) s[i] = (((u64)seeds[4 * i] << 36) + ((u64)seeds[4 * i + 1] << 24) + ((u64)seeds[4 * i + 2] << 12) + (u64)seeds[4 * i + 3]) & SQ_MASK48;
-  u64 *du, *dd, *ds, *dju, *djd, *dso; double *dw;
-  HIPCHK(hipMalloc(&du, n * 8)); HIPCHK(hipMalloc(&dd, n * 8)); HIPCHK(hipMalloc(&ds, n * 8)); HIPCHK(hipMalloc(&dju, n * 8));
-  HIPCHK(hipMalloc(&djd, n * 8)); HIPCHK(hipMalloc(&dso, n * 8)); HIPCHK(hipMalloc(&dw, n * 8));
-  HIPCHK(hipMemcpy(du, up, n * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dd, dn, n * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(ds, s.data(), n * 8, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_propose_cauchy_batch, dim3(nblk(n)), dim3(TPB), 0, c->st, c->dev, du, dd, ds, dju, djd, dw, dso, (long long)n, tau);
-  HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(c->st));
-  HIPCHK(hipMemcpy(ju, dju, n * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(jd, djd, n * 8, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(wj, dw, n * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(s.data(), dso, n * 8, hipMemcpyDeviceToHost));
-  for (long long i = 0; i < n; i++) { u64 x = s[i]; seeds_after[4 * i] = (int)((x >> 36) & 4095); seeds_after[4 * i + 1] = (int)((x >> 24) & 4095);
-    seeds_after[4 * i + 2] = (int)((x >> 12) & 4095); seeds_after[4 * i + 3] = (int)(x & 4095); }
-  hipFree(du); hipFree(dd); hipFree(ds); hipFree(dju); hipFree(djd); hipFree(dso); hipFree(dw);
-  return SQMC_OK;
+  return propose_batch(k_propose_cauchy_batch, "sqmc_gpu_propose_cauchy_schwarz_batch", 1, c, n, tau, up, dn, seeds, ju, jd, wj, seeds_after);
 }
 
 int sqmc_gpu_hci_connections(sqmc_gpu_ctx *c, int64_t n_ref, const uint64_t *ref_up, const uint64_t *ref_dn, const double *coeffs, double eps,
@@ -367,16 +360,35 @@ int sqmc_gpu_hci_connections(sqmc_gpu_ctx *c, int64_t n_ref, const uint64_t *ref
 // reference determinants (dru, drd), and nothing is copied to the host
 // rec: the generator carries the get_new_diag_elem record of every connection and the dedup keeps the first of each run (orold, orpk
 // of keep_dev; with host output: *out_old, *out_pqrs as four int32 per connection, zeros where there is no record)
-struct HciDevOut { u64 *ou, *od; double *onum, *oden; long long U; u64 *dru, *drd; double *orold; unsigned *orpk; };
+struct HciDevOut {
+  DevScratch mem; u64 *ou = nullptr, *od = nullptr; double *onum = nullptr, *oden = nullptr; long long U = 0; u64 *dru = nullptr, *drd = nullptr; double *orold = nullptr; unsigned *orpk = nullptr;
+  explicit HciDevOut(hipStream_t st) : mem(st) {}
+};
 static void hci_unpack_records(const unsigned *pk, long long n, int32_t *pqrs) {
   for (long long k = 0; k < n; k++) { pqrs[4 * k] = pk[k] & 255u; pqrs[4 * k + 1] = (pk[k] >> 8) & 255u; pqrs[4 * k + 2] = (pk[k] >> 16) & 255u; pqrs[4 * k + 3] = pk[k] >> 24; }
+}
+// Sorted ranks of n determinants on the device: k_main_keys, then the radix sort on the context's key bits.  *skey: the ranks ascending;
+// *perm: the position of each in the input order.  The two key buffers (*skey is one of them) and rowtot belong to `keys`, the rest
+// of the sort's scratch to `work` (the same owner, or one the caller clears sooner).  hist holds RS_MAX_RADIX counts per tile of the sort,
+// ceil(n / RS_TILE) tiles at most (scan_sort.h: hist[digit * ntiles + tile]); two of the callers used to allocate one tile more than that.
+static int det_ranks_sorted(sqmc_gpu_ctx *c, const char *who, long long n, const u64 *d_up, const u64 *d_dn, DevScratch &keys, DevScratch &work,
+                            u64 **skey, u32 **perm, u32 **rowtot = nullptr) {
+  u64 *vk = keys.take<u64>(n), *vkalt = keys.take<u64>(n); u32 *rt = keys.take<u32>(RS_MAX_RADIX);
+  u32 *vv = work.take<u32>(n), *vvalt = work.take<u32>(n), *hist = work.take<u32>((size_t)((n + RS_TILE - 1) / RS_TILE) * RS_MAX_RADIX);
+  if (!keys.ok() || !work.ok()) return hip_fail(who, keys.ok() ? work.err() : keys.err());
+  hipLaunchKernelGGL(k_main_keys, dim3(nblk(n)), dim3(TPB), 0, c->st, c->dev, d_up, d_dn, vk, vv, n, 0);
+  SortWork so; so.k_alt = vkalt; so.v_alt = vvalt; so.hist = hist; so.rowtot = rt; so.cap = n;
+  *skey = vk; *perm = vv;
+  device_radix_sort(*skey, *perm, n, c->key_bits, so, c->st);
+  if (rowtot) *rowtot = rt;
+  return SQMC_OK;
 }
 static int hci_connections_impl(sqmc_gpu_ctx *c, int64_t n_ref, const uint64_t *ref_up, const uint64_t *ref_dn, const double *coeffs, double eps,
                                 int diag_mode, int32_t slice, int32_t n_slices, int64_t *out_n, uint64_t **out_up, uint64_t **out_dn,
                                 double **out_num, double **out_den, HciDevOut *keep_dev, bool rec = false, double **out_old = nullptr, int32_t **out_pqrs = nullptr) {
   if (!c || !out_n) return fail(SQMC_ERR_BAD_ARG, "null argument");
   if (rec && (c->htab.time_sym || c->htab.sys_type >= 2)) return fail(SQMC_ERR_UNSUPPORTED, "the diagonal-update record is a determinant-basis formula for chem and heg contexts without time_sym");
-  if (keep_dev) { memset(keep_dev, 0, sizeof(*keep_dev)); if (diag_mode == 2) return fail(SQMC_ERR_BAD_ARG, "raw mode has no device-resident form"); }
+  if (keep_dev && diag_mode == 2) return fail(SQMC_ERR_BAD_ARG, "raw mode has no device-resident form");
   if (n_slices < 1 || slice < 0 || slice >= n_slices) return fail(SQMC_ERR_BAD_ARG, "slice out of range");
   u64 key_lo = 0, key_hi = ~0ull;
   if (n_slices > 1) {                 // equal parts of the key range [0, invalid_key]
@@ -387,109 +399,73 @@ static int hci_connections_impl(sqmc_gpu_ctx *c, int64_t n_ref, const uint64_t *
   if (c->htab.sys_type == 1 && c->htab.heg_nmax > 4) return fail(SQMC_ERR_UNSUPPORTED, "HEG connections: plane-wave index beyond +-4");
   *out_n = 0;
   if (n_ref <= 0) return SQMC_OK;
+  const char *who = "sqmc_gpu_hci_connections";
   hipStream_t st = c->st;
-  u64 *dru, *drd, *dcnt, *doff, *dtot, *dts; double *dco;
-  HIPCHK(hipMalloc(&dru, n_ref * 8)); HIPCHK(hipMalloc(&drd, n_ref * 8)); HIPCHK(hipMalloc(&dco, n_ref * 8));
-  HIPCHK(hipMalloc(&dcnt, n_ref * 8)); HIPCHK(hipMalloc(&doff, n_ref * 8)); HIPCHK(hipMalloc(&dtot, 8));
-  long long tiles = (n_ref + SCAN_TILE - 1) / SCAN_TILE + 1;
-  HIPCHK(hipMalloc(&dts, (tiles + 1) * 8));
+  DevScratch s(st);
+  const long long tiles = (n_ref + SCAN_TILE - 1) / SCAN_TILE + 1;
+  u64 *dru = s.take<u64>(n_ref), *drd = s.take<u64>(n_ref); double *dco = s.take<double>(n_ref);
+  u64 *dcnt = s.take<u64>(n_ref), *doff = s.take<u64>(n_ref), *dtot = s.take<u64>(1), *dts = s.take<u64>(tiles + 1);
+  if (!s.ok()) return hip_fail(who, s.err());
   HIPCHK(hipMemcpy(dru, ref_up, n_ref * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(drd, ref_dn, n_ref * 8, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(dco, coeffs, n_ref * 8, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_hci_gen<false>, dim3(nblk(n_ref)), dim3(TPB), 0, st, c->dev, dru, drd, dco, eps, diag_mode, (long long)n_ref, 0, dcnt, doff,
                      (u64 *)nullptr, (u64 *)nullptr, (double *)nullptr, (double *)nullptr, key_lo, key_hi, c->as, (double *)nullptr, (unsigned *)nullptr);
-  ScanWork sw; sw.state = dts; sw.ticket = (u32 *)(dts + tiles); sw.cap_tiles = tiles; sw.self_clear = true;
+  ScanWork sw = scan_work(dts, tiles);
   device_excl_scan_u64(dcnt, doff, n_ref, dtot, sw, st);
   u64 total = 0;
   HIPCHK(hipMemcpyAsync(&total, dtot, 8, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st));
-  if (total >= (1ull << 31) || total == 0) {          // both early returns release what the count pass allocated
-    void *fz[] = {dru, drd, dco, dcnt, doff, dtot, dts}; for (void *q : fz) hipFree(q);
-    if (total == 0) return SQMC_OK;
-    return fail(SQMC_ERR_UNSUPPORTED, "more than 2^31 connections in one call: use more slices (sqmc_gpu_hci_connections_slice)");
-  }
+  if (total == 0) return SQMC_OK;
+  if (total >= (1ull << 31)) return fail(SQMC_ERR_UNSUPPORTED, "more than 2^31 connections in one call: use more slices (sqmc_gpu_hci_connections_slice)");
   const long long T = (long long)total;
-  u64 *du, *dd, *keys, *kalt, *flags, *pos, *ou, *od, *dts2, *dtot2; u32 *vals, *valt, *hist, *rowtot; double *dnum, *dden, *onum, *oden;
-  HIPCHK(hipMalloc(&du, T * 8)); HIPCHK(hipMalloc(&dd, T * 8)); HIPCHK(hipMalloc(&dnum, T * 8)); HIPCHK(hipMalloc(&dden, T * 8));
-  double *drold = nullptr, *orold = nullptr; unsigned *drpk = nullptr, *orpk = nullptr;
-  if (rec) {
-    HIPCHK(hipMalloc(&drold, T * 8)); HIPCHK(hipMalloc(&drpk, T * 4));
-    hipLaunchKernelGGL(k_hci_gen<true>, dim3(nblk(n_ref)), dim3(TPB), 0, st, c->dev, dru, drd, dco, eps, diag_mode, (long long)n_ref, 1, dcnt, doff, du, dd, dnum, dden, key_lo, key_hi, c->as, drold, drpk);
-  } else
-    hipLaunchKernelGGL(k_hci_gen<false>, dim3(nblk(n_ref)), dim3(TPB), 0, st, c->dev, dru, drd, dco, eps, diag_mode, (long long)n_ref, 1, dcnt, doff, du, dd, dnum, dden, key_lo, key_hi, c->as, (double *)nullptr, (unsigned *)nullptr);
+  u64 *du = s.take<u64>(T), *dd = s.take<u64>(T); double *dnum = s.take<double>(T), *dden = s.take<double>(T);
+  double *drold = rec ? s.take<double>(T) : nullptr; unsigned *drpk = rec ? s.take<unsigned>(T) : nullptr;
+  if (!s.ok()) return hip_fail(who, s.err());
+  hipLaunchKernelGGL(rec ? k_hci_gen<true> : k_hci_gen<false>, dim3(nblk(n_ref)), dim3(TPB), 0, st, c->dev, dru, drd, dco, eps, diag_mode, (long long)n_ref, 1, dcnt, doff,
+                     du, dd, dnum, dden, key_lo, key_hi, c->as, drold, drpk);      // without records both are null
+  HostOut h;
+  // n connections from the device to fresh host arrays, with the records if the call carries them; the caller's pointers are written last
+  auto to_host = [&](long long n, const u64 *xu, const u64 *xd, const double *xnum, const double *xden, const double *xold, const unsigned *xpk) -> int {
+    uint64_t *hu = h.take<uint64_t>(n), *hd = h.take<uint64_t>(n); double *hn = h.take<double>(n), *hden = h.take<double>(n);
+    HIPCHK(hipMemcpy(hu, xu, n * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(hd, xd, n * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hn, xnum, n * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(hden, xden, n * 8, hipMemcpyDeviceToHost));
+    double *ho = nullptr; int32_t *hp = nullptr;
+    if (rec) {
+      ho = h.take<double>(n); hp = h.take<int32_t>(4 * n + 2); std::vector<unsigned> pk(n);
+      HIPCHK(hipMemcpy(ho, xold, n * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(pk.data(), xpk, n * 4, hipMemcpyDeviceToHost));
+      hci_unpack_records(pk.data(), n, hp);
+    }
+    *out_n = n;
+    h.commit(hu, out_up); h.commit(hd, out_dn); h.commit(hn, out_num); h.commit(hden, out_den); h.commit(ho, out_old); h.commit(hp, out_pqrs);
+    return SQMC_OK;
+  };
   if (diag_mode == 2) {               // the unmerged list, in generation order
     HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(st));
-    *out_n = T;
-    if (rec) {
-      double *ho = (double *)malloc(T * 8 + 8); int32_t *hp = (int32_t *)malloc(T * 16 + 16); std::vector<unsigned> pk(T);
-      HIPCHK(hipMemcpy(ho, drold, T * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(pk.data(), drpk, T * 4, hipMemcpyDeviceToHost));
-      hci_unpack_records(pk.data(), T, hp);
-      if (out_old) *out_old = ho; else free(ho);
-      if (out_pqrs) *out_pqrs = hp; else free(hp);
-      hipFree(drold); hipFree(drpk);
-    }
-    uint64_t *hu = (uint64_t *)malloc(T * 8 + 8), *hd = (uint64_t *)malloc(T * 8 + 8);
-    double *hn = (double *)malloc(T * 8 + 8), *hden = (double *)malloc(T * 8 + 8);
-    HIPCHK(hipMemcpy(hu, du, T * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(hd, dd, T * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(hn, dnum, T * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(hden, dden, T * 8, hipMemcpyDeviceToHost));
-    if (out_up) *out_up = hu; else free(hu);
-    if (out_dn) *out_dn = hd; else free(hd);
-    if (out_num) *out_num = hn; else free(hn);
-    if (out_den) *out_den = hden; else free(hden);
-    void *fr0[] = {dru, drd, dco, dcnt, doff, dtot, dts, du, dd, dnum, dden};
-    for (void *q : fr0) hipFree(q);
-    return SQMC_OK;
+    return to_host(T, du, dd, dnum, dden, drold, drpk);
   }
-  HIPCHK(hipMalloc(&keys, T * 8)); HIPCHK(hipMalloc(&kalt, T * 8)); HIPCHK(hipMalloc(&vals, T * 4)); HIPCHK(hipMalloc(&valt, T * 4));
-  long long ntiles = (T + RS_TILE - 1) / RS_TILE;
-  HIPCHK(hipMalloc(&hist, ntiles * RS_MAX_RADIX * 4)); HIPCHK(hipMalloc(&rowtot, RS_MAX_RADIX * 4));
-  hipLaunchKernelGGL(k_main_keys, dim3(nblk(T)), dim3(TPB), 0, st, c->dev, du, dd, keys, vals, T, 0);
-  SortWork so; so.k_alt = kalt; so.v_alt = valt; so.hist = hist; so.rowtot = rowtot; so.cap = T;
-  u64 *skey = keys; u32 *perm = vals;
-  device_radix_sort(skey, perm, T, c->key_bits, so, st);
-  HIPCHK(hipMalloc(&flags, T * 8)); HIPCHK(hipMalloc(&pos, T * 8));
-  long long tiles2 = (T + SCAN_TILE - 1) / SCAN_TILE + 1;
-  HIPCHK(hipMalloc(&dts2, (tiles2 + 1) * 8)); HIPCHK(hipMalloc(&dtot2, 8));
+  u64 *skey; u32 *perm;
+  { const int rs = det_ranks_sorted(c, who, T, du, dd, s, s, &skey, &perm); if (rs) return rs; }
+  const long long tiles2 = (T + SCAN_TILE - 1) / SCAN_TILE + 1;
+  u64 *flags = s.take<u64>(T), *pos = s.take<u64>(T), *dts2 = s.take<u64>(tiles2 + 1), *dtot2 = s.take<u64>(1);
+  if (!s.ok()) return hip_fail(who, s.err());
   hipLaunchKernelGGL(k_hci_heads, dim3(nblk(T)), dim3(TPB), 0, st, skey, flags, T);
-  ScanWork sw2; sw2.state = dts2; sw2.ticket = (u32 *)(dts2 + tiles2); sw2.cap_tiles = tiles2; sw2.self_clear = true;
+  ScanWork sw2 = scan_work(dts2, tiles2);
   device_excl_scan_u64(flags, pos, T, dtot2, sw2, st);
   u64 nuniq = 0;
   HIPCHK(hipMemcpyAsync(&nuniq, dtot2, 8, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st));
   const long long U = (long long)nuniq;
-  HIPCHK(hipMalloc(&ou, U * 8)); HIPCHK(hipMalloc(&od, U * 8)); HIPCHK(hipMalloc(&onum, U * 8)); HIPCHK(hipMalloc(&oden, U * 8));
-  if (rec) {
-    HIPCHK(hipMalloc(&orold, U * 8)); HIPCHK(hipMalloc(&orpk, U * 4));
-    hipLaunchKernelGGL(k_hci_dedup<true>, dim3(nblk(T)), dim3(TPB), 0, st, skey, perm, flags, pos, du, dd, dnum, dden, ou, od, onum, oden, T,
-                       (const double *)drold, (const unsigned *)drpk, orold, orpk);
-  } else
-    hipLaunchKernelGGL(k_hci_dedup<false>, dim3(nblk(T)), dim3(TPB), 0, st, skey, perm, flags, pos, du, dd, dnum, dden, ou, od, onum, oden, T,
-                       (const double *)nullptr, (const unsigned *)nullptr, (double *)nullptr, (unsigned *)nullptr);
+  DevScratch &o = keep_dev ? keep_dev->mem : s;      // the deduplicated arrays: the caller's when they stay on the device
+  u64 *ou = o.take<u64>(U), *od = o.take<u64>(U); double *onum = o.take<double>(U), *oden = o.take<double>(U);
+  double *orold = rec ? o.take<double>(U) : nullptr; unsigned *orpk = rec ? o.take<unsigned>(U) : nullptr;
+  if (!o.ok()) return hip_fail(who, o.err());
+  hipLaunchKernelGGL(rec ? k_hci_dedup<true> : k_hci_dedup<false>, dim3(nblk(T)), dim3(TPB), 0, st, skey, perm, flags, pos, du, dd, dnum, dden, ou, od, onum, oden, T,
+                     (const double *)drold, (const unsigned *)drpk, orold, orpk);
   HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(st));
+  s.drop(drold); s.drop(drpk);
+  if (!keep_dev) return to_host(U, ou, od, onum, oden, orold, orpk);
+  s.keep(dru, o); s.keep(drd, o);
+  keep_dev->ou = ou; keep_dev->od = od; keep_dev->onum = onum; keep_dev->oden = oden; keep_dev->U = U; keep_dev->dru = dru; keep_dev->drd = drd;
+  keep_dev->orold = orold; keep_dev->orpk = orpk;
   *out_n = U;
-  hipFree(drold); hipFree(drpk);
-  if (rec && !keep_dev) {
-    double *ho = (double *)malloc(U * 8 + 8); int32_t *hp = (int32_t *)malloc(U * 16 + 16); std::vector<unsigned> pk(U);
-    HIPCHK(hipMemcpy(ho, orold, U * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(pk.data(), orpk, U * 4, hipMemcpyDeviceToHost));
-    hci_unpack_records(pk.data(), U, hp);
-    if (out_old) *out_old = ho; else free(ho);
-    if (out_pqrs) *out_pqrs = hp; else free(hp);
-    hipFree(orold); hipFree(orpk);
-  }
-  if (keep_dev) {
-    keep_dev->orold = orold; keep_dev->orpk = orpk;
-    keep_dev->ou = ou; keep_dev->od = od; keep_dev->onum = onum; keep_dev->oden = oden; keep_dev->U = U; keep_dev->dru = dru; keep_dev->drd = drd;
-    void *frk[] = {dco, dcnt, doff, dtot, dts, du, dd, dnum, dden, keys, kalt, vals, valt, hist, rowtot, flags, pos, dts2, dtot2};
-    for (void *q : frk) hipFree(q);
-    return SQMC_OK;
-  }
-  uint64_t *hu = (uint64_t *)malloc(U * 8 + 8), *hd = (uint64_t *)malloc(U * 8 + 8);
-  double *hn = (double *)malloc(U * 8 + 8), *hden = (double *)malloc(U * 8 + 8);
-  HIPCHK(hipMemcpy(hu, ou, U * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(hd, od, U * 8, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(hn, onum, U * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(hden, oden, U * 8, hipMemcpyDeviceToHost));
-  if (out_up) *out_up = hu; else free(hu);
-  if (out_dn) *out_dn = hd; else free(hd);
-  if (out_num) *out_num = hn; else free(hn);
-  if (out_den) *out_den = hden; else free(hden);
-  void *fr[] = {dru, drd, dco, dcnt, doff, dtot, dts, du, dd, dnum, dden, keys, kalt, vals, valt, hist, rowtot, flags, pos, dts2, dtot2, ou, od, onum, oden};
-  for (void *q : fr) hipFree(q);
   return SQMC_OK;
 }
 
@@ -517,9 +493,10 @@ int sqmc_gpu_diag_update_batch(sqmc_gpu_ctx *c, int64_t n, const double *old_dia
   if (form != 0 && form != 1) return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_diag_update_batch: form must be 0 (one lane, reference order) or 1 (lane group)");
   if (n <= 0) return SQMC_OK;
   if (!old_diag || !pqrs || !new_up || !new_dn || !new_diag) return fail(SQMC_ERR_BAD_ARG, "null argument");
-  double *dold, *dout; int *dpq, *dbad; u64 *du, *dd;
-  HIPCHK(hipMalloc(&dold, n * 8)); HIPCHK(hipMalloc(&dout, n * 8)); HIPCHK(hipMalloc(&dpq, n * 16)); HIPCHK(hipMalloc(&du, n * 8)); HIPCHK(hipMalloc(&dd, n * 8));
-  HIPCHK(hipMalloc(&dbad, 4));
+  DevScratch s(c->st);
+  double *dold = s.take<double>(n), *dout = s.take<double>(n); int *dpq = s.take<int>(4 * n); u64 *du = s.take<u64>(n), *dd = s.take<u64>(n);
+  int *dbad = s.take<int>(1);
+  if (!s.ok()) return hip_fail("sqmc_gpu_diag_update_batch", s.err());
   HIPCHK(hipMemcpy(dold, old_diag, n * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dpq, pqrs, n * 16, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(du, new_up, n * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dd, new_dn, n * 8, hipMemcpyHostToDevice));
   HIPCHK(hipMemsetAsync(dbad, 0, 4, c->st));
@@ -529,8 +506,6 @@ int sqmc_gpu_diag_update_batch(sqmc_gpu_ctx *c, int64_t n, const double *old_dia
   int bad = 0;
   HIPCHK(hipMemcpyAsync(&bad, dbad, 4, hipMemcpyDeviceToHost, c->st)); HIPCHK(hipStreamSynchronize(c->st));      // the one status read
   if (!bad) HIPCHK(hipMemcpy(new_diag, dout, n * 8, hipMemcpyDeviceToHost));
-  void *fr[] = {dold, dout, dpq, dbad, du, dd};
-  for (void *q : fr) hipFree(q);
   if (bad) return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_diag_update_batch: a record does not describe a double excitation into its determinant (orbital out of 1..2 norb, "
                                          "p or q still occupied, r or s empty, spins of p/r or q/s differ, or wrong electron numbers); nothing was evaluated for it");
   return SQMC_OK;
@@ -555,28 +530,25 @@ int sqmc_gpu_debug_bucket_boundaries(sqmc_gpu_ctx *c, int64_t n0, const uint32_t
   const size_t nb = (size_t)B + 1;
   std::vector<u64> words(n0);
   for (int64_t i = 0; i < n0; i++) words[i] = ((u64)keys[i] << 32) | (u64)i;
-  u64 *d_keys = nullptr; u32 *d_w = nullptr;                 // eight arrays of B + 1 words: kb, hint, kb_prev, pos_prev, scount, pos, kb_out, hint_out
-  if (hipMalloc(&d_keys, (size_t)n0 * 8) != hipSuccess || hipMalloc(&d_w, 8 * nb * 4) != hipSuccess) { (void)hipGetLastError(); hipFree(d_keys); return fail(SQMC_ERR_HIP, "hipMalloc"); }
+  const char *who = "sqmc_gpu_debug_bucket_boundaries";
+  DevScratch s(c->st);
+  u64 *d_keys = s.take<u64>(n0); u32 *d_w = s.take<u32>(8 * nb);      // eight arrays of B + 1 words: kb, hint, kb_prev, pos_prev, scount, pos, kb_out, hint_out
+  if (!s.ok()) return fail(SQMC_ERR_HIP, "hipMalloc");
   const uint32_t *in[5] = {kb, hint, kb_prev, pos_prev, scount};
-  hipError_t e = hipMemcpy(d_keys, words.data(), (size_t)n0 * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(d_w, 0, 8 * nb * 4);
-  for (int q = 0; q < 5 && e == hipSuccess; q++) if (in[q]) e = hipMemcpy(d_w + q * nb, in[q], nb * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    BucketArgs ba; memset(&ba, 0, sizeof(ba));
-    ba.B = B; ba.scount = d_w + 4 * nb;
-    if (kb) { ba.kb = d_w; ba.pos = d_w + 5 * nb; if (hint) ba.hint = d_w + nb; }
-    if (kb_prev) ba.kb_prev = d_w + 2 * nb;
-    if (pos_prev) ba.pos_prev = d_w + 3 * nb;
-    if (kb_out) { ba.kb_out = d_w + 6 * nb; if (hint_out) ba.hint_out = d_w + 7 * nb; }
-    hipLaunchKernelGGL(k_bucket_boundaries, dim3(2), dim3(BK_T), 0, c->st, (const u64 *)d_keys, (long long)n0, ba);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(c->st);
-  }
-  if (e == hipSuccess && pos) e = hipMemcpy(pos, d_w + 5 * nb, nb * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && kb_out) e = hipMemcpy(kb_out, d_w + 6 * nb, (size_t)B * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && hint_out) e = hipMemcpy(hint_out, d_w + 7 * nb, (size_t)B * 4, hipMemcpyDeviceToHost);
-  hipFree(d_keys); hipFree(d_w);
-  if (e != hipSuccess) return fail(SQMC_ERR_HIP, std::string("sqmc_gpu_debug_bucket_boundaries: ") + hipGetErrorString(e));
+  HIPDOOR(who, hipMemcpy(d_keys, words.data(), (size_t)n0 * 8, hipMemcpyHostToDevice));
+  HIPDOOR(who, hipMemset(d_w, 0, 8 * nb * 4));
+  for (int q = 0; q < 5; q++) if (in[q]) HIPDOOR(who, hipMemcpy(d_w + q * nb, in[q], nb * 4, hipMemcpyHostToDevice));
+  BucketArgs ba; memset(&ba, 0, sizeof(ba));
+  ba.B = B; ba.scount = d_w + 4 * nb;
+  if (kb) { ba.kb = d_w; ba.pos = d_w + 5 * nb; if (hint) ba.hint = d_w + nb; }
+  if (kb_prev) ba.kb_prev = d_w + 2 * nb;
+  if (pos_prev) ba.pos_prev = d_w + 3 * nb;
+  if (kb_out) { ba.kb_out = d_w + 6 * nb; if (hint_out) ba.hint_out = d_w + 7 * nb; }
+  hipLaunchKernelGGL(k_bucket_boundaries, dim3(2), dim3(BK_T), 0, c->st, (const u64 *)d_keys, (long long)n0, ba);
+  HIPDOOR(who, hipGetLastError()); HIPDOOR(who, hipStreamSynchronize(c->st));
+  if (pos) HIPDOOR(who, hipMemcpy(pos, d_w + 5 * nb, nb * 4, hipMemcpyDeviceToHost));
+  if (kb_out) HIPDOOR(who, hipMemcpy(kb_out, d_w + 6 * nb, (size_t)B * 4, hipMemcpyDeviceToHost));
+  if (hint_out) HIPDOOR(who, hipMemcpy(hint_out, d_w + 7 * nb, (size_t)B * 4, hipMemcpyDeviceToHost));
   return SQMC_OK;
 }
 int sqmc_gpu_hci_connections_record(sqmc_gpu_ctx *c, int64_t n_ref, const uint64_t *ref_up, const uint64_t *ref_dn, const double *coeffs, double eps,
@@ -601,49 +573,37 @@ int sqmc_gpu_hci_pt2(sqmc_gpu_ctx *c, int64_t n_var, const uint64_t *var_up, con
   c->pt2_terms_ms = 0.0;
   double total = 0.0; long long nconn = 0;
   // sorted ranks of the variational determinants
-  u64 *vu, *vd, *vk, *vkalt; u32 *vv, *vvalt, *hist, *rowtot;
-  HIPCHK(hipMalloc(&vu, n_var * 8)); HIPCHK(hipMalloc(&vd, n_var * 8)); HIPCHK(hipMalloc(&vk, n_var * 8)); HIPCHK(hipMalloc(&vkalt, n_var * 8));
-  HIPCHK(hipMalloc(&vv, n_var * 4)); HIPCHK(hipMalloc(&vvalt, n_var * 4));
-  const long long vt = (n_var + RS_TILE - 1) / RS_TILE;
-  HIPCHK(hipMalloc(&hist, vt * RS_MAX_RADIX * 4)); HIPCHK(hipMalloc(&rowtot, RS_MAX_RADIX * 4));
+  const char *who = "sqmc_gpu_hci_pt2";
+  DevScratch s(st);
+  u64 *vu = s.take<u64>(n_var), *vd = s.take<u64>(n_var);
+  if (!s.ok()) return hip_fail(who, s.err());
   HIPCHK(hipMemcpy(vu, var_up, n_var * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(vd, var_dn, n_var * 8, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_main_keys, dim3(nblk(n_var)), dim3(TPB), 0, st, c->dev, vu, vd, vk, vv, (long long)n_var, 0);
-  SortWork so; so.k_alt = vkalt; so.v_alt = vvalt; so.hist = hist; so.rowtot = rowtot; so.cap = n_var;
-  u64 *skey = vk; u32 *sperm = vv;
-  device_radix_sort(skey, sperm, n_var, c->key_bits, so, st);
-  int rc = SQMC_OK;
-  for (int sl = 0; sl < n_slices && rc == SQMC_OK; sl++) {
-    HciDevOut d; int64_t U = 0;
-    rc = hci_connections_impl(c, n_var, var_up, var_dn, coeffs, eps_pt, 0, sl, n_slices, &U, nullptr, nullptr, nullptr, nullptr, &d, c->du_mode != 0);
-    if (rc != SQMC_OK) break;
+  u64 *skey; u32 *sperm;
+  { const int rs = det_ranks_sorted(c, who, n_var, vu, vd, s, s, &skey, &sperm); if (rs) return rs; }
+  EventMarks ev(timed, 2);
+  for (int sl = 0; sl < n_slices; sl++) {
+    HciDevOut d(st); int64_t U = 0;
+    const int rc = hci_connections_impl(c, n_var, var_up, var_dn, coeffs, eps_pt, 0, sl, n_slices, &U, nullptr, nullptr, nullptr, nullptr, &d, c->du_mode != 0);
+    if (rc != SQMC_OK) return rc;
     if (U > 0 && d.ou) {
       const int nb = std::min(nblk(U), 4096);
-      double *dpart; HIPCHK(hipMalloc(&dpart, nb * 8));
-      hipEvent_t ev[2];
-      if (timed) { HIPCHK(hipEventCreate(&ev[0])); HIPCHK(hipEventCreate(&ev[1])); HIPCHK(hipEventRecord(ev[0], st)); }
-      if (c->du_mode == 1)
-        hipLaunchKernelGGL(k_pt2_terms_upd<0>, dim3(nb), dim3(TPB), 0, st, c->dev, (const u64 *)d.ou, (const u64 *)d.od, (const double *)d.onum, (const double *)d.orold,
-                           (const unsigned *)d.orpk, (long long)U, (const u64 *)skey, (long long)n_var, e_var, dpart);
-      else if (c->du_mode == 2)
-        hipLaunchKernelGGL(k_pt2_terms_upd<1>, dim3(nb), dim3(TPB), 0, st, c->dev, (const u64 *)d.ou, (const u64 *)d.od, (const double *)d.onum, (const double *)d.orold,
-                           (const unsigned *)d.orpk, (long long)U, (const u64 *)skey, (long long)n_var, e_var, dpart);
+      double *dpart = d.mem.take<double>(nb);
+      if (!d.mem.ok()) return hip_fail(who, d.mem.err());
+      HIPCHK(ev.mark(st));
+      if (c->du_mode)
+        hipLaunchKernelGGL(c->du_mode == 1 ? k_pt2_terms_upd<0> : k_pt2_terms_upd<1>, dim3(nb), dim3(TPB), 0, st, c->dev, (const u64 *)d.ou, (const u64 *)d.od,
+                           (const double *)d.onum, (const double *)d.orold, (const unsigned *)d.orpk, (long long)U, (const u64 *)skey, (long long)n_var, e_var, dpart);
       else
         hipLaunchKernelGGL(k_pt2_terms, dim3(nb), dim3(TPB), 0, st, c->dev, (const u64 *)d.ou, (const u64 *)d.od, (const double *)d.onum, (long long)U,
                            (const u64 *)skey, (long long)n_var, e_var, dpart);
-      if (timed) HIPCHK(hipEventRecord(ev[1], st));
+      HIPCHK(ev.mark(st));
       std::vector<double> part(nb);
       HIPCHK(hipMemcpyAsync(part.data(), dpart, nb * 8, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st));
-      if (timed) { float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1])); c->pt2_terms_ms += ms; hipEventDestroy(ev[0]); hipEventDestroy(ev[1]); }
+      ev.add(&c->pt2_terms_ms);
       double ssum = 0.0; for (int q = 0; q < nb; q++) ssum += part[q];          // block partials in block order
       total += ssum; nconn += U;
-      hipFree(dpart);
     }
-    void *fr[] = {d.ou, d.od, d.onum, d.oden, d.dru, d.drd, d.orold, d.orpk};
-    for (void *q : fr) hipFree(q);
   }
-  void *fv[] = {vu, vd, vk, vkalt, vv, vvalt, hist, rowtot};
-  for (void *q : fv) hipFree(q);
-  if (rc != SQMC_OK) return rc;
   *delta_e = total; *n_connections = nconn;
   return SQMC_OK;
 }
@@ -656,13 +616,14 @@ int sqmc_gpu_hci_pt2(sqmc_gpu_ctx *c, int64_t n_var, const uint64_t *var_up, con
 struct sqmc_pt2s_plan {
   sqmc_gpu_ctx *c; long long n_var; int n_mc; double e_var, eps_pt, eps_pt_big;
   std::vector<double> prob;          // p_i = |c_i| / sum |c|
-  u64 *vu, *vd, *vk, *vkalt, *skey; double *vc;                       // variational determinants, coefficients, sorted ranks (skey: vk or vkalt)
+  u64 *vu, *vd, *skey; double *vc;                                    // variational determinants, coefficients, sorted ranks
   char *h_in; u64 *h_out;                                             // pinned: a sample's (w/p, ids) on the way in; total / (sum, count) on the way out
   char *d_in; u64 *d_ru, *d_rd, *d_cnt, *d_off, *d_tot, *d_scan, *d_out; double *d_rc; long long scan_tiles;
   long long cap; u64 *du, *dd, *keys, *kalt; double *dx, *dsrc; u32 *vals, *valt, *hist, *rowtot;     // per connection, capacity cap
   double *d_part; u64 *d_pcnt;
   int du_mode; double *drold; unsigned *drpk;                         // sqmc_gpu_hci_set_diag_update as it stood at prepare; the records, capacity cap (null in mode 0)
   long long n_alloc, n_samples, last_raw, max_raw;
+  DevScratch mem, conn;              // owners of the device buffers above: those of the plan's lifetime; those of capacity cap, replaced when a sample outgrows them
 };
 // sum of n doubles in the blocked pairwise order (leaves of at most 128 summed in 8 interleaved accumulators, halves split on a
 // multiple of 8): error O(log n) ulp, and the order numpy's sum uses, so that p_i has the bits of the host path
@@ -680,53 +641,52 @@ static double pt2s_pairwise_sum(const double *a, long long n) {
   return pt2s_pairwise_sum(a, n2) + pt2s_pairwise_sum(a + n2, n - n2);
 }
 static void pt2s_free_conn(sqmc_pt2s_plan *p) {
-  void *fr[] = {p->du, p->dd, p->keys, p->kalt, p->dx, p->dsrc, p->vals, p->valt, p->hist, p->drold, p->drpk};
-  for (void *q : fr) hipFree(q);
-  p->drold = nullptr; p->drpk = nullptr;
-  p->du = p->dd = p->keys = p->kalt = nullptr; p->dx = p->dsrc = nullptr; p->vals = p->valt = p->hist = nullptr; p->cap = 0;
+  p->conn.clear();
+  p->du = p->dd = p->keys = p->kalt = nullptr; p->dx = p->dsrc = p->drold = nullptr; p->vals = p->valt = p->hist = p->drpk = nullptr; p->cap = 0;
 }
 static int pt2s_grow(sqmc_pt2s_plan *p, long long need) {
   pt2s_free_conn(p);
   long long cap = need + need / 4 + 1024;
   if (cap > (1ll << 31) - 1) cap = (1ll << 31) - 1;
-  HIPCHK(hipMalloc(&p->du, cap * 8)); HIPCHK(hipMalloc(&p->dd, cap * 8)); HIPCHK(hipMalloc(&p->dx, cap * 8)); HIPCHK(hipMalloc(&p->dsrc, cap * 8));
-  HIPCHK(hipMalloc(&p->keys, cap * 8)); HIPCHK(hipMalloc(&p->kalt, cap * 8)); HIPCHK(hipMalloc(&p->vals, cap * 4)); HIPCHK(hipMalloc(&p->valt, cap * 4));
-  HIPCHK(hipMalloc(&p->hist, (size_t)RS_MAX_RADIX * ((cap + RS_TILE - 1) / RS_TILE + 1) * 4));
-  if (p->du_mode) { HIPCHK(hipMalloc(&p->drold, cap * 8)); HIPCHK(hipMalloc(&p->drpk, cap * 4)); }
+  DevScratch &s = p->conn;
+  p->du = s.take<u64>(cap); p->dd = s.take<u64>(cap); p->dx = s.take<double>(cap); p->dsrc = s.take<double>(cap);
+  p->keys = s.take<u64>(cap); p->kalt = s.take<u64>(cap); p->vals = s.take<u32>(cap); p->valt = s.take<u32>(cap);
+  p->hist = s.take<u32>((size_t)RS_MAX_RADIX * ((cap + RS_TILE - 1) / RS_TILE + 1));
+  if (p->du_mode) { p->drold = s.take<double>(cap); p->drpk = s.take<unsigned>(cap); }
+  if (!s.ok()) { const hipError_t e = s.err(); pt2s_free_conn(p); return hip_fail("sqmc_gpu_hci_pt2_stochastic_sample", e); }
   p->cap = cap; p->n_alloc++;
   return SQMC_OK;
 }
 int sqmc_gpu_hci_pt2_stochastic_free(sqmc_pt2s_plan *p) {
   if (!p) return SQMC_OK;
-  pt2s_free_conn(p);
-  void *fr[] = {p->vu, p->vd, p->vk, p->vkalt, p->vc, p->d_in, p->d_ru, p->d_rd, p->d_cnt, p->d_off, p->d_tot, p->d_scan, p->d_out, p->d_rc, p->rowtot, p->d_part, p->d_pcnt};
-  for (void *q : fr) hipFree(q);
-  if (p->h_in) hipHostFree(p->h_in);
+  p->conn.clear(); p->mem.clear();   // these wait for the context's stream (the handle of prepare: the plan goes before its context, as the header says)
+  if (p->h_in) hipHostFree(p->h_in);   // behind the owners: nothing queued can still read the pinned buffers
   if (p->h_out) hipHostFree(p->h_out);
   delete p;
   return SQMC_OK;
 }
 static int pt2s_prepare(sqmc_pt2s_plan *p, const uint64_t *var_up, const uint64_t *var_dn, const double *coeffs) {
+  const char *who = "sqmc_gpu_hci_pt2_stochastic_prepare";
   sqmc_gpu_ctx *c = p->c; hipStream_t st = c->st; const long long n = p->n_var, m = p->n_mc;
-  HIPCHK(hipMalloc(&p->vu, n * 8)); HIPCHK(hipMalloc(&p->vd, n * 8)); HIPCHK(hipMalloc(&p->vc, n * 8)); HIPCHK(hipMalloc(&p->vk, n * 8)); HIPCHK(hipMalloc(&p->vkalt, n * 8));
-  u32 *vv, *vvalt, *hist;
-  HIPCHK(hipMalloc(&vv, n * 4)); HIPCHK(hipMalloc(&vvalt, n * 4));
-  HIPCHK(hipMalloc(&hist, (size_t)RS_MAX_RADIX * ((n + RS_TILE - 1) / RS_TILE + 1) * 4)); HIPCHK(hipMalloc(&p->rowtot, RS_MAX_RADIX * 4));
+  DevScratch &s = p->mem;
+  p->vu = s.take<u64>(n); p->vd = s.take<u64>(n); p->vc = s.take<double>(n);
+  if (!s.ok()) return hip_fail(who, s.err());
   HIPCHK(hipMemcpy(p->vu, var_up, n * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(p->vd, var_dn, n * 8, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(p->vc, coeffs, n * 8, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_main_keys, dim3(nblk(n)), dim3(TPB), 0, st, c->dev, p->vu, p->vd, p->vk, vv, n, 0);
-  SortWork so; so.k_alt = p->vkalt; so.v_alt = vvalt; so.hist = hist; so.rowtot = p->rowtot; so.cap = n;
-  u64 *skey = p->vk; u32 *sperm = vv;
-  device_radix_sort(skey, sperm, n, c->key_bits, so, st);
-  HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(st));
-  p->skey = skey;
-  hipFree(vv); hipFree(vvalt); hipFree(hist);
+  {
+    DevScratch work(st);             // the permutation and the histogram go before the sample buffers come
+    u32 *sperm;
+    const int rs = det_ranks_sorted(c, who, n, p->vu, p->vd, s, work, &p->skey, &sperm, &p->rowtot);
+    if (rs) return rs;
+    HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(st));
+  }
   HIPCHK(hipHostMalloc(&p->h_in, m * 12 + 16)); HIPCHK(hipHostMalloc(&p->h_out, 32));
-  HIPCHK(hipMalloc(&p->d_in, m * 12 + 16)); HIPCHK(hipMalloc(&p->d_ru, m * 8)); HIPCHK(hipMalloc(&p->d_rd, m * 8)); HIPCHK(hipMalloc(&p->d_rc, m * 8));
-  HIPCHK(hipMalloc(&p->d_cnt, m * 8)); HIPCHK(hipMalloc(&p->d_off, m * 8)); HIPCHK(hipMalloc(&p->d_tot, 8)); HIPCHK(hipMalloc(&p->d_out, 16));
+  p->d_in = s.take<char>(m * 12 + 16); p->d_ru = s.take<u64>(m); p->d_rd = s.take<u64>(m); p->d_rc = s.take<double>(m);
+  p->d_cnt = s.take<u64>(m); p->d_off = s.take<u64>(m); p->d_tot = s.take<u64>(1); p->d_out = s.take<u64>(2);
   p->scan_tiles = (m + SCAN_TILE - 1) / SCAN_TILE + 1;
-  HIPCHK(hipMalloc(&p->d_scan, (p->scan_tiles + 1) * 8));
-  HIPCHK(hipMalloc(&p->d_part, PT2S_MAXBLK * 8)); HIPCHK(hipMalloc(&p->d_pcnt, PT2S_MAXBLK * 8));
+  p->d_scan = s.take<u64>(p->scan_tiles + 1);
+  p->d_part = s.take<double>(PT2S_MAXBLK); p->d_pcnt = s.take<u64>(PT2S_MAXBLK);
+  if (!s.ok()) return hip_fail(who, s.err());
   return SQMC_OK;
 }
 int sqmc_gpu_hci_pt2_stochastic_prepare(sqmc_gpu_ctx *c, int64_t n_var, const uint64_t *var_up, const uint64_t *var_dn, const double *coeffs, double e_var,
@@ -744,6 +704,7 @@ int sqmc_gpu_hci_pt2_stochastic_prepare(sqmc_gpu_ctx *c, int64_t n_var, const ui
       return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_hci_pt2_stochastic_prepare: the variational determinants must be sorted by (up, dn) without repeats (hci.f90:1373-1380)");
   sqmc_pt2s_plan *p = new sqmc_pt2s_plan();       // value-initialised: every pointer null, every counter 0
   p->c = c; p->n_var = n_var; p->n_mc = n_mc; p->e_var = e_var; p->eps_pt = eps_pt; p->eps_pt_big = eps_pt_big; p->du_mode = c->du_mode;
+  p->mem.stream = p->conn.stream = c->st;
   p->prob.resize(n_var);
   for (long long i = 0; i < n_var; i++) p->prob[i] = fabs(coeffs[i]);
   double norm = 0.0;                              // numpy adds the pairwise sums of consecutive 8192-element pieces left to right
@@ -778,8 +739,7 @@ int sqmc_gpu_hci_pt2_stochastic_sample(sqmc_pt2s_plan *p, int64_t n_distinct, co
   if (total >= (1ull << 31)) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_hci_pt2_stochastic_sample: 2^31 or more raw connections in one sample (no slicing here: lower n_mc or raise eps_pt)");
   const long long T = (long long)total;
   p->last_raw = T; if (T > p->max_raw) p->max_raw = T;
-  *value = 0.0; *n_connected = 0;
-  if (T == 0) { p->n_samples++; return SQMC_OK; }
+  if (T == 0) { *value = 0.0; *n_connected = 0; p->n_samples++; return SQMC_OK; }
   if (T > p->cap) { const int rc = pt2s_grow(p, T); if (rc != SQMC_OK) return rc; }
   if (p->du_mode)
     hipLaunchKernelGGL(k_hci_gen<true>, dim3(nblk(m)), dim3(TPB), 0, st, c->dev, p->d_ru, p->d_rd, p->d_rc, p->eps_pt, 2, m, 1, p->d_cnt, p->d_off,
@@ -792,12 +752,8 @@ int sqmc_gpu_hci_pt2_stochastic_sample(sqmc_pt2s_plan *p, int64_t n_distinct, co
   u64 *skey = p->keys; u32 *perm = p->vals;
   device_radix_sort(skey, perm, T, c->key_bits, so, st);
   const int nb = std::min(nblk(T), PT2S_MAXBLK);
-  if (p->du_mode == 1)
-    hipLaunchKernelGGL(k_pt2s_terms_upd<0>, dim3(nb), dim3(TPB), 0, st, c->dev, (const u64 *)skey, (const u32 *)perm, (const u64 *)p->du, (const u64 *)p->dd,
-                       (const double *)p->dx, (const double *)p->dsrc, (const double *)p->drold, (const unsigned *)p->drpk, d_wop, T, (const u64 *)p->skey, p->n_var,
-                       p->e_var, p->eps_pt_big, (double)(p->n_mc - 1), p->d_part, p->d_pcnt);
-  else if (p->du_mode == 2)
-    hipLaunchKernelGGL(k_pt2s_terms_upd<1>, dim3(nb), dim3(TPB), 0, st, c->dev, (const u64 *)skey, (const u32 *)perm, (const u64 *)p->du, (const u64 *)p->dd,
+  if (p->du_mode)
+    hipLaunchKernelGGL(p->du_mode == 1 ? k_pt2s_terms_upd<0> : k_pt2s_terms_upd<1>, dim3(nb), dim3(TPB), 0, st, c->dev, (const u64 *)skey, (const u32 *)perm, (const u64 *)p->du, (const u64 *)p->dd,
                        (const double *)p->dx, (const double *)p->dsrc, (const double *)p->drold, (const unsigned *)p->drpk, d_wop, T, (const u64 *)p->skey, p->n_var,
                        p->e_var, p->eps_pt_big, (double)(p->n_mc - 1), p->d_part, p->d_pcnt);
   else
@@ -832,21 +788,21 @@ int sqmc_gpu_spmv_prepare(int64_t n, const int64_t *rc, const int64_t *idx, cons
   if (2 * nnz >= (1ll << 31)) return fail(SQMC_ERR_UNSUPPORTED, "more than 2^31 expanded nonzeros");
   std::vector<int> ptr, col; std::vector<double> v;
   expand_full_csr(n, rc, idx, val, ptr, col, v);
-  sqmc_spmv_plan *p = new sqmc_spmv_plan(); p->n = n; p->nnz_full = (long long)col.size();
-  HIPCHK(hipStreamCreate(&p->st));
-  HIPCHK(hipMalloc(&p->d_ptr, (n + 1) * 4)); HIPCHK(hipMalloc(&p->d_col, (col.size() + 1) * 4)); HIPCHK(hipMalloc(&p->d_val, (v.size() + 1) * 8));
-  HIPCHK(hipMalloc(&p->d_x, n * 8)); HIPCHK(hipMalloc(&p->d_y, n * 8));
+  SpmvPlanOwned *p = nullptr;
+  { const int rp = spmv_plan_new(n, (long long)col.size(), &p); if (rp) return rp; }
+  std::unique_ptr<sqmc_spmv_plan, int (*)(sqmc_spmv_plan *)> guard(p, sqmc_gpu_spmv_free);
   HIPCHK(hipMemcpy(p->d_ptr, ptr.data(), (n + 1) * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(p->d_col, col.data(), col.size() * 4, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(p->d_val, v.data(), v.size() * 8, hipMemcpyHostToDevice));
   if (getenv("SQMC_SPMV_UPPER_ATOMIC")) {        // measurement only: the stored triangle + atomics (spmv_kernels.h)
     std::vector<int> up(n + 1, 0), uc(nnz);
     for (long long i = 0; i < n; i++) up[i + 1] = up[i] + (int)rc[i];
     for (long long k = 0; k < nnz; k++) uc[k] = (int)(idx[k] - 1);
-    HIPCHK(hipMalloc(&p->u_ptr, (n + 1) * 4)); HIPCHK(hipMalloc(&p->u_col, (nnz + 1) * 4)); HIPCHK(hipMalloc(&p->u_val, (nnz + 1) * 8));
+    p->u_ptr = p->mem.take<int>(n + 1); p->u_col = p->mem.take<int>(nnz + 1); p->u_val = p->mem.take<double>(nnz + 1);
+    if (!p->mem.ok()) return hip_fail("sqmc_gpu_spmv_prepare", p->mem.err());
     HIPCHK(hipMemcpy(p->u_ptr, up.data(), (n + 1) * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(p->u_col, uc.data(), nnz * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(p->u_val, val, nnz * 8, hipMemcpyHostToDevice));
   }
-  *plan = p;
+  *plan = guard.release();
   return SQMC_OK;
 }
 int sqmc_gpu_spmv_apply(sqmc_spmv_plan *p, const double *x, double *y, int on_device) {
@@ -871,7 +827,8 @@ int sqmc_gpu_spmv_apply(sqmc_spmv_plan *p, const double *x, double *y, int on_de
 }
 int sqmc_gpu_spmv_free(sqmc_spmv_plan *p) {
   if (!p) return SQMC_OK;
-  hipFree(p->d_ptr); hipFree(p->d_col); hipFree(p->d_val); hipFree(p->d_x); hipFree(p->d_y); hipFree(p->u_ptr); hipFree(p->u_col); hipFree(p->u_val); hipStreamDestroy(p->st); delete p;
+  SpmvPlanOwned *q = static_cast<SpmvPlanOwned *>(p);      // every plan is made by spmv_plan_new
+  q->mem.clear(); hipStreamDestroy(q->st); delete q;
   return SQMC_OK;
 }
 int sqmc_gpu_spmv_sym_upper(int64_t n, const int64_t *rc, const int64_t *idx, const double *val, const double *x, double *y) {
@@ -882,3 +839,13 @@ int sqmc_gpu_spmv_sym_upper(int64_t n, const int64_t *rc, const int64_t *idx, co
   sqmc_gpu_spmv_free(p);
   return r;
 }
+
+// ----------------------------------------------------------------------- the scratch owner's counters (dev_scratch.h); not part of the ABI
+int sqmc_gpu_debug_scratch(int64_t *live_allocs, int64_t *live_bytes, int64_t *peak_bytes, int64_t *n_takes, int reset_peak) {
+  if (live_allocs) *live_allocs = g_scratch_stats.live_allocs; if (live_bytes) *live_bytes = g_scratch_stats.live_bytes;
+  if (peak_bytes) *peak_bytes = g_scratch_stats.peak_bytes; if (n_takes) *n_takes = g_scratch_stats.n_takes;       // peak: the most live_bytes has been since the last reset
+  if (reset_peak) g_scratch_stats.peak_bytes = g_scratch_stats.live_bytes.load();
+  return SQMC_OK;
+}
+// the nth take from now on fails without calling hipMalloc, once; 0 disarms
+int sqmc_gpu_debug_scratch_fail_at(int64_t nth) { g_scratch_stats.fail_at = nth > 0 ? nth : 0; return SQMC_OK; }

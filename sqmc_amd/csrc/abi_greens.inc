@@ -20,19 +20,19 @@ static int gf_half_dev(bool NP1, sqmc_gpu_ctx *c, const RdmList &L, double e0, i
   if (ctile < 1) ctile = 1;
   if (ctile > nchunks) ctile = nchunks;
   const long long dtile = ctile * GF_CHUNK;
-  double *poles = nullptr, *part = nullptr;
-  hipError_t e = hipMalloc(&poles, (size_t)(dtile < L.n ? dtile : L.n) * nslot * 8);
-  if (e == hipSuccess) e = hipMalloc(&part, (size_t)ctile * wt_max * nn * 2 * 8);
-  hipEvent_t ev[3]; const bool timed = gf_timed() && e == hipSuccess;
-  if (timed) for (hipEvent_t &q : ev) hipEventCreate(&q);
-  for (long long j0 = 0; j0 < L.n && e == hipSuccess; j0 += dtile) {
+  const char *who = "sqmc_gpu_hci_greens_function";
+  DevScratch s(st);
+  double *poles = s.take<double>((size_t)(dtile < L.n ? dtile : L.n) * nslot), *part = s.take<double>((size_t)ctile * wt_max * nn * 2);
+  if (!s.ok()) return hip_fail(who, s.err());
+  EventMarks ev(gf_timed(), 3);
+  for (long long j0 = 0; j0 < L.n; j0 += dtile) {
     const long long nd = (L.n - j0 < dtile) ? L.n - j0 : dtile;
     const int nch = (int)((nd + GF_CHUNK - 1) / GF_CHUNK);
     const int last = (j0 + dtile >= L.n) ? 1 : 0;
-    if (timed) hipEventRecord(ev[0], st);
+    HIPDOOR(who, ev.mark(st));
     if (NP1) hipLaunchKernelGGL(k_gf_poles<true>, dim3(nblk(nd * nslot)), dim3(TPB), 0, st, c->dev, (const u64 *)L.su, (const u64 *)L.sd, j0, nd, n_su, nslot, e0, poles);
     else hipLaunchKernelGGL(k_gf_poles<false>, dim3(nblk(nd * nslot)), dim3(TPB), 0, st, c->dev, (const u64 *)L.su, (const u64 *)L.sd, j0, nd, n_su, nslot, e0, poles);
-    if (timed) hipEventRecord(ev[1], st);
+    HIPDOOR(who, ev.mark(st));
     for (int w0 = 0; w0 < n_w; w0 += GF_WTILE) {
       const int wt = (n_w - w0 < GF_WTILE) ? n_w - w0 : GF_WTILE;
       if (NP1) hipLaunchKernelGGL(k_gf_terms<true>, dim3(nch, (unsigned)(nn * 2)), dim3(GF_T), 0, st, c->dev, (const u64 *)L.su, (const u64 *)L.sd, (const double *)L.sc,
@@ -41,17 +41,10 @@ static int gf_half_dev(bool NP1, sqmc_gpu_ctx *c, const RdmList &L, double e0, i
                               (const u64 *)L.skey, L.n, j0, nd, (const double *)poles, norb, n_su, nslot, fermi, d_w + w0, wt, part);
       hipLaunchKernelGGL(k_gf_sum, dim3(nblk((long long)wt * nn)), dim3(TPB), 0, st, (const double *)part, nch, norb, wt, w0, n_w, last, d_run, d_g);
     }
-    e = hipGetLastError();
-    if (timed && e == hipSuccess) e = hipEventRecord(ev[2], st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);         // the next tile writes poles and part again
-    if (timed && e == hipSuccess) {
-      float a = 0.f, b = 0.f;
-      if (hipEventElapsedTime(&a, ev[0], ev[1]) == hipSuccess && hipEventElapsedTime(&b, ev[1], ev[2]) == hipSuccess) { c->gf_ms[0] += a; c->gf_ms[1] += b; }
-    }
+    HIPDOOR(who, hipGetLastError()); HIPDOOR(who, ev.mark(st));
+    HIPDOOR(who, hipStreamSynchronize(st));         // the next tile writes poles and part again
+    ev.add(c->gf_ms);
   }
-  if (timed) for (hipEvent_t &q : ev) hipEventDestroy(q);
-  hipFree(poles); hipFree(part);
-  if (e != hipSuccess) { (void)hipGetLastError(); return fail(SQMC_ERR_HIP, std::string("sqmc_gpu_hci_greens_function: ") + hipGetErrorString(e)); }
   return SQMC_OK;
 }
 
@@ -68,27 +61,23 @@ int sqmc_gpu_hci_greens_function(sqmc_gpu_ctx *c, int64_t n_var, const uint64_t 
   if (!c->dev.integrals) return fail(SQMC_ERR_BAD_ARG, std::string(who) + ": the context holds no integrals");
   const int norb = c->htab.norb;
   const size_t nn = (size_t)norb * norb, ng = (size_t)n_w * nn;
-  RdmList L;
+  RdmList L(c->st);
   int rc = rdm_list_build(c, who, n_var, var_up, var_dn, coeffs, L);
   if (rc != SQMC_OK) return rc;
   c->gf_ms[0] = c->gf_ms[1] = 0.0;
-  double *d_w = nullptr, *d_run = nullptr, *d_g = nullptr;
   std::vector<double> host_p(g_np1 ? ng : 0), host_m(g_nm1 ? ng : 0);
-  hipError_t e = hipMalloc(&d_w, (size_t)n_w * 8);
-  if (e == hipSuccess) e = hipMalloc(&d_run, ng * 2 * 8);
-  if (e == hipSuccess) e = hipMalloc(&d_g, ng * 8);
-  if (e == hipSuccess) e = hipMemcpy(d_w, w, (size_t)n_w * 8, hipMemcpyHostToDevice);
-  if (e != hipSuccess) { (void)hipGetLastError(); rc = fail(SQMC_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e)); }
-  if (rc == SQMC_OK && g_np1) {
-    rc = gf_half_dev(true, c, L, e0, n_w, d_w, fermi_sign, d_run, d_g);
-    if (rc == SQMC_OK && hipMemcpy(host_p.data(), d_g, ng * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(SQMC_ERR_HIP, std::string(who) + ": copy back failed");
+  DevScratch s(c->st);
+  double *d_w = s.take<double>(n_w), *d_run = s.take<double>(ng * 2), *d_g = s.take<double>(ng);
+  if (!s.ok()) return hip_fail(who, s.err());
+  HIPDOOR(who, hipMemcpy(d_w, w, (size_t)n_w * 8, hipMemcpyHostToDevice));
+  if (g_np1) {
+    if ((rc = gf_half_dev(true, c, L, e0, n_w, d_w, fermi_sign, d_run, d_g)) != SQMC_OK) return rc;
+    if (hipMemcpy(host_p.data(), d_g, ng * 8, hipMemcpyDeviceToHost) != hipSuccess) return fail(SQMC_ERR_HIP, std::string(who) + ": copy back failed");
   }
-  if (rc == SQMC_OK && g_nm1) {
-    rc = gf_half_dev(false, c, L, e0, n_w, d_w, fermi_sign, d_run, d_g);
-    if (rc == SQMC_OK && hipMemcpy(host_m.data(), d_g, ng * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(SQMC_ERR_HIP, std::string(who) + ": copy back failed");
+  if (g_nm1) {
+    if ((rc = gf_half_dev(false, c, L, e0, n_w, d_w, fermi_sign, d_run, d_g)) != SQMC_OK) return rc;
+    if (hipMemcpy(host_m.data(), d_g, ng * 8, hipMemcpyDeviceToHost) != hipSuccess) return fail(SQMC_ERR_HIP, std::string(who) + ": copy back failed");
   }
-  hipFree(d_w); hipFree(d_run); hipFree(d_g); rdm_list_free(L);
-  if (rc != SQMC_OK) return rc;
   if (g_np1) memcpy(g_np1, host_p.data(), ng * 8);      // only finished arrays reach the caller
   if (g_nm1) memcpy(g_nm1, host_m.data(), ng * 8);
   return SQMC_OK;

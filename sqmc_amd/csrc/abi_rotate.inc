@@ -36,30 +36,25 @@ int sqmc_gpu_rotate_integrals(sqmc_gpu_ctx *c, const double *rot, double *integr
     }
   if (A * (A - 1) / 2 + A > c->n_ints) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_rotate_integrals: integral table shorter than integral_index(norb+1,...)");
   const size_t n_out = (size_t)c->n_ints + 1, lds = (size_t)3 * nn * sizeof(double);
-  double *d_rot = nullptr, *d_work = nullptr, *d_out = nullptr;
+  const char *who = "sqmc_gpu_rotate_integrals";
   std::vector<double> host(n_out);
-  hipEvent_t ev[4]; int n_ev = 0; const bool timed = rot_timed();
   c->rot_ms[0] = c->rot_ms[1] = c->rot_ms[2] = 0.0;
-  hipError_t e = hipMalloc(&d_rot, (size_t)nn * 8);
-  if (e == hipSuccess) e = hipMalloc(&d_work, (size_t)npair * npair * 8);
-  if (e == hipSuccess) e = hipMalloc(&d_out, n_out * 8);
-  if (e == hipSuccess) e = hipMemcpy(d_rot, rot, (size_t)nn * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, n_out * 8, c->st);      // every slot no kernel addresses is 0.0
-  while (timed && n_ev < 4 && e == hipSuccess) { e = hipEventCreate(&ev[n_ev]); if (e == hipSuccess) n_ev++; }
-  if (timed && e == hipSuccess) e = hipEventRecord(ev[0], c->st);
-  if (e == hipSuccess) e = rot_launch_mode<ROT_HALF1>(c, (int)npair, lds, d_rot, c->d_ints, d_work);
-  if (timed && e == hipSuccess) e = hipEventRecord(ev[1], c->st);
-  if (e == hipSuccess) e = rot_launch_mode<ROT_HALF2>(c, (int)npair, lds, d_rot, d_work, d_out);
-  if (timed && e == hipSuccess) e = hipEventRecord(ev[2], c->st);
-  if (e == hipSuccess) e = rot_launch_mode<ROT_ONE>(c, 1, lds, d_rot, c->d_ints, d_out);
-  if (timed && e == hipSuccess) e = hipEventRecord(ev[3], c->st);
-  if (e == hipSuccess) e = hipMemcpyAsync(host.data(), d_out, n_out * 8, hipMemcpyDeviceToHost, c->st);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->st);
-  if (timed && e == hipSuccess)
-    for (int k = 0; k < 3; k++) { float ms = 0.f; if (hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess) c->rot_ms[k] = ms; }
-  for (int k = 0; k < n_ev; k++) hipEventDestroy(ev[k]);
-  hipFree(d_rot); hipFree(d_work); hipFree(d_out);
-  if (e != hipSuccess) { (void)hipGetLastError(); return fail(SQMC_ERR_HIP, std::string("sqmc_gpu_rotate_integrals: ") + hipGetErrorString(e)); }
+  DevScratch s(c->st);
+  double *d_rot = s.take<double>(nn), *d_work = s.take<double>((size_t)npair * npair), *d_out = s.take<double>(n_out);
+  if (!s.ok()) return hip_fail(who, s.err());
+  HIPDOOR(who, hipMemcpy(d_rot, rot, (size_t)nn * 8, hipMemcpyHostToDevice));
+  HIPDOOR(who, hipMemsetAsync(d_out, 0, n_out * 8, c->st));      // every slot no kernel addresses is 0.0
+  EventMarks ev(rot_timed(), 4);
+  HIPDOOR(who, ev.mark(c->st));
+  HIPDOOR(who, rot_launch_mode<ROT_HALF1>(c, (int)npair, lds, d_rot, c->d_ints, d_work));
+  HIPDOOR(who, ev.mark(c->st));
+  HIPDOOR(who, rot_launch_mode<ROT_HALF2>(c, (int)npair, lds, d_rot, d_work, d_out));
+  HIPDOOR(who, ev.mark(c->st));
+  HIPDOOR(who, rot_launch_mode<ROT_ONE>(c, 1, lds, d_rot, c->d_ints, d_out));
+  HIPDOOR(who, ev.mark(c->st));
+  HIPDOOR(who, hipMemcpyAsync(host.data(), d_out, n_out * 8, hipMemcpyDeviceToHost, c->st));
+  HIPDOOR(who, hipStreamSynchronize(c->st));
+  ev.add(c->rot_ms);
   memcpy(integrals_out, host.data(), n_out * 8);      // only a finished table reaches the caller
   return SQMC_OK;
 }

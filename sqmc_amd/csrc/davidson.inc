@@ -180,12 +180,10 @@ int sqmc_gpu_davidson(sqmc_spmv_plan *p, const double *diag, int32_t n_states, c
   const int niter = (int)std::min<long long>(n, (long long)m_max);
   hipStream_t st = p->st;
   const int nb = (int)std::min<long long>((n + DV_TPB - 1) / DV_TPB, DV_MAXB);
-  double *V = nullptr, *HV = nullptr, *W = nullptr, *HW = nullptr, *t = nullptr, *dd = nullptr, *part = nullptr, *dy = nullptr;
-  struct Free { std::vector<void *> v; ~Free() { for (void *q : v) hipFree(q); } } fr;
-#define DV_ALLOC(P, BYTES) do { HIPCHK(hipMalloc(&P, (BYTES))); fr.v.push_back(P); } while (0)
-  DV_ALLOC(V, (size_t)n * m_max * 8); DV_ALLOC(HV, (size_t)n * m_max * 8); DV_ALLOC(W, (size_t)n * k * 8); DV_ALLOC(HW, (size_t)n * k * 8);
-  DV_ALLOC(t, (size_t)n * 8); DV_ALLOC(dd, (size_t)n * 8); DV_ALLOC(part, (size_t)(m_max + 2) * nb * 8); DV_ALLOC(dy, (size_t)m_max * k * 8);
-#undef DV_ALLOC
+  DevScratch s(st);
+  double *V = s.take<double>((size_t)n * m_max), *HV = s.take<double>((size_t)n * m_max), *W = s.take<double>((size_t)n * k), *HW = s.take<double>((size_t)n * k);
+  double *t = s.take<double>(n), *dd = s.take<double>(n), *part = s.take<double>((size_t)(m_max + 2) * nb), *dy = s.take<double>((size_t)m_max * k);
+  if (!s.ok()) return hip_fail("sqmc_gpu_davidson", s.err());
   HIPCHK(hipMemcpyAsync(dd, diag, n * 8, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(V, 0, (size_t)n * m_max * 8, st));
   std::vector<double> hpart((size_t)(m_max + 2) * nb);

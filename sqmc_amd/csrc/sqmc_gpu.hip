@@ -28,6 +28,7 @@
 #include <vector>
 #include <string>
 #include <algorithm>
+#include <memory>
 #include "../../include/sqmc_gpu.h"
 #include "chem_device.h"
 #include "heatbath_device.h"
@@ -36,12 +37,16 @@
 #include "spawn_prof.h"
 #include "bucket_partition.h"
 #include "hii_group.h"
+#include "dev_scratch.h"
 
 #define TPB 256
 #define SPAWN_WIN 1024
 static thread_local std::string g_err;
 static int fail(int code, const std::string &m) { g_err = m; return code; }
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(SQMC_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
+// the doors' form of a HIP failure: "door name: hipGetErrorString"
+static int hip_fail(const char *who, hipError_t e) { return fail(SQMC_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e)); }
+#define HIPDOOR(who, x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return hip_fail(who, e_); } while (0)
 static inline int nblk(long long n, int tpb = TPB) { return (int)((n + tpb - 1) / tpb); }
 
 // ------------------------------------------------------------------ walker SoA in HBM
@@ -551,7 +556,7 @@ int sqmc_gpu_set_hubbardk_space_sym(sqmc_gpu_ctx *c, int32_t z, int32_t p, const
   return SQMC_OK;
 }
 // with space_sym: every determinant of an uploaded list must be its own representative and have a state in the (z, p) sector.
-// (Both doors below work in ONE device buffer that their caller-side half allocates and frees, whatever the HIP calls in between return.)
+// (the check works in ONE device buffer that its caller-side half allocates and frees, whatever the HIP calls in between return)
 static int hk_sym_check_run(sqmc_gpu_ctx *c, int64_t n, const uint64_t *up, const uint64_t *dn, u64 *buf, unsigned long long *bad) {
   u64 *du = buf, *dd = buf + n; unsigned long long *dbad = (unsigned long long *)(buf + 2 * n);
   HIPCHK(hipMemcpy(du, up, n * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dd, dn, n * 8, hipMemcpyHostToDevice));
@@ -571,8 +576,17 @@ static int hk_sym_check_list(sqmc_gpu_ctx *c, int64_t n, const uint64_t *up, con
   if (bad < (unsigned long long)n) return fail(SQMC_ERR_BAD_ARG, what);
   return SQMC_OK;
 }
-static int hk_sym_images_run(sqmc_gpu_ctx *c, int64_t n, const uint64_t *up, const uint64_t *dn, uint64_t *images_up, uint64_t *images_dn, int32_t *phases,
-                             uint64_t *rep_up, uint64_t *rep_dn, int32_t *phase_w_rep, double *norm, int32_t *num_distinct, u64 *buf) {
+int sqmc_gpu_hubbardk_sym_images(sqmc_gpu_ctx *c, int64_t n, const uint64_t *up, const uint64_t *dn, uint64_t *images_up, uint64_t *images_dn, int32_t *phases,
+                                 uint64_t *rep_up, uint64_t *rep_dn, int32_t *phase_w_rep, double *norm, int32_t *num_distinct) {
+  if (!c) return fail(SQMC_ERR_BAD_ARG, "null ctx");
+  if (c->htab.sys_type != 3 || !c->htab.hk_sym) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_hubbardk_sym_images: not a hubbardk context with space_sym set");
+  if (n <= 0) return SQMC_OK;
+  if (!up || !dn || !images_up || !images_dn || !phases || !rep_up || !rep_dn || !phase_w_rep || !norm || !num_distinct) return fail(SQMC_ERR_BAD_ARG, "null argument");
+  const u64 lim = c->htab.orb_mask;
+  for (long long i = 0; i < n; i++) if ((up[i] & ~lim) || (dn[i] & ~lim)) return fail(SQMC_ERR_BAD_ARG, "determinant has bits beyond norb");
+  DevScratch s(c->st);
+  u64 *buf = (u64 *)s.take<char>((size_t)n * (37 * 8 + 18 * 4));
+  if (!s.ok()) return hip_fail("sqmc_gpu_hubbardk_sym_images", s.err());
   // 8-byte items first: up, dn, rep_up, rep_dn [n each], norm [n], images_up, images_dn [16 n each]; then the 4-byte ones: phases [16 n], phase_w_rep, num_distinct [n each]
   u64 *du = buf, *dd = buf + n, *dru = buf + 2 * n, *drd = buf + 3 * n; double *dnm = (double *)(buf + 4 * n);
   u64 *diu = buf + 5 * n, *did = buf + 21 * n; int *dph = (int *)(buf + 37 * n), *dpw = dph + 16 * n, *dnd = dpw + n;
@@ -585,20 +599,6 @@ static int hk_sym_images_run(sqmc_gpu_ctx *c, int64_t n, const uint64_t *up, con
   HIPCHK(hipMemcpy(phase_w_rep, dpw, n * 4, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(num_distinct, dnd, n * 4, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(norm, dnm, n * 8, hipMemcpyDeviceToHost));
   return SQMC_OK;
-}
-int sqmc_gpu_hubbardk_sym_images(sqmc_gpu_ctx *c, int64_t n, const uint64_t *up, const uint64_t *dn, uint64_t *images_up, uint64_t *images_dn, int32_t *phases,
-                                 uint64_t *rep_up, uint64_t *rep_dn, int32_t *phase_w_rep, double *norm, int32_t *num_distinct) {
-  if (!c) return fail(SQMC_ERR_BAD_ARG, "null ctx");
-  if (c->htab.sys_type != 3 || !c->htab.hk_sym) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_hubbardk_sym_images: not a hubbardk context with space_sym set");
-  if (n <= 0) return SQMC_OK;
-  if (!up || !dn || !images_up || !images_dn || !phases || !rep_up || !rep_dn || !phase_w_rep || !norm || !num_distinct) return fail(SQMC_ERR_BAD_ARG, "null argument");
-  const u64 lim = c->htab.orb_mask;
-  for (long long i = 0; i < n; i++) if ((up[i] & ~lim) || (dn[i] & ~lim)) return fail(SQMC_ERR_BAD_ARG, "determinant has bits beyond norb");
-  u64 *buf = nullptr;
-  HIPCHK(hipMalloc(&buf, (size_t)n * (37 * 8 + 18 * 4)));
-  const int rc = hk_sym_images_run(c, n, up, dn, images_up, images_dn, phases, rep_up, rep_dn, phase_w_rep, norm, num_distinct, buf);
-  hipFree(buf);
-  return rc;
 }
 
 static void comm_release(sqmc_gpu_ctx *c);
