@@ -466,6 +466,20 @@ int sqmc_gpu_davidson(sqmc_spmv_plan *plan, const double *diag, int32_t n_states
  * nonzeros come back.  Use the plan with sqmc_gpu_spmv_apply / _free. */
 int sqmc_gpu_build_spmv_plan(sqmc_gpu_ctx *ctx, int64_t n, const uint64_t *up, const uint64_t *dn, sqmc_spmv_plan **plan, double *diag,
                              int64_t *out_nnz);
+/* The principal submatrix of a resident plan as a plan of its own: dst(i, j) = src(sel[i], sel[j]).  sel[m]: row numbers of src,
+ * 1-based like `indices`, strictly ascending.  The kept entries of a row stay in the source order, and sel ascends, so dst is entry
+ * for entry the plan that sqmc_gpu_build_spmv_plan / sqmc_gpu_spmv_prepare build from the subset itself: its products and its
+ * sqmc_gpu_davidson run return the same bits.  dst owns its buffers (sqmc_gpu_spmv_apply, sqmc_gpu_davidson, sqmc_gpu_spmv_free); src
+ * is not modified and stays usable.  *out_nnz_full: the entries of dst's full CSR, (that number + m) / 2 of them in the stored triangle.
+ * The preconditioner of dst is diag[sel] of src's.
+ * SQMC_ERR_BAD_ARG: a null pointer, m < 1, m > n of src, sel out of range or not strictly ascending.  SQMC_ERR_UNSUPPORTED: the
+ * measurement-only layout is on (SQMC_SPMV_UPPER_ATOMIC), whose stored triangle is not extracted.  A call that fails has written
+ * neither *dst nor *out_nnz_full and holds no device memory. */
+int sqmc_gpu_spmv_plan_submatrix(const sqmc_spmv_plan *src, int64_t m, const int64_t *sel, sqmc_spmv_plan **dst, int64_t *out_nnz_full);
+/* shell_sort_real_rank1_int_rank1 without consider_sign (generic_sort.f90:685-735) on the host: a[n] by magnitude, greatest first,
+ * iorder[n] carried along; not stable, so for equal magnitudes only this gives the reference's order.  Afterwards a changes sign as a
+ * whole if a[0] < 0.  Touches no device. */
+int sqmc_shell_sort_magnitude(int64_t n, double *a, int32_t *iorder);
 int sqmc_gpu_spmv_sym_upper(int64_t n, const int64_t *row_counts, const int64_t *indices,
                             const double *values, const double *x, double *y);
 

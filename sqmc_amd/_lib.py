@@ -27,7 +27,7 @@ EXPORTS = [
     "sqmc_gpu_download_walkers", "sqmc_gpu_step", "sqmc_gpu_run", "sqmc_gpu_annihilate", "sqmc_gpu_det_owner", "sqmc_gpu_set_owner_hash", "sqmc_gpu_shard_config",
     "sqmc_gpu_shard_begin", "sqmc_gpu_shard_pack", "sqmc_gpu_shard_finish", "sqmc_gpu_shard_finish_psit", "sqmc_gpu_comm_unique_id", "sqmc_gpu_comm_init", "sqmc_gpu_comm_size",
     "sqmc_gpu_shard_step", "sqmc_gpu_shard_run", "sqmc_gpu_shard_time_split", "sqmc_gpu_get_rng", "sqmc_gpu_set_rng", "sqmc_gpu_tail_stats", "sqmc_gpu_last_tail", "sqmc_gpu_slowest_steps", "sqmc_gpu_set_chained_runs", "sqmc_gpu_spmv_prepare", "sqmc_gpu_davidson",
-    "sqmc_gpu_spmv_apply", "sqmc_gpu_spmv_free", "sqmc_gpu_build_spmv_plan", "sqmc_gpu_spmv_sym_upper", "sqmc_gpu_hamiltonian_batch",
+    "sqmc_gpu_spmv_apply", "sqmc_gpu_spmv_free", "sqmc_gpu_spmv_plan_submatrix", "sqmc_gpu_build_spmv_plan", "sqmc_gpu_spmv_sym_upper", "sqmc_gpu_hamiltonian_batch",
     "sqmc_gpu_propose_batch", "sqmc_gpu_hamiltonian_chem_batch", "sqmc_gpu_build_sparse_ham", "sqmc_gpu_hci_connections", "sqmc_gpu_hci_connections_slice", "sqmc_gpu_hci_pt2", "sqmc_gpu_hci_pt2_stochastic_prepare", "sqmc_gpu_hci_pt2_stochastic_sample", "sqmc_gpu_hci_pt2_stochastic_stats", "sqmc_gpu_hci_pt2_stochastic_free", "sqmc_gpu_hci_set_active_space", "sqmc_gpu_diag_update_batch", "sqmc_gpu_hci_set_diag_update", "sqmc_gpu_hci_connections_record", "sqmc_gpu_hci_1rdm", "sqmc_gpu_hci_1rdm_pt", "sqmc_gpu_rotate_integrals", "sqmc_gpu_hci_greens_function", "sqmc_gpu_free", "sqmc_gpu_set_timing", "sqmc_gpu_get_timing",
     "sqmc_gpu_set_spawn_diagnostics", "sqmc_gpu_reset_spawn_diagnostics", "sqmc_gpu_get_spawn_diagnostics", "sqmc_gpu_debug_bucket_boundaries",
 ]
@@ -769,6 +769,19 @@ class SpmvPlan:
         self.h = h
         return self, diag, nnz.value
 
+    def submatrix(self, sel):
+        """sqmc_gpu_spmv_plan_submatrix: the plan of the principal submatrix on the rows sel (0-based, strictly ascending), extracted on the
+        device from this plan, which stays as it is.  Entry for entry the plan built from the subset itself; its preconditioner is
+        diag[sel].  nnz_full of the result: the entries of its full CSR."""
+        s = np.ascontiguousarray(sel, np.int64) + 1
+        new = type(self).__new__(type(self))
+        new.L, new.n, new.h = self.L, len(s), None
+        h = C.c_void_p(); nnz = C.c_int64()
+        self.L.sqmc_gpu_spmv_plan_submatrix.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        _chk(self.L.sqmc_gpu_spmv_plan_submatrix(self.h, len(s), _p(s) if len(s) else None, C.byref(h), C.byref(nnz)))
+        new.h, new.nnz_full = h, nnz.value
+        return new
+
     def apply(self, x):
         x = _f64(x); y = np.zeros(self.n)
         _chk(self.L.sqmc_gpu_spmv_apply(self.h, _p(x), _p(y), 0))
@@ -787,6 +800,20 @@ class SpmvPlan:
         if self.h:
             self.L.sqmc_gpu_spmv_free(self.h)
             self.h = None
+
+
+def shell_sort_magnitude(a):
+    """sqmc_shell_sort_magnitude: the reference's shell sort by magnitude, greatest first (shell_sort_real_rank1_int_rank1,
+    generic_sort.f90:685-735; not stable).  Returns (sorted copy of a, its sign changed as a whole if the first element is negative;
+    iorder, the 0-based positions in a that the sorted elements came from).  Runs on the host."""
+    L = load_library()
+    s = np.array(a, np.float64).ravel()
+    if len(s) >= 2 ** 31:
+        raise ValueError("more elements than iorder's 32-bit integers number")
+    o = np.arange(len(s), dtype=np.int32)
+    L.sqmc_shell_sort_magnitude.argtypes = [C.c_int64, C.c_void_p, C.c_void_p]
+    _chk(L.sqmc_shell_sort_magnitude(len(s), _p(s), _p(o)))
+    return s, o.astype(np.int64)
 
 
 class Pt2StochasticPlan:

@@ -831,6 +831,66 @@ int sqmc_gpu_spmv_free(sqmc_spmv_plan *p) {
   q->mem.clear(); hipStreamDestroy(q->st); delete q;
   return SQMC_OK;
 }
+// The principal submatrix dst(i, j) = src(sel[i], sel[j]) of a resident plan as a plan of its own (submatrix_kernels.h): mark, count,
+// scan, fill on the source plan's stream.  Everything lives in `s` until the call has succeeded; only then does the new plan take its
+// five arrays, so an early return frees what was taken and has written nothing.
+static double g_submatrix_ms[2];      // SQMC_SUBMATRIX_TIME=1 (tools/extrap_time.py): the last call's mark + count + scan, and its fill, by HIP events
+int sqmc_gpu_spmv_plan_submatrix(const sqmc_spmv_plan *src, int64_t m, const int64_t *sel, sqmc_spmv_plan **dst, int64_t *out_nnz_full) {
+  const char *who = "sqmc_gpu_spmv_plan_submatrix";
+  static const bool timed = getenv("SQMC_SUBMATRIX_TIME") != nullptr;
+  if (!src || !sel || !dst || !out_nnz_full) return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_spmv_plan_submatrix: null argument");
+  if (m < 1 || m > src->n) return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_spmv_plan_submatrix: m must lie in [1, n of the source plan]");
+  if (src->u_ptr || getenv("SQMC_SPMV_UPPER_ATOMIC"))
+    return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_spmv_plan_submatrix: the stored triangle of the SQMC_SPMV_UPPER_ATOMIC layout is not extracted");
+  const long long n = src->n;
+  hipStream_t st = src->st;
+  DevScratch s(st);
+  const long long tiles = (m + SCAN_TILE - 1) / SCAN_TILE + 1;
+  long long *dsel = s.take<long long>(m); int *inv = s.take<int>(n);
+  u64 *cnt = s.take<u64>(m), *off = s.take<u64>(m), *dtot = s.take<u64>(2), *dts = s.take<u64>(tiles + 1);      // dtot: the kept entries, the flag of a refused sel
+  if (!s.ok()) return hip_fail(who, s.err());
+  ScanWork sw = scan_work(dts, tiles);
+  const unsigned wave_blocks = (unsigned)((m + SPMV_ROWS_PER_BLOCK - 1) / SPMV_ROWS_PER_BLOCK);
+  HIPCHK(hipMemcpyAsync(dsel, sel, m * 8, hipMemcpyHostToDevice, st));
+  EventMarks ev(timed, 2);
+  g_submatrix_ms[0] = g_submatrix_ms[1] = 0.0;
+  HIPCHK(ev.mark(st));
+  HIPCHK(hipMemsetAsync(inv, 0xff, n * 4, st)); HIPCHK(hipMemsetAsync(dtot, 0, 16, st));
+  hipLaunchKernelGGL(k_sub_mark, dim3(nblk(m)), dim3(TPB), 0, st, (const long long *)dsel, (long long)m, n, inv, dtot + 1);
+  hipLaunchKernelGGL(k_sub_count, dim3(wave_blocks), dim3(64 * SPMV_ROWS_PER_BLOCK), 0, st, (const int *)src->d_ptr, (const int *)src->d_col, (const long long *)dsel,
+                     (const int *)inv, (const u64 *)(dtot + 1), cnt, (long long)m);
+  device_excl_scan_u64(cnt, off, m, dtot, sw, st);
+  u64 tot[2] = {0, 0};
+  HIPCHK(hipGetLastError()); HIPCHK(ev.mark(st));
+  HIPCHK(hipMemcpyAsync(tot, dtot, 16, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st));
+  ev.add(&g_submatrix_ms[0]);
+  if (tot[1]) return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_spmv_plan_submatrix: sel must be strictly ascending row numbers in [1, n] (1-based)");
+  const long long nnz = (long long)tot[0];
+  int *d_ptr = s.take<int>(m + 1), *d_col = s.take<int>(nnz + 1); double *d_val = s.take<double>(nnz + 1), *d_x = s.take<double>(m), *d_y = s.take<double>(m);
+  if (!s.ok()) return hip_fail(who, s.err());
+  HIPCHK(ev.mark(st));
+  hipLaunchKernelGGL(k_sub_fill, dim3(wave_blocks), dim3(64 * SPMV_ROWS_PER_BLOCK), 0, st, (const int *)src->d_ptr, (const int *)src->d_col, (const double *)src->d_val,
+                     (const long long *)dsel, (const int *)inv, (const u64 *)off, d_ptr, d_col, d_val, (long long)m, nnz);
+  HIPCHK(hipGetLastError()); HIPCHK(ev.mark(st)); HIPCHK(hipStreamSynchronize(st));
+  ev.add(&g_submatrix_ms[1]);
+  SpmvPlanOwned *p = new SpmvPlanOwned(); p->n = m; p->nnz_full = nnz;
+  if (hipError_t e = hipStreamCreate(&p->st)) { delete p; return hip_fail(who, e); }
+  p->mem.stream = p->st;
+  p->d_ptr = d_ptr; p->d_col = d_col; p->d_val = d_val; p->d_x = d_x; p->d_y = d_y;
+  s.keep(d_ptr, p->mem); s.keep(d_col, p->mem); s.keep(d_val, p->mem); s.keep(d_x, p->mem); s.keep(d_y, p->mem);
+  *out_nnz_full = (int64_t)nnz; *dst = p;
+  return SQMC_OK;
+}
+int sqmc_gpu_debug_submatrix_ms(double *count_ms, double *fill_ms) {      // not part of the ABI
+  if (count_ms) *count_ms = g_submatrix_ms[0]; if (fill_ms) *fill_ms = g_submatrix_ms[1];
+  return SQMC_OK;
+}
+// shell_sort_real_rank1_int_rank1 (host_sort.h): no device is touched
+int sqmc_shell_sort_magnitude(int64_t n, double *a, int32_t *iorder) {
+  if (n < 0 || (n > 0 && (!a || !iorder))) return fail(SQMC_ERR_BAD_ARG, "sqmc_shell_sort_magnitude: bad argument");
+  host_shell_sort_magnitude(n, a, iorder);
+  return SQMC_OK;
+}
 int sqmc_gpu_spmv_sym_upper(int64_t n, const int64_t *rc, const int64_t *idx, const double *val, const double *x, double *y) {
   sqmc_spmv_plan *p = nullptr;
   int r = sqmc_gpu_spmv_prepare(n, rc, idx, val, &p);

@@ -38,6 +38,7 @@
 #include "bucket_partition.h"
 #include "hii_group.h"
 #include "dev_scratch.h"
+#include "host_sort.h"
 
 #define TPB 256
 #define SPAWN_WIN 1024
@@ -281,6 +282,7 @@ static inline u64 *spawn_diag(const sqmc_gpu_ctx *c) { return c->sdiag_on ? c->d
 #include "hci_kernels.h"
 #include "hbuild_kernels.h"
 #include "spmv_kernels.h"
+#include "submatrix_kernels.h"
 #include "rdm_kernels.h"
 #include "rotate_kernels.h"
 #include "greens_kernels.h"

@@ -25,6 +25,7 @@ module sqmc_gpu_mod
   public :: sqmc_gpu_set_spawn_diagnostics, sqmc_gpu_reset_spawn_diagnostics, sqmc_gpu_get_spawn_diagnostics
   public :: sqmc_gpu_set_hubbardk_space_sym, sqmc_gpu_hubbardk_sym_images, sqmc_gpu_debug_bucket_boundaries
   public :: sqmc_gpu_hci_1rdm, sqmc_gpu_hci_1rdm_pt, sqmc_gpu_rotate_integrals, sqmc_gpu_hci_greens_function
+  public :: sqmc_gpu_spmv_plan_submatrix, sqmc_shell_sort_magnitude
   public :: sqmc_gpu_check
 
   integer(c_int), parameter, public :: SQMC_RNG_REPLAY = 0, SQMC_RNG_COUNTER = 1
@@ -394,6 +395,13 @@ module sqmc_gpu_mod
     end function
     integer(c_int) function sqmc_gpu_spmv_free(plan) bind(C, name='sqmc_gpu_spmv_free')
       import; type(c_ptr), value :: plan
+    end function
+    integer(c_int) function sqmc_gpu_spmv_plan_submatrix(src, m, sel, dst, out_nnz_full) bind(C, name='sqmc_gpu_spmv_plan_submatrix')
+      import; type(c_ptr), value :: src; integer(c_int64_t), value :: m; integer(c_int64_t), intent(in) :: sel(*)
+      type(c_ptr), intent(out) :: dst; integer(c_int64_t), intent(out) :: out_nnz_full
+    end function
+    integer(c_int) function sqmc_shell_sort_magnitude(n, a, iorder) bind(C, name='sqmc_shell_sort_magnitude')
+      import; integer(c_int64_t), value :: n; real(c_double), intent(inout) :: a(*); integer(c_int32_t), intent(inout) :: iorder(*)
     end function
     integer(c_int) function sqmc_gpu_spmv_sym_upper(n, row_counts, indices, values, x, y) bind(C, name='sqmc_gpu_spmv_sym_upper')
       import; integer(c_int64_t), value :: n; integer(c_int64_t), intent(in) :: row_counts(*), indices(*)

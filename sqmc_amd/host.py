@@ -1619,6 +1619,146 @@ def hci_pt2_determinant_basis(host, up, dn, coeffs, e_var, eps_pt, n_slices=1, d
         g.close()
 
 
+# ------------------------------------------------------------- energies for extrapolation from truncated wavefunctions
+def extrapolation_order(wts):
+    """The order in which energies_for_extrapolation truncates (hci.f90:1866-1880): the determinants by the magnitude of state 1's
+    coefficient, greatest first, through the reference's own shell sort (sqmc_shell_sort_magnitude: not stable, so ties fall as
+    there); state 1's column changes sign as a whole if its leading coefficient is negative, the other states' columns are permuted
+    and nothing else.  Returns (iorder, 0-based positions in the list; the permuted coefficients, n x n_states)."""
+    from ._lib import shell_sort_magnitude
+    wts = np.asarray(wts, float).reshape(len(wts), -1)
+    first, iorder = shell_sort_magnitude(wts[:, 0])
+    w = np.ascontiguousarray(wts[iorder, :])
+    w[:, 0] = first
+    return iorder, w
+
+
+def extrapolation_truncations(ndets, n_energy_batch):
+    """[(determinants kept, the ndets the reference prints)] of energies_for_extrapolation's loop (hci.f90:1892-1903, 1940):
+    batch_size = ndets / n_energy_batch in integers, i = 1 .. n_energy_batch + 1, the first min(batch_size i, ndets) kept and
+    batch_size i printed unclamped; where ndets divides evenly the last two are both the full space."""
+    if n_energy_batch < 1 or n_energy_batch > ndets:
+        raise ValueError("n_energy_batch =%d must lie between 1 and the number of determinants (%d): the reference would diagonalise empty spaces"
+                         % (n_energy_batch, ndets))
+    batch = ndets // n_energy_batch
+    return [(min(batch * i, ndets), batch * i) for i in range(1, n_energy_batch + 2)]
+
+
+def _fortran_e(x, width, dec):
+    """Fortran Ew.d: 0.ddE+ee"""
+    m, e = ("%.*e" % (dec - 1, abs(x))).split("e")
+    e = int(e) + 1 if float(m) != 0.0 else 0
+    return ("%s0.%sE%+03d" % ("-" if x < 0 else "", m.replace(".", ""), e)).rjust(width)
+
+
+def format_extrapolation_state(rec, eps_var, eps_pt):
+    """the lines of one state of one truncation, hci.f90:1995-2005 (t36: the number starts in column 36; the deterministic total
+    carries its state as i2, as there)"""
+    i, e, big, diff, sd = rec["state"], rec["e_var"], rec["pt_big"], rec["pt_diff"], rec["pt_diff_std_dev"]
+    head = "eps_var, eps_pt, ndets, ndets_connected(total), Variational, PT_actv, PT_full, Total Energies(%d)=" % i
+    nums = "%s%s%9d%11d" % (_fortran_e(eps_var, 9, 2), _fortran_e(eps_pt, 9, 2), rec["ndets_printed"], rec["n_connected"])
+    out = ["", "State%4d:" % i, ("Variational energy(%d)=" % i).ljust(35) + "%15.9f" % e]
+    if sd == 0.0:
+        out += [("2nd-order PT energy lowering(%d)=" % i).ljust(35) + "%15.9f" % big, ("Total energy(%2d)=" % i).ljust(35) + "%15.9f" % (e + big),
+                head + nums + "%16.9f%15.9f%15.9f%16.9f" % (e, big, big, e + big)]
+    else:
+        de = big + diff
+        out += [("2nd-order PT energy lowering(%d)=" % i).ljust(35) + "%15.9f +-%12.9f (%13.9f%13.9f)" % (de, sd, big, diff),
+                ("Total energy(%d)=" % i).ljust(35) + "%15.9f +-%12.9f" % (e + de, sd),
+                head + nums + "%16.9f%15.9f%15.9f%16.9f +-%12.9f" % (e, de, de, e + de, sd)]
+    return out
+
+
+def format_extrapolation_tail(rec):
+    """write(6,*) 'ndets: ', ndets_global_old, 'energy: ', energy(1) (hci.f90:2007), list-directed there: in the fixed forms i12 and
+    es24.16e3 here, as the other list-directed lines of the deck runner"""
+    return " ndets: %12d energy: %s" % (rec["ndets_pt"], _es24(rec["e_var"]))
+
+
+EXTRAP_SORTING = "Sorting global dets list to create truncated wavefunctions"
+EXTRAP_TO_DETS = ("Converting to determinant basis", "From now on, no more time-reversal symmetry")
+
+
+def hci_extrapolation_energies(host, g, up, dn, wts, n_energy_batch, eps_var, eps_pt, eps_pt_big=0.0, n_mc=0, target_error=0.0, seed=None,
+                               reuse_matrix=True, pt_diag_update=0, log=None, pt_on_device=False, davidson_tol=1e-10, keep_vectors=False):
+    """energies_for_extrapolation (hci.f90:1824-2017) on one rank: variational and PT energies of the wavefunction truncated to its
+    leading determinants, for the plot of E_total against the PT correction.  The list is put in the order of extrapolation_order;
+    for each size of extrapolation_truncations the leading determinants, in (up, dn) order, are re-diagonalised by the device
+    Davidson for n_states states from the truncated coefficients as they are (not renormalised, :1932-1939), and every state gets
+    its PT stage as run_hci gives it: in the determinant basis (time_symmetrized_to_dets when host.time_sym), deterministic at
+    eps_pt, or semistochastic when n_mc > 0 and eps_pt_big > eps_pt, the random stream restarted from `seed` for every call.
+    reuse_matrix: the Hamiltonian of the whole list is built once (SpmvPlan.from_dets) and each truncation's plan is its principal
+    submatrix, extracted on the device (SpmvPlan.submatrix, preconditioner diag[sel]); False: SpmvPlan.from_dets for every
+    truncation, the yardstick -- both give the same plan entry for entry, hence the same bits throughout.
+    g: the context of the variational stage (host's time_sym).  log: called with every line the reference prints, as it arises.
+    Returns one dict per (truncation, state), truncations outermost: truncation and state (1-based), ndets (kept), ndets_printed
+    (batch_size i, unclamped), ndets_pt (determinants of the PT stage), e_var, pt_big, pt_diff, pt_diff_std_dev (0.0 when
+    deterministic), n_connected, n_matvec (products of the truncation's Davidson run); with keep_vectors also up, dn (the truncation in
+    (up, dn) order) and coeffs (the state's eigenvector on it)."""
+    import copy
+    up, dn = np.ascontiguousarray(up, np.uint64), np.ascontiguousarray(dn, np.uint64)
+    wts = np.asarray(wts, float).reshape(len(up), -1)
+    ndets, n_states = wts.shape
+    sizes = extrapolation_truncations(ndets, int(n_energy_batch))
+    say = log if log else (lambda line: None)
+    say(""); say(EXTRAP_SORTING)
+    iorder, w = extrapolation_order(wts)
+    up_m, dn_m = up[iorder], dn[iorder]
+    stochastic = n_mc > 0 and eps_pt_big > eps_pt
+    plain = host
+    if host.time_sym:
+        plain = copy.copy(host); plain.time_sym = False
+    full = rank = diag_full = None
+    gp = plain.gpu()
+    records = []
+    try:
+        gp.set_hb_tables(*plain.hb_tables(gp))
+        if reuse_matrix:
+            order_full = sort_dets(up, dn)
+            full, diag_full, _ = SpmvPlan.from_dets(g, up[order_full], dn[order_full])
+            rank = np.empty(ndets, np.int64); rank[order_full] = np.arange(ndets)          # place of a determinant in the (up, dn) order of the whole list
+        for it, (nt, printed) in enumerate(sizes, 1):
+            o = sort_dets(up_m[:nt], dn_m[:nt])
+            tu, td, v0 = up_m[:nt][o], dn_m[:nt][o], w[:nt][o]
+            if reuse_matrix:
+                sel = rank[iorder[:nt][o]]                  # ascending: both orders are (up, dn)
+                plan, diag = full.submatrix(sel), diag_full[sel]
+            else:
+                plan, diag, _ = SpmvPlan.from_dets(g, tu, td)
+            try:
+                ev, X, n_mv = plan.davidson(diag, k=n_states, v0=v0, tol=davidson_tol)
+            finally:
+                plan.close()
+            if host.time_sym:
+                say(""); say(EXTRAP_TO_DETS[0])
+            pt_in = [time_symmetrized_to_dets(tu, td, X[:, q], host.z) if host.time_sym else (tu, td, X[:, q]) for q in range(n_states)]
+            if host.time_sym:
+                say(EXTRAP_TO_DETS[1]); say("")
+            for q in range(n_states):
+                du, dd, dc = pt_in[q]
+                if stochastic:
+                    kw = {} if seed is None else dict(seed=seed)
+                    r = hci_pt2_stochastic(plain, gp, du, dd, dc, float(ev[q]), eps_pt, eps_pt_big, n_mc, target_error, on_device=pt_on_device,
+                                           diag_update=pt_diag_update, log=(lambda m: (say(""), say(m))) if log else None, **kw)
+                    big, diff, sd, nconn = r["pt_big"], r["pt_diff"], r["pt_diff_std_dev"], r["n_connected_big"]
+                else:
+                    big, nconn = hci_pt2(plain, gp, du, dd, dc, float(ev[q]), eps_pt, diag_update=pt_diag_update)
+                    diff = sd = 0.0
+                rec = dict(truncation=it, state=q + 1, ndets=nt, ndets_printed=printed, ndets_pt=len(du), e_var=float(ev[q]), pt_big=float(big),
+                           pt_diff=float(diff), pt_diff_std_dev=float(sd), n_connected=int(nconn), n_matvec=int(n_mv))
+                if keep_vectors:
+                    rec.update(up=tu, dn=td, coeffs=X[:, q].copy())
+                records.append(rec)
+                for line in format_extrapolation_state(rec, eps_var, eps_pt):
+                    say(line)
+            say(format_extrapolation_tail(records[-n_states]))
+    finally:
+        if full is not None:
+            full.close()
+        gp.close()
+    return records
+
+
 # ------------------------------------------------------------------------- 1-RDM and natural orbitals
 def hci_one_rdm(host, up, dn, wts, energies=None, use_pt=False, eps_pt_big=None, n_slices=1):
     """The 1-RDM of an HCI wavefunction as perform_hci forms it (hci.f90:683-736), an (norb, norb) array indexed [p, r] as

@@ -14,7 +14,11 @@ integrals into the natural orbitals (sqmc_gpu_rotate_integrals) and the run writ
 run, where the reference stops too (:745).  `&greens_function get_greens_function=t n_w=... w_min=... w_max=... /` (hci.f90:748-759): the
 zeroth-order Green's function of state 1 on the device (sqmc_gpu_hci_greens_function), written as G0_N+1, G0_N-1 and rho into the
 working directory, after which the run goes on to the PT stage as the reference does; --greens-signed selects the matrix elements
-with their fermionic sign (the reference applies none).  Host-side plumbing: every piece that scales with the number of determinants runs in libsqmc_gpu."""
+with their fermionic sign (the reference applies none).  `&selected_ci n_energy_batch=K /` (hci.f90:638-643, 1824-2017): after the
+variational stage the wavefunction is truncated to its leading determinants by magnitude in K + 1 steps, each re-diagonalised and
+given its PT stage, one `eps_var, eps_pt, ndets, ...` line per truncation for the extrapolation of E_total against the PT correction,
+and the run stops there as the reference does; each truncation's Hamiltonian is the principal submatrix of the whole list's, extracted
+on the device (sqmc_gpu_spmv_plan_submatrix), or with --extrap-rebuild built from its determinants.  Host-side plumbing: every piece that scales with the number of determinants runs in libsqmc_gpu."""
 import argparse
 import os
 import re
@@ -91,6 +95,7 @@ def parse_hci_deck(text):
     deck["eps_var_sched"] = [float(v.lower().replace("d", "e")) for v in sci.get("eps_var_sched", [])]
     deck["n_mc"] = int(float(sci.get("n_mc", ["0"])[0]))
     deck["eps_pt_big"] = float(sci["eps_pt_big"][0].lower().replace("d", "e")) if "eps_pt_big" in sci else 0.0
+    deck["n_energy_batch"] = int(float(sci["n_energy_batch"][0])) if "n_energy_batch" in sci else 0      # hci.f90:638
     nat = nl.get("natorb", {})               # hci.f90:683-745
     deck["get_natorbs"] = _logical(nat["get_natorbs"][0]) if "get_natorbs" in nat else False
     deck["use_pt"] = _logical(nat["use_pt"][0]) if "use_pt" in nat else False
@@ -126,6 +131,8 @@ def run_hci_heg(deck, out=sys.stdout, pt_on_device=False, pt_diag_update=0):
         raise SystemExit("Natural orbitals only implemented for chem so far")          # hci.f90:684
     if deck.get("get_greens_function"):
         raise SystemExit("sqmc_amd: &greens_function is built for chem only (the reference calls hamiltonian_chem there, hci.f90:3936)")
+    if deck.get("n_energy_batch", 0) > 0:
+        raise SystemExit("sqmc_amd: &selected_ci n_energy_batch (energies for extrapolation) is built for chem decks only")
     import torch            # noqa: F401
     import sqmc_amd
     from . import host as H
@@ -255,14 +262,31 @@ def run_greens(deck, h, up, dn, wts, energy, p, signed=False):
     return w, gp, gm
 
 
-def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False, pt_diag_update=0, one_rdm_path=None, natorb_fcidump=None, greens_signed=False):
+def run_extrapolation(deck, h, g, up, dn, wts, p, pt_on_device=False, pt_diag_update=0, rebuild=False):
+    """&selected_ci n_energy_batch = K (hci.f90:638-643, energies_for_extrapolation :1824-2017): the reference's lines for the K + 1
+    truncations of the variational wavefunction, after which the run stops as there (:2016).  rebuild: every truncation's matrix from
+    its determinants instead of the principal submatrix of the whole list's (host.hci_extrapolation_energies reuse_matrix)."""
+    from . import host as H
+    try:
+        H.extrapolation_truncations(len(up), deck["n_energy_batch"])
+    except ValueError as e:
+        raise SystemExit("sqmc_amd: " + str(e))
+    records = H.hci_extrapolation_energies(h, g, up, dn, wts[:, :deck["n_states"]], deck["n_energy_batch"], deck["eps_var"], deck["eps_pt"], eps_pt_big=deck["eps_pt_big"],
+                                           n_mc=deck["n_mc"], target_error=deck["target_error"], seed=deck["irand_seed"][0], reuse_matrix=not rebuild,
+                                           pt_diag_update=pt_diag_update, log=p, pt_on_device=pt_on_device)
+    return dict(ndets=len(up), extrapolation=records)
+
+
+def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False, pt_diag_update=0, one_rdm_path=None, natorb_fcidump=None, greens_signed=False,
+            extrap_rebuild=False):
     """pt_on_device: the samples of the semistochastic PT are evaluated by the library (host.hci_pt2_stochastic on_device);
     pt_diag_update: 0 / 1 / 2, how the PT stage forms H_aa (host.hci_pt2); one_rdm_path: with &natorb get_natorbs = t, also save the
     1-RDM there as .npy; natorb_fcidump: with &natorb get_natorbs = t, rotate the integrals into the natural orbitals and write them
     to this new file (True: the reference's name, FCIDUMP_eps_var=<smallest eps_var>, in the working directory); the result then
     holds natorb_integrals (packed, the host's combine_2) and natorb_fcidump (the path).  None: the run ends on NATORB_STOP.
     greens_signed: with &greens_function get_greens_function = t, fermi_sign = 1 instead of the reference's sums; the result then holds
-    greens = (w, G_np1, G_nm1)."""
+    greens = (w, G_np1, G_nm1).  extrap_rebuild: with &selected_ci n_energy_batch > 0, see run_extrapolation; the result then holds
+    extrapolation, the records of host.hci_extrapolation_energies."""
     if deck["hamiltonian_type"] == "heg":
         return run_hci_heg(deck, out, pt_on_device, pt_diag_update)
     want_greens = bool(deck.get("get_greens_function")) and not deck.get("get_natorbs")      # get_natorbs stops first (hci.f90:745)
@@ -299,6 +323,11 @@ def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False, pt_diag
         if deck["dump_wf_var"]:
             p("\nWriting variational wavefn to " + wf)
             H.write_wf_var(wf, up, dn, wts, energy)
+    if deck.get("n_energy_batch", 0) > 0:            # hci.f90:638-643, in front of natural orbitals, Green's function and the PT stage
+        try:
+            return run_extrapolation(deck, h, g, up, dn, wts, p, pt_on_device, pt_diag_update, extrap_rebuild)
+        finally:
+            g.close()
     g.close()
     t1 = time.perf_counter()
     if deck.get("get_natorbs"):
@@ -370,6 +399,8 @@ def main(argv=None):
                     "into the natural orbitals on the device and write them to PATH, a new file (default: FCIDUMP_eps_var=<smallest eps_var>, the reference's name)")
     ap.add_argument("--greens-signed", action="store_true", help="HCI decks with &greens_function get_greens_function = t: the matrix elements with their "
                     "fermionic sign (fermi_sign = 1) instead of the reference's sums, which apply none")
+    ap.add_argument("--extrap-rebuild", action="store_true", help="HCI decks with &selected_ci n_energy_batch > 0: build every truncation's Hamiltonian from its "
+                    "determinants instead of extracting it from the whole list's on the device (the yardstick; the numbers are the same)")
     a = ap.parse_args(argv)
     text = open(a.input).read() if a.input else sys.stdin.read()
     lines = [l for l in text.splitlines() if l.strip() and not l.lstrip().startswith("!")]
@@ -380,7 +411,7 @@ def main(argv=None):
                         dtm_elems_in=a.dtm_elems_in, dtm_elems_out=a.dtm_elems_out, spawn_histograms=a.spawn_histograms)
     deck = parse_hci_deck(text)
     return run_hci(deck, a.fcidump, pt_on_device=a.pt_on_device, pt_diag_update=a.pt_diag_update, one_rdm_path=a.one_rdm, natorb_fcidump=a.rotate_integrals,
-                   greens_signed=a.greens_signed)
+                   greens_signed=a.greens_signed, extrap_rebuild=a.extrap_rebuild)
 
 
 if __name__ == "__main__":
