@@ -654,6 +654,24 @@ int sqmc_gpu_hci_1rdm(sqmc_gpu_ctx *ctx, int64_t n_var, const uint64_t *var_up, 
  * state of the context and apply as they stand.  Same bits run to run; a refused call leaves rdm and n_connections untouched. */
 int sqmc_gpu_hci_1rdm_pt(sqmc_gpu_ctx *ctx, int64_t n_var, const uint64_t *var_up, const uint64_t *var_dn, const double *coeffs, double e_var,
                          double eps_pt_big, int32_t n_slices, double *rdm, int64_t *n_connections);
+/* no counterpart in the reference (which stops at get_1rdm): the two-body reduced density matrix of a variational wavefunction
+ * sum c_i |up_i, dn_i> in three spin blocks, each a dense norb^4 array with flat index p + norb (q + norb (r + norb s)), 0-based:
+ *   rdm_aa = <a+_{p up} a+_{q up} a_{s up} a_{r up}>,  rdm_bb the same with dn,  rdm_ab = <a+_{p up} a+_{q dn} a_{s dn} a_{r up}>
+ * with a determinant = all its up operators in front of all its dn operators (the ordering behind the library's Hamiltonian).
+ * Nothing is renormalised: the traces sum_pq G[p,q,p,q] are 2 C(nup,2) sum c^2, 2 C(ndn,2) sum c^2 and nup ndn sum c^2.
+ * blocks: 1 = aa, 2 = bb, 4 = ab, or-ed; the pointer of a block that is not requested is not read and may be NULL.
+ * Evaluated through the (N-2)-electron intermediates K: every determinant emits one signed coefficient per pair of its electrons,
+ * the records are sorted by (orbital pair, rank of K) and an entry is the product of two sorted columns.  No floating-point atomics
+ * and a fixed order of additions: an entry has the same bits run to run, for every order of the caller's list and whichever other
+ * blocks the call asked for; G[p,q,r,s] == G[r,s,p,q], G_aa[p,q,r,s] == -G_aa[q,p,r,s] == -G_aa[p,q,s,r] exactly, and every entry
+ * no pair of determinants reaches is 0.0.  A block without a pair of electrons of its kind is all zeros.
+ * Every system type; reads determinants and coefficients only.  SQMC_ERR_BAD_ARG: blocks outside 1..7, a requested block with a NULL
+ * pointer, n_var < 1, a repeated determinant, a determinant with other electron numbers than the context's or an orbital beyond
+ * norb.  SQMC_ERR_UNSUPPORTED: contexts with time_sym = 1 and hubbardk with space_sym (pass the determinant-basis expansion, as to
+ * sqmc_gpu_hci_1rdm), a block whose intermediates need more than 64 key bits, a block of 2^32 - 1 records (n_var times the pairs of
+ * electrons) or more.  A refused or failed call leaves all three arrays untouched. */
+int sqmc_gpu_hci_2rdm(sqmc_gpu_ctx *ctx, int64_t n_var, const uint64_t *var_up, const uint64_t *var_dn, const double *coeffs,
+                      int32_t blocks, double *rdm_aa, double *rdm_bb, double *rdm_ab);
 /* replaces: the integral rotation of generate_natorb_integrals (hci.f90:3683-3791): the context's one- and two-body integrals in
  * the orbitals  new_p = sum_k rot[k norb + p] old_k  (k, p 0-based, in the context's orbital order; row-major: the C-order memory of
  * the eigenvector matrix the 1-RDM is diagonalised into, the transpose of a column-major host's rdm(k, p)):

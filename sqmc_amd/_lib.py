@@ -28,7 +28,7 @@ EXPORTS = [
     "sqmc_gpu_shard_begin", "sqmc_gpu_shard_pack", "sqmc_gpu_shard_finish", "sqmc_gpu_shard_finish_psit", "sqmc_gpu_comm_unique_id", "sqmc_gpu_comm_init", "sqmc_gpu_comm_size",
     "sqmc_gpu_shard_step", "sqmc_gpu_shard_run", "sqmc_gpu_shard_time_split", "sqmc_gpu_get_rng", "sqmc_gpu_set_rng", "sqmc_gpu_tail_stats", "sqmc_gpu_last_tail", "sqmc_gpu_slowest_steps", "sqmc_gpu_set_chained_runs", "sqmc_gpu_spmv_prepare", "sqmc_gpu_davidson",
     "sqmc_gpu_spmv_apply", "sqmc_gpu_spmv_free", "sqmc_gpu_spmv_plan_submatrix", "sqmc_gpu_build_spmv_plan", "sqmc_gpu_spmv_sym_upper", "sqmc_gpu_hamiltonian_batch",
-    "sqmc_gpu_propose_batch", "sqmc_gpu_hamiltonian_chem_batch", "sqmc_gpu_build_sparse_ham", "sqmc_gpu_hci_connections", "sqmc_gpu_hci_connections_slice", "sqmc_gpu_hci_pt2", "sqmc_gpu_hci_pt2_stochastic_prepare", "sqmc_gpu_hci_pt2_stochastic_sample", "sqmc_gpu_hci_pt2_stochastic_stats", "sqmc_gpu_hci_pt2_stochastic_free", "sqmc_gpu_hci_set_active_space", "sqmc_gpu_diag_update_batch", "sqmc_gpu_hci_set_diag_update", "sqmc_gpu_hci_connections_record", "sqmc_gpu_hci_1rdm", "sqmc_gpu_hci_1rdm_pt", "sqmc_gpu_rotate_integrals", "sqmc_gpu_hci_greens_function", "sqmc_gpu_free", "sqmc_gpu_set_timing", "sqmc_gpu_get_timing",
+    "sqmc_gpu_propose_batch", "sqmc_gpu_hamiltonian_chem_batch", "sqmc_gpu_build_sparse_ham", "sqmc_gpu_hci_connections", "sqmc_gpu_hci_connections_slice", "sqmc_gpu_hci_pt2", "sqmc_gpu_hci_pt2_stochastic_prepare", "sqmc_gpu_hci_pt2_stochastic_sample", "sqmc_gpu_hci_pt2_stochastic_stats", "sqmc_gpu_hci_pt2_stochastic_free", "sqmc_gpu_hci_set_active_space", "sqmc_gpu_diag_update_batch", "sqmc_gpu_hci_set_diag_update", "sqmc_gpu_hci_connections_record", "sqmc_gpu_hci_1rdm", "sqmc_gpu_hci_1rdm_pt", "sqmc_gpu_hci_2rdm", "sqmc_gpu_rotate_integrals", "sqmc_gpu_hci_greens_function", "sqmc_gpu_free", "sqmc_gpu_set_timing", "sqmc_gpu_get_timing",
     "sqmc_gpu_set_spawn_diagnostics", "sqmc_gpu_reset_spawn_diagnostics", "sqmc_gpu_get_spawn_diagnostics", "sqmc_gpu_debug_bucket_boundaries",
 ]
 
@@ -45,14 +45,16 @@ class SqmcGpuError(RuntimeError):
 def build_library(force=False):
     """hipcc cross-compiles for gfx950 without a GPU present."""
     csrc = os.path.join(_HERE, "csrc")
-    # one translation unit: sqmc_gpu.hip includes every other file of csrc/ textually
-    src = [os.path.join(csrc, "sqmc_gpu.hip")] + sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".h", ".inc"))) \
+    # two translation units: sqmc_gpu.hip includes every .h / .inc of csrc/ textually but rdm2_kernels.h, which rdm2_device.hip compiles into
+    # a code object of its own
+    units = [os.path.join(csrc, "sqmc_gpu.hip"), os.path.join(csrc, "rdm2_device.hip")]
+    src = units + sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".h", ".inc"))) \
         + [os.path.join(_ROOT, "include", "sqmc_gpu.h")]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in src):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unused-value",
-           "-I" + os.path.join(_ROOT, "include")] + os.environ.get("SQMC_EXTRA_CFLAGS", "").split() + [src[0], "-o", LIB_PATH]
+           "-I" + os.path.join(_ROOT, "include")] + os.environ.get("SQMC_EXTRA_CFLAGS", "").split() + units + ["-o", LIB_PATH]
     subprocess.check_call(cmd)
     return LIB_PATH
 
@@ -702,6 +704,27 @@ def _gpuchem_one_rdm_pt(self, up, dn, coeffs, e_var, eps_pt_big, n_slices=1):
     return np.ascontiguousarray(out.reshape(self.norb, self.norb).T), nc.value
 
 
+_RDM2_BLOCKS = {"aa": 1, "bb": 2, "ab": 4}
+
+
+def _gpuchem_two_rdm(self, up, dn, coeffs, blocks="all"):
+    """sqmc_gpu_hci_2rdm: the spin blocks of the two-body density matrix of a determinant list in any order, a dict of (norb,) * 4
+    arrays in Fortran order keyed "aa", "bb", "ab": G_aa[p, q, r, s] = <a+_{p up} a+_{q up} a_{s up} a_{r up}>, G_bb the same with dn,
+    G_ab[p, q, r, s] = <a+_{p up} a+_{q dn} a_{s dn} a_{r up}> (0-based; nothing is renormalised).  blocks: "all", one of the keys, or a
+    sequence of them; only those are computed and returned"""
+    u, d, c = _u64(up), _u64(dn), _f64(coeffs)
+    if not (len(u) == len(d) == len(c)):
+        raise ValueError("up, dn and coeffs differ in length")
+    names = ("aa", "bb", "ab") if blocks == "all" else (blocks,) if isinstance(blocks, str) else tuple(blocks)
+    if not names or any(b not in _RDM2_BLOCKS for b in names):
+        raise ValueError("two_rdm: blocks must be 'all' or among 'aa', 'bb', 'ab'")
+    out = {b: np.zeros(self.norb ** 4) for b in ("aa", "bb", "ab") if b in names}
+    self.L.sqmc_gpu_hci_2rdm.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    _chk(self.L.sqmc_gpu_hci_2rdm(self.h, len(u), _p(u), _p(d), _p(c), sum(_RDM2_BLOCKS[b] for b in out),
+                                  *[_p(out[b]) if b in out else None for b in ("aa", "bb", "ab")]))
+    return {b: a.reshape((self.norb,) * 4, order="F") for b, a in out.items()}
+
+
 def _gpuchem_rotate_integrals(self, rot):
     """sqmc_gpu_rotate_integrals (the rotation of generate_natorb_integrals, hci.f90:3683-3791): the context's integrals in the orbitals
     new_p = sum_k rot[k, p] old_k, as a new packed array of n_integrals + 1 doubles addressed by the same combine_2.  rot: (norb, norb),
@@ -918,5 +941,6 @@ GpuChem.hci_set_diag_update = _gpuchem_hci_set_diag_update
 GpuChem.hci_connections_record = _gpuchem_hci_connections_record
 GpuChem.one_rdm = _gpuchem_one_rdm
 GpuChem.one_rdm_pt = _gpuchem_one_rdm_pt
+GpuChem.two_rdm = _gpuchem_two_rdm
 GpuChem.greens_function = _gpuchem_greens_function
 GpuChem.rotate_integrals = _gpuchem_rotate_integrals

@@ -39,6 +39,8 @@
 #include "hii_group.h"
 #include "dev_scratch.h"
 #include "host_sort.h"
+#include "rdm2_plan.h"
+#include "rdm2_launch.h"
 
 #define TPB 256
 #define SPAWN_WIN 1024
@@ -251,6 +253,8 @@ struct sqmc_gpu_ctx {
   // e_loc_num / den, the T^-1 exchange vector, and the caller's all-reduce of it (three-phase steps without a communicator)
   bool psit_shard; std::vector<u64> ps_ct_up, ps_ct_dn; double *d_ps_num, *d_ps_den, *d_ps_tx;
   sqmc_allreduce_fn psit_reduce; void *psit_reduce_user; double *psit_reduce_buf;
+  // behind everything a step reads, so that the layout of the walk's fields is the one it had
+  double rdm2_ms[3]; long long rdm2_records[3];      // HIP-event times and record counts of the last sqmc_gpu_hci_2rdm, per block aa, bb, ab (sqmc_gpu_debug_rdm2_ms)
 };
 // a head enqueued for a step that is not going to be the next thing that happens (chained runs): forget it
 static void abandon_head(sqmc_gpu_ctx *c);
@@ -1760,6 +1764,7 @@ int sqmc_gpu_debug_premerge(sqmc_gpu_ctx *c, int64_t cap, int64_t *n0, int64_t *
 #include "abi_shard.inc"
 #include "abi_doors.inc"
 #include "abi_rdm.inc"
+#include "abi_rdm2.inc"
 #include "abi_greens.inc"
 #include "abi_rotate.inc"
 #include "abi_spawn_diag.inc"

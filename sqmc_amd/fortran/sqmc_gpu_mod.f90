@@ -24,7 +24,7 @@ module sqmc_gpu_mod
   public :: sqmc_gpu_hci_pt2_stochastic_prepare, sqmc_gpu_hci_pt2_stochastic_sample, sqmc_gpu_hci_pt2_stochastic_stats, sqmc_gpu_hci_pt2_stochastic_free
   public :: sqmc_gpu_set_spawn_diagnostics, sqmc_gpu_reset_spawn_diagnostics, sqmc_gpu_get_spawn_diagnostics
   public :: sqmc_gpu_set_hubbardk_space_sym, sqmc_gpu_hubbardk_sym_images, sqmc_gpu_debug_bucket_boundaries
-  public :: sqmc_gpu_hci_1rdm, sqmc_gpu_hci_1rdm_pt, sqmc_gpu_rotate_integrals, sqmc_gpu_hci_greens_function
+  public :: sqmc_gpu_hci_1rdm, sqmc_gpu_hci_1rdm_pt, sqmc_gpu_hci_2rdm, sqmc_gpu_rotate_integrals, sqmc_gpu_hci_greens_function
   public :: sqmc_gpu_spmv_plan_submatrix, sqmc_shell_sort_magnitude
   public :: sqmc_gpu_check
 
@@ -201,6 +201,12 @@ module sqmc_gpu_mod
       import; type(c_ptr), value :: ctx; integer(c_int64_t), value :: n_var; integer(c_int64_t), intent(in) :: var_up(*), var_dn(*)
       real(c_double), intent(in) :: coeffs(*); real(c_double), value :: e_var, eps_pt_big; integer(c_int32_t), value :: n_slices
       real(c_double), intent(out) :: rdm(*); integer(c_int64_t), intent(out) :: n_connections
+    end function
+    ! the two-body reduced density matrix in spin blocks: rdm_aa, rdm_bb, rdm_ab = c_loc of arrays (norb, norb, norb, norb) indexed
+    ! (p, q, r, s) = <a+_p a+_q a_s a_r>, or c_null_ptr for a block that is not requested; blocks = 1 (aa) + 2 (bb) + 4 (ab)
+    integer(c_int) function sqmc_gpu_hci_2rdm(ctx, n_var, var_up, var_dn, coeffs, blocks, rdm_aa, rdm_bb, rdm_ab) bind(C, name='sqmc_gpu_hci_2rdm')
+      import; type(c_ptr), value :: ctx; integer(c_int64_t), value :: n_var; integer(c_int64_t), intent(in) :: var_up(*), var_dn(*)
+      real(c_double), intent(in) :: coeffs(*); integer(c_int32_t), value :: blocks; type(c_ptr), value :: rdm_aa, rdm_bb, rdm_ab
     end function
     ! the integral rotation of generate_natorb_integrals (hci.f90:3683-3791): rot(norb, norb) with rot(p, k) = component on the
     ! context's orbital k of new orbital p (column-major; the C side reads rot[k norb + p], 0-based); integrals_out(0:n_integrals)

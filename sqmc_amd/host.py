@@ -1796,6 +1796,114 @@ def hci_one_rdm(host, up, dn, wts, energies=None, use_pt=False, eps_pt_big=None,
         g.close()
 
 
+def hci_two_rdm(host, up, dn, wts, blocks="all"):
+    """The two-body density matrix of an HCI wavefunction in spin blocks, GpuChem.two_rdm's dict.  wts: [n] or [n, n_states]; the
+    blocks of several states are averaged, as hci_one_rdm averages.  A time-symmetrised wavefunction is expanded in determinants
+    first (time_symmetrized_to_dets) and the context is one with time_sym off."""
+    import copy
+    w = np.asarray(wts, float)
+    w = w.reshape(len(w), -1)
+    plain, z = host, getattr(host, "z", 1)
+    ts = bool(getattr(host, "time_sym", False))
+    if ts:
+        plain = copy.copy(host)
+        plain.time_sym = False
+    g = plain.gpu()
+    try:
+        total = None
+        for i in range(w.shape[1]):
+            du, dd, dc = time_symmetrized_to_dets(up, dn, w[:, i], z) if ts else (up, dn, w[:, i])
+            d = g.two_rdm(du, dd, dc, blocks)
+            total = d if total is None else {b: total[b] + d[b] for b in d}
+        return {b: a / w.shape[1] for b, a in total.items()} if w.shape[1] > 1 else total
+    finally:
+        g.close()
+
+
+def spin_free_two_rdm(d):
+    """G[p,q,r,s] = G_aa + G_bb + G_ab[p,q,r,s] + G_ab[q,p,s,r] from the dict of GpuChem.two_rdm (all three blocks)"""
+    return d["aa"] + d["bb"] + d["ab"] + d["ab"].transpose(1, 0, 3, 2)
+
+
+def dense_integrals(host):
+    """(h[p, r], (pr|qs) as eri[p, r, q, s], constant) of a ChemHost in its own orbital order, or of a HubbardHost"""
+    n = host.norb
+    if isinstance(host, ChemHost):
+        n1, c2 = n + 1, host.combine_2
+        o = np.arange(1, n1)
+        h = host.integrals[host._index(c2, o[:, None], o[None, :], np.full((n, n), n1), np.full((n, n), n1))]
+        pr = c2[1:n1, 1:n1].astype(np.int64)
+        hi, lo = np.maximum(pr[:, :, None, None], pr[None, None, :, :]), np.minimum(pr[:, :, None, None], pr[None, None, :, :])
+        eri = host.integrals[(hi * (hi - 1)) // 2 + lo]
+        return h, eri, float(host._iv(c2, n1, n1, n1, n1))
+    if isinstance(host, HubbardHost):
+        h, eri = np.zeros((n, n)), np.zeros((n,) * 4)
+        for site in range(n):
+            for nb in host.nbr[site]:
+                if nb:
+                    h[site, nb - 1] -= host.t          # a neighbour reached both ways round a periodic width of 2 hops twice
+            eri[site, site, site, site] = host.U
+        return h, eri, 0.0
+    raise ValueError("dense_integrals: a ChemHost or a HubbardHost")
+
+
+def rdm_energy(host, one_rdm, two_rdm_sf):
+    """E = sum_pr h_pr D_pr + 1/2 sum_pqrs (pr|qs) G[p,q,r,s] + E_core sum c^2, D the spin-summed one-body matrix of GpuChem.one_rdm,
+    G the spin-free two-body matrix; sum c^2 = trace(D) / nelec (nothing is renormalised)"""
+    h, eri, const = dense_integrals(host)
+    one = np.asarray(one_rdm, float)
+    n2 = float(np.trace(one)) / (host.nup + host.ndn)
+    return float(np.sum(h * one)) + 0.5 * float(np.einsum("prqs,pqrs->", eri, np.asarray(two_rdm_sf, float))) + const * n2
+
+
+def s_squared(host, d_ab, norm2=1.0):
+    """<S^2> = (Sz^2 + Sz + n_dn) sum c^2 - sum_pq G_ab[q,p,p,q], Sz = (nup - ndn) / 2"""
+    sz = 0.5 * (host.nup - host.ndn)
+    return (sz * sz + sz + host.ndn) * float(norm2) - float(np.einsum("qppq->", np.asarray(d_ab, float)))
+
+
+def _occ_sign(state, P):
+    return -1.0 if bin(state & ((1 << P) - 1)).count("1") & 1 else 1.0
+
+
+def two_rdm_host(up, dn, coeffs, norb, blocks="all"):
+    """The same three blocks by a plain evaluation over all pairs of the list (the operators applied to the 2 norb-bit strings, up
+    orbitals in front): the timing yardstick of tools/rdm2_time.py, quadratic in the list."""
+    from itertools import combinations
+    names = ("aa", "bb", "ab") if blocks == "all" else (blocks,) if isinstance(blocks, str) else tuple(blocks)
+    up, dn, c = np.asarray(up, np.uint64), np.asarray(dn, np.uint64), np.asarray(coeffs, float)
+    out = {b: np.zeros((norb,) * 4, order="F") for b in names}
+    states = [int(a) | (int(b) << norb) for a, b in zip(up, dn)]
+    pop = np.array([bin(x).count("1") for x in range(65536)], np.uint8)
+
+    def popcount(x):
+        return sum(pop[(x >> np.uint64(16 * k)) & np.uint64(0xFFFF)].astype(np.int32) for k in range(4))
+
+    def bits(x):
+        return [k for k in range(2 * norb) if x >> k & 1]
+
+    for i in range(len(c)):
+        near = np.nonzero(popcount(up ^ up[i]) + popcount(dn ^ dn[i]) <= 4)[0]
+        I = states[i]
+        for j in near:
+            J = states[int(j)]
+            gone, come = bits(J & ~I), bits(I & ~J)
+            w = c[i] * c[j]
+            for extra in combinations(bits(I & J), 2 - len(gone)):
+                A, B = gone + list(extra), come + list(extra)
+                for R, S in ((A[0], A[1]), (A[1], A[0])):
+                    s1 = _occ_sign(J, R); K1 = J ^ (1 << R)
+                    s2 = _occ_sign(K1, S); K2 = K1 ^ (1 << S)
+                    for P, Q in ((B[0], B[1]), (B[1], B[0])):
+                        kind = (P >= norb, Q >= norb, R >= norb, S >= norb)
+                        b = "aa" if not any(kind) else "bb" if all(kind) else "ab" if kind == (False, True, False, True) else None
+                        if b not in out:
+                            continue
+                        s3 = _occ_sign(K2, Q); K3 = K2 | (1 << Q)
+                        out[b][P % norb, Q % norb, R % norb, S % norb] += s1 * s2 * s3 * _occ_sign(K3, P) * w
+    return out
+
+
 def natural_orbitals(rdm, orbital_symmetries):
     """The diagonalisation of generate_natorb_integrals (hci.f90:3591-3632) and nothing after it: one eigh per irrep on the block of
     that irrep's orbitals, eigenvalues (occupation numbers) in decreasing order within the irrep at that irrep's orbital positions,

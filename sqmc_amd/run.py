@@ -277,8 +277,39 @@ def run_extrapolation(deck, h, g, up, dn, wts, p, pt_on_device=False, pt_diag_up
     return dict(ndets=len(up), extrapolation=records)
 
 
+def run_two_rdm(h, up, dn, wts, energy, p, path):
+    """--two-rdm PATH: the spin blocks of the two-body density matrix of every state of the variational wavefunction (host.hci_two_rdm),
+    their checks in print, and all of them in one .npz (aa_1, bb_1, ab_1, aa_2, ...: arrays [p, q, r, s])"""
+    from math import comb
+    from . import host as H
+    nelec, saved, rows = h.nup + h.ndn, {}, []
+    p("\nComputing 2-RDM of the variational wavefunction in spin blocks aa, bb, ab")
+    for i in range(wts.shape[1]):
+        d = H.hci_two_rdm(h, up, dn, wts[:, i])
+        sf = H.spin_free_two_rdm(d)
+        pairs = {"ab": h.nup * h.ndn, "aa": h.nup * (h.nup - 1), "bb": h.ndn * (h.ndn - 1)}      # a block with pairs exists: nelec >= 2
+        b0 = next(b for b in ("ab", "aa", "bb") if pairs[b])
+        n2 = float(np.einsum("pqpq->", d[b0])) / pairs[b0]
+        one = np.einsum("pqrq->rp", sf) / (nelec - 1)          # [p, r] = <a+_r a_p>, the layout of GpuChem.one_rdm
+        e2, s2 = H.rdm_energy(h, one, sf), H.s_squared(h, d["ab"], n2)
+        p("\n2-RDM of state%4d:" % (i + 1))
+        p(" sum c^2 =%18.12f" % n2)
+        for b, want, name in (("aa", comb(h.nup, 2), "C(nup,2)"), ("bb", comb(h.ndn, 2), "C(ndn,2)"), ("ab", h.nup * h.ndn, "nup*ndn")):
+            tr = float(np.einsum("pqpq->", d[b])) * (1.0 if b == "ab" else 0.5)
+            p(" trace %s =%18.12f   %s =%4d" % (b, tr, name, want))
+        p(" Energy from the density matrices =%18.9f   Variational energy =%18.9f   difference =%10.2E" % (e2, energy[i], e2 - energy[i]))
+        p(" <S^2> =%16.9f" % s2)
+        for b in d:
+            saved["%s_%d" % (b, i + 1)] = d[b]
+        rows.append(dict(norm2=n2, energy=e2, s_squared=s2))
+    with open(path, "wb") as f:
+        np.savez(f, **saved)
+    p("\n2-RDM blocks written to " + path)
+    return rows
+
+
 def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False, pt_diag_update=0, one_rdm_path=None, natorb_fcidump=None, greens_signed=False,
-            extrap_rebuild=False):
+            extrap_rebuild=False, two_rdm_path=None):
     """pt_on_device: the samples of the semistochastic PT are evaluated by the library (host.hci_pt2_stochastic on_device);
     pt_diag_update: 0 / 1 / 2, how the PT stage forms H_aa (host.hci_pt2); one_rdm_path: with &natorb get_natorbs = t, also save the
     1-RDM there as .npy; natorb_fcidump: with &natorb get_natorbs = t, rotate the integrals into the natural orbitals and write them
@@ -286,7 +317,12 @@ def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False, pt_diag
     holds natorb_integrals (packed, the host's combine_2) and natorb_fcidump (the path).  None: the run ends on NATORB_STOP.
     greens_signed: with &greens_function get_greens_function = t, fermi_sign = 1 instead of the reference's sums; the result then holds
     greens = (w, G_np1, G_nm1).  extrap_rebuild: with &selected_ci n_energy_batch > 0, see run_extrapolation; the result then holds
-    extrapolation, the records of host.hci_extrapolation_energies."""
+    extrapolation, the records of host.hci_extrapolation_energies.  two_rdm_path: after the variational stage, run_two_rdm; the result
+    then holds two_rdm, its per-state records.  Without it the output is what it is without this argument."""
+    if two_rdm_path and (deck["hamiltonian_type"] == "heg" or deck.get("get_natorbs") or deck.get("n_energy_batch", 0) > 0):
+        raise SystemExit("--two-rdm runs between the variational and the PT stage of a chem deck: not with heg, &natorb get_natorbs or n_energy_batch > 0, which end elsewhere")
+    if two_rdm_path and deck["nelec"] < 2:
+        raise SystemExit("--two-rdm needs at least two electrons")
     if deck["hamiltonian_type"] == "heg":
         return run_hci_heg(deck, out, pt_on_device, pt_diag_update)
     want_greens = bool(deck.get("get_greens_function")) and not deck.get("get_natorbs")      # get_natorbs stops first (hci.f90:745)
@@ -334,6 +370,10 @@ def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False, pt_diag
         if natorb_fcidump is True:
             natorb_fcidump = H.natorb_fcidump_name(min([eps_var] + deck["eps_var_sched"]))
         return run_natorbs(deck, h, up, dn, wts, energy, p, one_rdm_path, natorb_fcidump)
+    two_rdm = None
+    if two_rdm_path:
+        two_rdm = run_two_rdm(h, up, dn, np.asarray(wts, float).reshape(len(up), -1), energy, p, two_rdm_path)
+        t0, t1 = t0 + (time.perf_counter() - t1), time.perf_counter()      # keep the stage out of both times of the last line
     greens = run_greens(deck, h, up, dn, wts, energy, p, greens_signed) if want_greens else None
     results = []
     for i in range(n_states):
@@ -370,6 +410,8 @@ def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False, pt_diag
     res = dict(ndets=len(up), states=results)
     if greens is not None:
         res["greens"] = greens
+    if two_rdm is not None:
+        res["two_rdm"] = two_rdm
     return res
 
 
@@ -401,6 +443,9 @@ def main(argv=None):
                     "fermionic sign (fermi_sign = 1) instead of the reference's sums, which apply none")
     ap.add_argument("--extrap-rebuild", action="store_true", help="HCI decks with &selected_ci n_energy_batch > 0: build every truncation's Hamiltonian from its "
                     "determinants instead of extracting it from the whole list's on the device (the yardstick; the numbers are the same)")
+    ap.add_argument("--two-rdm", default=None, metavar="PATH", help="chem HCI decks: after the variational stage compute the two-body density matrix of every "
+                    "state in spin blocks on the device, print its traces, the energy it gives and <S^2>, and save the blocks to PATH (.npz); refused with heg decks, "
+                    "&natorb get_natorbs and n_energy_batch > 0, whose runs end elsewhere")
     a = ap.parse_args(argv)
     text = open(a.input).read() if a.input else sys.stdin.read()
     lines = [l for l in text.splitlines() if l.strip() and not l.lstrip().startswith("!")]
@@ -411,7 +456,7 @@ def main(argv=None):
                         dtm_elems_in=a.dtm_elems_in, dtm_elems_out=a.dtm_elems_out, spawn_histograms=a.spawn_histograms)
     deck = parse_hci_deck(text)
     return run_hci(deck, a.fcidump, pt_on_device=a.pt_on_device, pt_diag_update=a.pt_diag_update, one_rdm_path=a.one_rdm, natorb_fcidump=a.rotate_integrals,
-                   greens_signed=a.greens_signed, extrap_rebuild=a.extrap_rebuild)
+                   greens_signed=a.greens_signed, extrap_rebuild=a.extrap_rebuild, two_rdm_path=a.two_rdm)
 
 
 if __name__ == "__main__":
