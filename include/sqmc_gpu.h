@@ -600,6 +600,10 @@ int sqmc_gpu_hci_pt2(sqmc_gpu_ctx *ctx, int64_t n_var, const uint64_t *var_up, c
  * owns the work buffers, which are reused from sample to sample and grow only when a sample has more raw connections than any before
  * it.  The list must be sorted by (up, dn) without repeats (hci.f90:1373-1380: an unsorted one is refused); n_mc >= 2.  Chemistry
  * (sqmc_gpu_set_hb_tables first) and HEG; the plan is not built for hubbard2 or hubbardk (refused).  p_i = |c_i| / sum |c|.
+ * A context initialised with time_sym is refused (SQMC_ERR_UNSUPPORTED): on time-reversal representatives the estimator is biased
+ * (two raw excitations of one source that reach one representative stay two connections, so term2 holds x'^2 + x''^2 where
+ * (x' + x'')^2 is needed, and the eps_pt_big mask would see the element after the time-reversal factors).  Pass the
+ * determinant-basis expansion on a context with time_sym = 0, as for sqmc_gpu_hci_pt2 and as the reference does.
  * The plan borrows ctx: free it before sqmc_gpu_finalize.  Active-space masks (sqmc_gpu_hci_set_active_space) are generator
  * state of ctx and apply to every sample as they stand when it runs. */
 typedef struct sqmc_pt2s_plan sqmc_pt2s_plan;
@@ -615,7 +619,11 @@ int sqmc_gpu_hci_pt2_stochastic_prepare(sqmc_gpu_ctx *ctx, int64_t n_var, const 
  * those with |H_ki c_i| > eps_pt_big; n_connected = the number of those k.  The additions have one fixed order (generation order
  * within k, a fixed tree over k), so a sample returns the same bits run to run.  ids and counts go in, one double and one count
  * come back; nothing else crosses the bus.  A sample whose raw connection count reaches 2^31 is refused: this entry does not slice.
- * A refused sample leaves the plan usable. */
+ * A refused sample leaves the plan usable.
+ * The eps_pt_big test is strict for every excitation class, |H_ki c_i| > eps_pt_big (chemistry.f90:6978, 7139, heg.f90:2703).
+ * A sampled determinant with c_i = 0 has p_i = 0 and w_i/p_i = inf; the generator emits nothing for it, its own slot included, so
+ * nothing reads that value: the sample has the bits and the count of the same sample without it, and a sample of such
+ * determinants only returns value = 0.0 and n_connected = 0. */
 int sqmc_gpu_hci_pt2_stochastic_sample(sqmc_pt2s_plan *plan, int64_t n_distinct, const int64_t *ids, const int64_t *counts, double *value,
                                        int64_t *n_connected);
 /* the plan's bookkeeping (any pointer may be NULL): n_alloc = how many times the per-connection buffers were (re)allocated, capacity =

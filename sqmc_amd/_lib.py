@@ -841,7 +841,8 @@ def shell_sort_magnitude(a):
 
 class Pt2StochasticPlan:
     """sqmc_gpu_hci_pt2_stochastic_prepare / _sample / _free: the samples of second_order_pt_alias (hci.f90:1314-1660) on the device.
-    up, dn sorted by (up, dn); the plan borrows the context g: close it before g."""
+    up, dn sorted by (up, dn); the plan borrows the context g: close it before g.  A context with time_sym is refused (the
+    estimator is biased on time-reversal representatives): pass the determinant-basis expansion on one without."""
 
     def __init__(self, g, up, dn, coeffs, e_var, eps_pt, eps_pt_big, n_mc):
         self.L = g.L

@@ -697,6 +697,11 @@ int sqmc_gpu_hci_pt2_stochastic_prepare(sqmc_gpu_ctx *c, int64_t n_var, const ui
   if (n_var >= (1ll << 31)) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_hci_pt2_stochastic_prepare: more than 2^31 variational determinants");
   if (c->htab.sys_type == 2) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_hci_pt2_stochastic_prepare: the stochastic PT plan is not built for hubbard2");
   if (c->htab.sys_type == 3) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_hci_pt2_stochastic_prepare: the stochastic PT plan is not built for hubbardk");
+  // Raw mode keeps the two raw excitations that take one source to one time-reversal representative apart: term2 would hold
+  // x'^2 + x''^2 where the estimator needs (x' + x'')^2, and the big mask would see the element after the time-reversal factors.
+  if (c->htab.time_sym)
+    return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_hci_pt2_stochastic_prepare: the estimator is biased on time-reversal representatives; pass the determinant-basis "
+                                      "expansion (convert_time_symmetrized_to_dets, hci.f90:4365-4564) on a context initialised with time_sym = 0");
   if (c->htab.sys_type == 0 && !c->dev.hb_r) return fail(SQMC_ERR_BAD_ARG, "heat-bath tables not set (sqmc_gpu_set_hb_tables)");
   if (c->htab.sys_type == 1 && c->htab.heg_nmax > 4) return fail(SQMC_ERR_UNSUPPORTED, "HEG connections: plane-wave index beyond +-4");
   for (long long i = 1; i < n_var; i++)

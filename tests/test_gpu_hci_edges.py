@@ -105,7 +105,7 @@ def test_eps_above_max_double(door, which):
     TH.check_eps_above_max_double(d, c, sysm.s.max_double)
 
 
-@pytest.mark.parametrize("which", ["c2_walk", "heg14"])
+@pytest.mark.parametrize("which", ["c2_walk", "c2_hci", "heg14"])
 def test_pt2_against_brute_force(door, which):
     """n_var = 1, a small space, a space closed under the screened generator (delta_e exactly 0.0) and one whose outside
     determinants hold both the smallest and the largest key in sight, each in 1, 2, 5 and 64 slices: delta_e within the
