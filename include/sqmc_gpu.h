@@ -694,6 +694,28 @@ int sqmc_gpu_hci_2rdm(sqmc_gpu_ctx *ctx, int64_t n_var, const uint64_t *var_up, 
  * combine_2 that is not a symmetric one-to-one pair index.  A null pointer or a non-finite entry of rot: SQMC_ERR_BAD_ARG.
  * A refused or failed call leaves integrals_out untouched.  Device memory: (norb (norb + 1) / 2)^2 doubles of work space. */
 int sqmc_gpu_rotate_integrals(sqmc_gpu_ctx *ctx, const double *rot, double *integrals_out);
+/* no counterpart in the reference (which stops at natural orbitals): the generalised Fock matrix, the orbital gradient and the
+ * diagonal of the orbital Hessian of the fixed-coefficient energy, from the density matrices and the context's integrals.
+ * Consumes: one_rdm = the spin-summed 1-RDM D[p,r] as sqmc_gpu_hci_1rdm writes it (norb^2 doubles, flat index p + norb r);
+ * two_rdm_sf = the spin-free 2-RDM G = G_aa + G_bb + G_ab + G_ab[q,p,s,r] of the blocks of sqmc_gpu_hci_2rdm (norb^4 doubles, flat
+ * index p + norb (q + norb (r + norb s))); h and (pr|qs) are the context's packed integrals.  Orbitals 0-based, in the context's
+ * order; nothing is renormalised.  With E(U) = sum h'_pr D[p,r] + 1/2 sum (pr|qs)' G[p,q,r,s] on the integrals rotated as
+ * sqmc_gpu_rotate_integrals rotates them and U(theta) = exp(theta (e_p e_q^T - e_q e_p^T)):
+ *   fock[a + norb P]  = F[a,P] = sum_r h[a,r] D[P,r] + sum_qrs (ar|qs) G[P,q,r,s]
+ *   grad[p + norb q]  = dE/dtheta at 0    = 2 (F[p,q] - F[q,p])
+ *   hdiag[p + norb q] = d2E/dtheta2 at 0  = -2 (F[p,p] + F[q,q]) + Y[pq,pq] + Y[qp,qp] - 2 Y[pq,qp],  hdiag[p + norb p] = 0.0,
+ *   Y[xP,yQ] = 2 h[x,y] D[P,Q] + 2 sum_rs { (xy|rs) G[P,r,Q,s] + (xr|ys) (G[P,Q,r,s] + G[P,s,r,Q]) }.
+ * The formulas are evaluated literally for whatever arrays are passed; they are the derivatives when D is symmetric and
+ * G[p,q,r,s] == G[r,s,p,q] == G[q,p,s,r], as the library's own matrices are.  Each output is norb^2 doubles; any may be NULL (it
+ * is then not computed), not all three.  F is a blocked fp64 GEMM over (q,r,s) split over up to 512 blocks whose partial tiles a
+ * second kernel adds in ascending order; vector FMAs, no floating-point atomics: the same bits call to call and whichever outputs
+ * are asked for; grad[p,q] == -grad[q,p] and grad[p,p] == 0.0 exactly; no output holds -0.0.
+ * Chem contexts only, time_sym and n_core_orb do not matter (only the integrals are read): heg, hubbard2 and hubbardk return
+ * SQMC_ERR_UNSUPPORTED, as does a combine_2 sqmc_gpu_rotate_integrals refuses.  SQMC_ERR_BAD_ARG: a null context or input, all
+ * outputs NULL, a non-finite entry of one_rdm or two_rdm_sf.  A refused or failed call leaves the outputs untouched.
+ * Device memory: norb^4 doubles for G and up to 512 norb^2 for the partial tiles. */
+int sqmc_gpu_orbital_gradient(sqmc_gpu_ctx *ctx, const double *one_rdm, const double *two_rdm_sf, double *fock_out, double *grad_out,
+                              double *hdiag_out);
 /* replaces: get_zeroth_order_variational_greens_function (hci.f90:3849-4050) without its file output: the Green's function of a
  * variational wavefunction sum c_i |i> of energy e0 with the diagonal of H as the zeroth-order Hamiltonian of the N+-1 electron
  * spaces, spin-summed, at the frequencies w[0 .. n_w - 1]:

@@ -28,7 +28,7 @@ EXPORTS = [
     "sqmc_gpu_shard_begin", "sqmc_gpu_shard_pack", "sqmc_gpu_shard_finish", "sqmc_gpu_shard_finish_psit", "sqmc_gpu_comm_unique_id", "sqmc_gpu_comm_init", "sqmc_gpu_comm_size",
     "sqmc_gpu_shard_step", "sqmc_gpu_shard_run", "sqmc_gpu_shard_time_split", "sqmc_gpu_get_rng", "sqmc_gpu_set_rng", "sqmc_gpu_tail_stats", "sqmc_gpu_last_tail", "sqmc_gpu_slowest_steps", "sqmc_gpu_set_chained_runs", "sqmc_gpu_spmv_prepare", "sqmc_gpu_davidson",
     "sqmc_gpu_spmv_apply", "sqmc_gpu_spmv_free", "sqmc_gpu_spmv_plan_submatrix", "sqmc_gpu_build_spmv_plan", "sqmc_gpu_spmv_sym_upper", "sqmc_gpu_hamiltonian_batch",
-    "sqmc_gpu_propose_batch", "sqmc_gpu_hamiltonian_chem_batch", "sqmc_gpu_build_sparse_ham", "sqmc_gpu_hci_connections", "sqmc_gpu_hci_connections_slice", "sqmc_gpu_hci_pt2", "sqmc_gpu_hci_pt2_stochastic_prepare", "sqmc_gpu_hci_pt2_stochastic_sample", "sqmc_gpu_hci_pt2_stochastic_stats", "sqmc_gpu_hci_pt2_stochastic_free", "sqmc_gpu_hci_set_active_space", "sqmc_gpu_diag_update_batch", "sqmc_gpu_hci_set_diag_update", "sqmc_gpu_hci_connections_record", "sqmc_gpu_hci_1rdm", "sqmc_gpu_hci_1rdm_pt", "sqmc_gpu_hci_2rdm", "sqmc_gpu_rotate_integrals", "sqmc_gpu_hci_greens_function", "sqmc_gpu_free", "sqmc_gpu_set_timing", "sqmc_gpu_get_timing",
+    "sqmc_gpu_propose_batch", "sqmc_gpu_hamiltonian_chem_batch", "sqmc_gpu_build_sparse_ham", "sqmc_gpu_hci_connections", "sqmc_gpu_hci_connections_slice", "sqmc_gpu_hci_pt2", "sqmc_gpu_hci_pt2_stochastic_prepare", "sqmc_gpu_hci_pt2_stochastic_sample", "sqmc_gpu_hci_pt2_stochastic_stats", "sqmc_gpu_hci_pt2_stochastic_free", "sqmc_gpu_hci_set_active_space", "sqmc_gpu_diag_update_batch", "sqmc_gpu_hci_set_diag_update", "sqmc_gpu_hci_connections_record", "sqmc_gpu_hci_1rdm", "sqmc_gpu_hci_1rdm_pt", "sqmc_gpu_hci_2rdm", "sqmc_gpu_rotate_integrals", "sqmc_gpu_orbital_gradient", "sqmc_gpu_hci_greens_function", "sqmc_gpu_free", "sqmc_gpu_set_timing", "sqmc_gpu_get_timing",
     "sqmc_gpu_set_spawn_diagnostics", "sqmc_gpu_reset_spawn_diagnostics", "sqmc_gpu_get_spawn_diagnostics", "sqmc_gpu_debug_bucket_boundaries",
 ]
 
@@ -45,9 +45,9 @@ class SqmcGpuError(RuntimeError):
 def build_library(force=False):
     """hipcc cross-compiles for gfx950 without a GPU present."""
     csrc = os.path.join(_HERE, "csrc")
-    # two translation units: sqmc_gpu.hip includes every .h / .inc of csrc/ textually but rdm2_kernels.h, which rdm2_device.hip compiles into
-    # a code object of its own
-    units = [os.path.join(csrc, "sqmc_gpu.hip"), os.path.join(csrc, "rdm2_device.hip")]
+    # three translation units: sqmc_gpu.hip includes every .h / .inc of csrc/ textually but rdm2_kernels.h and orbopt_kernels.h, which
+    # rdm2_device.hip and orbopt_device.hip compile into code objects of their own
+    units = [os.path.join(csrc, "sqmc_gpu.hip"), os.path.join(csrc, "rdm2_device.hip"), os.path.join(csrc, "orbopt_device.hip")]
     src = units + sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".h", ".inc"))) \
         + [os.path.join(_ROOT, "include", "sqmc_gpu.h")]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in src):
@@ -738,6 +738,30 @@ def _gpuchem_rotate_integrals(self, rot):
     return out
 
 
+_ORBOPT_OUT = ("fock", "gradient", "hdiag")
+
+
+def _gpuchem_orbital_gradient(self, one_rdm, two_rdm_sf, outputs="all"):
+    """sqmc_gpu_orbital_gradient: the generalised Fock matrix, the orbital gradient and the diagonal orbital Hessian of the
+    fixed-coefficient energy from the spin-summed one-body matrix (one_rdm's [p, r]) and the spin-free two-body matrix
+    (host.spin_free_two_rdm's [p, q, r, s]) on the context's integrals: a dict of (norb, norb) arrays "fock" [a, P], "gradient" and
+    "hdiag" [p, q] (0-based; dE/dtheta and d2E/dtheta2 at 0 along exp(theta (e_p e_q^T - e_q e_p^T)), rotations as rotate_integrals').
+    outputs: "all", one of the keys, or a sequence of them; only those are computed and returned"""
+    n = self.norb
+    d = np.asarray(one_rdm, np.float64)
+    gg = np.asarray(two_rdm_sf, np.float64)
+    if d.shape != (n, n) or gg.shape != (n,) * 4:
+        raise ValueError("orbital_gradient: one_rdm must be (norb, norb) and two_rdm_sf (norb,) * 4 with norb = %d, got %r and %r" % (n, d.shape, gg.shape))
+    names = _ORBOPT_OUT if outputs == "all" else (outputs,) if isinstance(outputs, str) else tuple(outputs)
+    if not names or any(b not in _ORBOPT_OUT for b in names):
+        raise ValueError("orbital_gradient: outputs must be 'all' or among 'fock', 'gradient', 'hdiag'")
+    d, gg = np.ascontiguousarray(d.reshape(-1, order="F")), np.ascontiguousarray(gg.reshape(-1, order="F"))
+    out = {b: np.zeros(n * n) for b in _ORBOPT_OUT if b in names}
+    self.L.sqmc_gpu_orbital_gradient.argtypes = [C.c_void_p] * 6
+    _chk(self.L.sqmc_gpu_orbital_gradient(self.h, _p(d), _p(gg), *[_p(out[b]) if b in out else None for b in _ORBOPT_OUT]))
+    return {b: a.reshape((n, n), order="F") for b, a in out.items()}
+
+
 def _gpuchem_greens_function(self, up, dn, coeffs, e0, w, fermi_sign=False, parts="both"):
     """sqmc_gpu_hci_greens_function (get_zeroth_order_variational_greens_function, hci.f90:3849-4050): (G_np1, G_nm1) of a determinant
     list in any order at the frequencies w, each an (n_w, norb, norb) array indexed [i_w, p, q] (0-based), spin-summed.  fermi_sign
@@ -945,3 +969,4 @@ GpuChem.one_rdm_pt = _gpuchem_one_rdm_pt
 GpuChem.two_rdm = _gpuchem_two_rdm
 GpuChem.greens_function = _gpuchem_greens_function
 GpuChem.rotate_integrals = _gpuchem_rotate_integrals
+GpuChem.orbital_gradient = _gpuchem_orbital_gradient

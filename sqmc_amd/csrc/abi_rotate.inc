@@ -19,22 +19,32 @@ static hipError_t rot_launch_mode(sqmc_gpu_ctx *c, int blocks, size_t lds, const
 }
 }
 
+// the kernels address the table through combine_2: every index they form must lie inside it, and no two pairs may share a slot
+// (also the test of sqmc_gpu_orbital_gradient, abi_orbopt.inc)
+static int rot_check_combine2(const sqmc_gpu_ctx *c, const char *who) {
+  const ChemTab &t = c->htab;
+  const int n = t.norb, n1 = n + 1;
+  const long long A = t.c2[n1 * t.c2_stride + n1];
+  std::vector<char> seen((size_t)A + 1, 0);
+  for (int p = 1; p <= n; p++)
+    for (int q = 1; q <= p; q++) {
+      const int a = t.c2[p * t.c2_stride + q];
+      if (a < 1 || a >= A || a != t.c2[q * t.c2_stride + p] || seen[a]) return fail(SQMC_ERR_UNSUPPORTED, std::string(who) + ": combine_2 is not a symmetric one-to-one pair index below combine_2(norb+1, norb+1)");
+      seen[a] = 1;
+    }
+  if (A * (A - 1) / 2 + A > c->n_ints) return fail(SQMC_ERR_UNSUPPORTED, std::string(who) + ": integral table shorter than integral_index(norb+1,...)");
+  return SQMC_OK;
+}
+
 int sqmc_gpu_rotate_integrals(sqmc_gpu_ctx *c, const double *rot, double *integrals_out) {
   if (!c || !rot || !integrals_out) return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_rotate_integrals: null argument");
   if (c->htab.sys_type != 0) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_rotate_integrals: chem contexts only (heg, hubbard2 and hubbardk hold no integral table)");
   const ChemTab &t = c->htab;
   const int n = t.norb, n1 = n + 1, nn = n * n;
   for (int e = 0; e < nn; e++) if (!std::isfinite(rot[e])) return fail(SQMC_ERR_BAD_ARG, "sqmc_gpu_rotate_integrals: rot holds a non-finite entry");
-  // the kernels write through combine_2: every index they form must lie inside the table, and no two pairs may share a slot
-  const long long npair = (long long)n * n1 / 2, A = t.c2[n1 * t.c2_stride + n1];
-  std::vector<char> seen((size_t)A + 1, 0);
-  for (int p = 1; p <= n; p++)
-    for (int q = 1; q <= p; q++) {
-      const int a = t.c2[p * t.c2_stride + q];
-      if (a < 1 || a >= A || a != t.c2[q * t.c2_stride + p] || seen[a]) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_rotate_integrals: combine_2 is not a symmetric one-to-one pair index below combine_2(norb+1, norb+1)");
-      seen[a] = 1;
-    }
-  if (A * (A - 1) / 2 + A > c->n_ints) return fail(SQMC_ERR_UNSUPPORTED, "sqmc_gpu_rotate_integrals: integral table shorter than integral_index(norb+1,...)");
+  const long long npair = (long long)n * n1 / 2;
+  int rc = rot_check_combine2(c, "sqmc_gpu_rotate_integrals");
+  if (rc != SQMC_OK) return rc;
   const size_t n_out = (size_t)c->n_ints + 1, lds = (size_t)3 * nn * sizeof(double);
   const char *who = "sqmc_gpu_rotate_integrals";
   std::vector<double> host(n_out);

@@ -41,6 +41,8 @@
 #include "host_sort.h"
 #include "rdm2_plan.h"
 #include "rdm2_launch.h"
+#include "orbopt_plan.h"
+#include "orbopt_launch.h"
 
 #define TPB 256
 #define SPAWN_WIN 1024
@@ -255,6 +257,7 @@ struct sqmc_gpu_ctx {
   sqmc_allreduce_fn psit_reduce; void *psit_reduce_user; double *psit_reduce_buf;
   // behind everything a step reads, so that the layout of the walk's fields is the one it had
   double rdm2_ms[3]; long long rdm2_records[3];      // HIP-event times and record counts of the last sqmc_gpu_hci_2rdm, per block aa, bb, ab (sqmc_gpu_debug_rdm2_ms)
+  double orbopt_ms[3];               // HIP-event times of the last sqmc_gpu_orbital_gradient: Fock GEMM and reduction, gradient, diagonal Hessian (sqmc_gpu_debug_orbopt_ms)
 };
 // a head enqueued for a step that is not going to be the next thing that happens (chained runs): forget it
 static void abandon_head(sqmc_gpu_ctx *c);
@@ -1767,6 +1770,7 @@ int sqmc_gpu_debug_premerge(sqmc_gpu_ctx *c, int64_t cap, int64_t *n0, int64_t *
 #include "abi_rdm2.inc"
 #include "abi_greens.inc"
 #include "abi_rotate.inc"
+#include "abi_orbopt.inc"
 #include "abi_spawn_diag.inc"
 #include "davidson.inc"
 #include "heatbath_setup.inc"

@@ -24,7 +24,7 @@ module sqmc_gpu_mod
   public :: sqmc_gpu_hci_pt2_stochastic_prepare, sqmc_gpu_hci_pt2_stochastic_sample, sqmc_gpu_hci_pt2_stochastic_stats, sqmc_gpu_hci_pt2_stochastic_free
   public :: sqmc_gpu_set_spawn_diagnostics, sqmc_gpu_reset_spawn_diagnostics, sqmc_gpu_get_spawn_diagnostics
   public :: sqmc_gpu_set_hubbardk_space_sym, sqmc_gpu_hubbardk_sym_images, sqmc_gpu_debug_bucket_boundaries
-  public :: sqmc_gpu_hci_1rdm, sqmc_gpu_hci_1rdm_pt, sqmc_gpu_hci_2rdm, sqmc_gpu_rotate_integrals, sqmc_gpu_hci_greens_function
+  public :: sqmc_gpu_hci_1rdm, sqmc_gpu_hci_1rdm_pt, sqmc_gpu_hci_2rdm, sqmc_gpu_rotate_integrals, sqmc_gpu_orbital_gradient, sqmc_gpu_hci_greens_function
   public :: sqmc_gpu_spmv_plan_submatrix, sqmc_shell_sort_magnitude
   public :: sqmc_gpu_check
 
@@ -213,6 +213,12 @@ module sqmc_gpu_mod
     ! in the layout of sqmc_chem_cfg%integrals.  Chem contexts only
     integer(c_int) function sqmc_gpu_rotate_integrals(ctx, rot, integrals_out) bind(C, name='sqmc_gpu_rotate_integrals')
       import; type(c_ptr), value :: ctx; real(c_double), intent(in) :: rot(*); real(c_double), intent(out) :: integrals_out(*)
+    end function
+    ! the generalised Fock matrix, the orbital gradient and the diagonal orbital Hessian from one_rdm(norb, norb) (as sqmc_gpu_hci_1rdm
+    ! writes it) and the spin-free two_rdm_sf(norb, norb, norb, norb); fock_out, grad_out, hdiag_out = c_loc of arrays (norb, norb)
+    ! indexed (a, P) / (p, q), or c_null_ptr for one that is not wanted (not all three).  Chem contexts only
+    integer(c_int) function sqmc_gpu_orbital_gradient(ctx, one_rdm, two_rdm_sf, fock_out, grad_out, hdiag_out) bind(C, name='sqmc_gpu_orbital_gradient')
+      import; type(c_ptr), value :: ctx; real(c_double), intent(in) :: one_rdm(*), two_rdm_sf(*); type(c_ptr), value :: fock_out, grad_out, hdiag_out
     end function
     ! get_zeroth_order_variational_greens_function (hci.f90:3849-4050) without its files: g_np1(n_w, norb, norb) and
     ! g_nm1(n_w, norb, norb) = c_loc of the arrays, or c_null_ptr for a half that is not wanted; fermi_sign = 0 is the reference

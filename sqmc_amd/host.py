@@ -1972,6 +1972,116 @@ def write_natorb_fcidump(path, host, packed):
         f.write(rec % (v[ChemHost._index(c2, n1, n1, n1, n1)], 0, 0, 0, 0))
 
 
+# ------------------------------------------------------------------------- orbital gradient and one orbital-optimisation step
+ORBOPT_MIN_HESS, ORBOPT_MAX_STEP, ORBOPT_MAX_HALVINGS = 0.1, 0.2, 8      # unmeasured choices (tests/golden/README_orbital_gradient.md)
+
+
+def orbital_gradient_host(host, one_rdm, two_rdm_sf):
+    """GpuChem.orbital_gradient's dict by numpy einsum on dense_integrals(host): the formulas of sqmc_gpu_orbital_gradient evaluated
+    literally.  The timing yardstick of tools/orbopt_time.py; O(norb^5) and norb^4 doubles of its own."""
+    h, eri, _ = dense_integrals(host)
+    D, G = np.asarray(one_rdm, float), np.asarray(two_rdm_sf, float)
+    F = h @ D.T + np.einsum("arqs,Pqrs->aP", eri, G, optimize=True)
+    J, K = np.einsum("pprs->prs", eri), np.einsum("prps->prs", eri)
+    GA, GB = np.einsum("qrqs->qrs", G), np.einsum("qqrs->qrs", G) + np.einsum("qsrq->qrs", G)
+    same = 2.0 * np.outer(np.diag(h), np.diag(D)) + 2.0 * (np.einsum("prs,qrs->pq", J, GA) + np.einsum("prs,qrs->pq", K, GB))      # Y[pq,pq]
+    cross = 2.0 * h * D.T + 2.0 * (np.einsum("pqrs,qrps->pq", eri, G) + np.einsum("prqs,qprs->pq", eri, G) + np.einsum("prqs,qsrp->pq", eri, G))
+    fd = np.diag(F)
+    hd = -2.0 * (fd[:, None] + fd[None, :]) + same + same.T - 2.0 * cross
+    np.fill_diagonal(hd, 0.0)
+    return {"fock": F, "gradient": 2.0 * (F - F.T), "hdiag": hd}
+
+
+def orbital_step(gradient, hdiag, orbital_symmetries, min_hess=ORBOPT_MIN_HESS, max_step=ORBOPT_MAX_STEP):
+    """The antisymmetric kappa of one diagonal-Newton step: kappa[p,q] = -g[p,q] / max(|hdiag[p,q]|, min_hess) for p < q within an
+    irrep, kappa[q,p] = -kappa[p,q], exactly 0.0 between irreps and on the diagonal; the whole matrix is then scaled down so that
+    max |kappa| <= max_step.  exp(kappa) (rotation_from_kappa) is the rot of GpuChem.rotate_integrals."""
+    g, hd = np.asarray(gradient, float), np.asarray(hdiag, float)
+    sym = np.asarray(orbital_symmetries).reshape(-1)
+    n = g.shape[0]
+    if g.shape != (n, n) or hd.shape != (n, n) or len(sym) != n:
+        raise ValueError("orbital_step: gradient and hdiag must be (norb, norb) and orbital_symmetries hold norb labels")
+    if not (min_hess > 0.0 and max_step > 0.0):
+        raise ValueError("orbital_step: min_hess and max_step must be positive")
+    k = np.zeros((n, n))
+    for p in range(n):
+        for q in range(p + 1, n):
+            if sym[p] == sym[q]:
+                k[p, q] = -g[p, q] / max(abs(hd[p, q]), min_hess) + 0.0
+                k[q, p] = -k[p, q] + 0.0
+    top = float(np.max(np.abs(k))) if n else 0.0
+    if top > max_step:
+        scale = max_step / top
+        while np.max(np.abs(k * scale)) > max_step:
+            scale = np.nextafter(scale, 0.0)
+        k = k * scale + 0.0
+    return k
+
+
+def rotation_from_kappa(kappa):
+    """exp(kappa) of a real antisymmetric matrix through the Hermitian i kappa = V w V^H: exp(kappa) = V exp(-i w) V^H, real and
+    orthogonal to rounding"""
+    k = np.asarray(kappa, float)
+    if k.ndim != 2 or k.shape[0] != k.shape[1] or not np.array_equal(k, -k.T):
+        raise ValueError("rotation_from_kappa: a real antisymmetric square matrix")
+    n = k.shape[0]
+    # one exponential per connected block of kappa's non-zero pattern: orbitals kappa does not couple (different irreps after
+    # orbital_step) stay exactly uncoupled, and an orbital it does not touch keeps its exact 1.0
+    label = list(range(n))
+    for p, q in zip(*np.nonzero(np.triu(k, 1))):
+        a, b = label[p], label[q]
+        if a != b:
+            label = [a if x == b else x for x in label]
+    out = np.eye(n)
+    for a in sorted(set(label)):
+        ix = np.array([x for x in range(n) if label[x] == a])
+        if len(ix) > 1:
+            w, v = np.linalg.eigh(1j * k[np.ix_(ix, ix)])
+            out[np.ix_(ix, ix)] = ((v * np.exp(-1j * w)) @ v.conj().T).real
+    return out
+
+
+def optimize_orbitals_step(host, up, dn, wts, min_hess=ORBOPT_MIN_HESS, max_step=ORBOPT_MAX_STEP, max_halvings=ORBOPT_MAX_HALVINGS):
+    """One orbital-optimisation step on a fixed HCI wavefunction of a ChemHost: hci_one_rdm and hci_two_rdm (several states:
+    averaged), GpuChem.orbital_gradient, orbital_step, then the rotation exp(scale kappa) with scale = 1, 1/2, ... (at most
+    max_halvings halvings) until the fixed-coefficient energy -- rdm_energy of the same matrices on GpuChem.rotate_integrals' table --
+    is below the starting one.  Returns a dict: "rotation" (U, rot of rotate_integrals), "integrals" (the packed table in U's orbitals,
+    for ChemHost.with_integrals / write_natorb_fcidump), "energy_before", "energy_after", "max_gradient", "gradient_norm",
+    "max_kappa" (of the step taken), "scale", and the matrices "one_rdm", "two_rdm_sf", "gradient", "hdiag".  When no scale lowers the
+    energy the rotation is the identity, the integrals are the host's and scale is 0.0."""
+    if not isinstance(host, ChemHost):
+        raise ValueError("optimize_orbitals_step: a ChemHost (the other systems hold no integral table)")
+    D = hci_one_rdm(host, up, dn, wts)
+    G = spin_free_two_rdm(hci_two_rdm(host, up, dn, wts))
+    e0 = rdm_energy(host, D, G)
+    g = host.gpu()
+    try:
+        og = g.orbital_gradient(D, G, ("gradient", "hdiag"))
+        kappa = orbital_step(og["gradient"], og["hdiag"], host.orbsym[1:host.norb + 1], min_hess, max_step)
+        res = {"rotation": np.eye(host.norb), "integrals": host.integrals.copy(), "energy_before": e0, "energy_after": e0,
+               "max_gradient": float(np.max(np.abs(og["gradient"]))), "gradient_norm": float(np.sqrt(np.sum(np.triu(og["gradient"], 1) ** 2))),
+               "max_kappa": 0.0, "scale": 0.0, "one_rdm": D, "two_rdm_sf": G, "gradient": og["gradient"], "hdiag": og["hdiag"]}
+        scale = 1.0
+        for _ in range(max_halvings + 1):
+            if not np.any(kappa):
+                break
+            U = rotation_from_kappa(scale * kappa)
+            packed = g.rotate_integrals(U)
+            e1 = rdm_energy(host.with_integrals(packed), D, G)
+            if e1 < e0:
+                res.update(rotation=U, integrals=packed, energy_after=e1, max_kappa=float(np.max(np.abs(scale * kappa))), scale=scale)
+                break
+            scale *= 0.5
+        return res
+    finally:
+        g.close()
+
+
+def optorb_fcidump_name(eps):
+    """the file of --optimize-orbitals: natorb_fcidump_name's number behind 'FCIDUMP_opt_eps_var='"""
+    return "FCIDUMP_opt_eps_var=" + natorb_fcidump_name(eps)[len("FCIDUMP_eps_var="):]
+
+
 # ------------------------------------------------------------------------- Green's function and density of states
 GREENS_HEADERS = {"G0_N+1": " w,p,q,G0_{N+1}(w,p,q)", "G0_N-1": " w,p,q,G0_{N-1}(w,p,q)", "rho": " Density of states: w, rho_{N+1}(w),rho_{N-1}(w),rho_tot(w)"}
 GREENS_CUT = 1e-8
