@@ -329,7 +329,8 @@ class GpuChem:
     def debug_premerge(self):
         """sqmc_gpu_debug_premerge (debugging aid, not part of the ABI in include/): the list the last semistochastic radix-tail step or
         sqmc_gpu_annihilate call stood on in front of its merge, as dict(res_wt: the residents' weights after death/clone and the
-        projection; up, dn, wt, imp_distance, initiator: the spawn records in creation order, weight 0 meaning no walker)"""
+        projection; up, dn, wt, imp_distance, initiator: the spawn records in creation order, weight 0 meaning no walker).
+        The spawn records are valid behind any tail, the last step of a pipelined run() included; res_wt behind the radix tail only."""
         f = self.L.sqmc_gpu_debug_premerge
         f.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8
         n0, ns = C.c_int64(), C.c_int64()
@@ -441,6 +442,15 @@ class GpuChem:
         self.L.sqmc_gpu_last_tail.argtypes = [C.c_void_p, C.c_void_p]
         _chk(self.L.sqmc_gpu_last_tail(self.h, info))
         return dict(kind=("radix", "bucket", "bucket-retried")[info[0]], items=int(info[1]), merge=bool(info[2]), packed=bool(info[3]))
+
+    def debug_last_head(self):
+        """sqmc_gpu_debug_last_head (debugging aid, not part of the ABI in include/): the head the last step() ran behind, as
+        dict(pipelined, offsets=who wrote the child offsets, parent_hint, fuse=k_spawn's FUSE form, spare_blocks, proposal)"""
+        info = (C.c_int32 * 6)()
+        self.L.sqmc_gpu_debug_last_head.argtypes = [C.c_void_p, C.c_void_p]
+        _chk(self.L.sqmc_gpu_debug_last_head(self.h, info))
+        return dict(pipelined=bool(info[0]), offsets=("gate_scan", "fused_gate_scan", "anneal_lookback", "anneal_bucket", "anneal_split_place", "replay_prepass")[info[1]],
+                    parent_hint=bool(info[2]), fuse=bool(info[3]), spare_blocks=int(info[4]), proposal=("uniform", "heatbath", "cauchy", "cauchy_ts")[info[5]])
 
     def set_chained_runs(self, on):
         """sqmc_gpu_set_chained_runs: keep the step pipeline primed across run() calls (block-structured hosts)"""

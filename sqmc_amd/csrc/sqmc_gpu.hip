@@ -250,6 +250,8 @@ struct sqmc_gpu_ctx {
   // hf_to_psit (psit_kernels.h)
   HbHost *hb_host;
   long long dbg_n0, dbg_nall;          // sizes of the last step's list in front of the merge (sqmc_gpu_debug_premerge)
+  int nh[6], lh[6];                    // the head enqueued last / the head the last sqmc_gpu_step ran behind (sqmc_gpu_debug_last_head); host bookkeeping only
+  bool head_offsets_split;             // head_offsets_done by the two-kernel annihilation (k_anneal<., 0, 1> + k_anneal_place)
   bool psit_on; int base_key_bits; PsitArgs psit; int *d_ps_loc, *d_ps_of, *d_ps_impof; double *d_ps_c, *d_ps_diag, *d_ps_dwct, *d_ps_dwps, *d_ps_dwimp, *d_ps_p2, *d_ps_part, *d_ps_raw;
   // hf_to_psit sharded over ranks (sqmc_gpu_set_hf_to_psit_shard): this rank's C(T) share (host copy, for the upload's check), its
   // e_loc_num / den, the T^-1 exchange vector, and the caller's all-reduce of it (three-phase steps without a communicator)
@@ -1003,6 +1005,9 @@ static int enqueue_head(sqmc_gpu_ctx *c, const StepP &p, u64 step, long long n0,
   PrjPre pp; memset(&pp, 0, sizeof(pp));
   c->head_y_done = false;
   c->shard_y_ok = false;
+  // who writes the child offsets this head's k_spawn searches: 0 k_gate + scan, 1 the fused gate + the scan that carries the final sums,
+  // 2 k_anneal's own look-back, 3 k_anneal_bucket, 4 k_anneal<., 0, 1> + k_anneal_place (5: k_replay_prepass, sqmc_gpu_step)
+  const int offsets_producer = !gate_done ? 0 : (!c->head_offsets_done ? 1 : (c->head_offsets_bucket ? 3 : (c->head_offsets_split ? 4 : 2)));
   if (dev_n && c->d_grow && c->comm && !c->comm2 && c->n_imp > 0 && p.semi) {
     // In-library sharded step (one communicator): the all-reduce of the deterministic weights needs nothing the host still has to
     // decide either.  It goes in front of k_spawn, whose spare blocks then multiply this rank's rows of the projector into the
@@ -1103,6 +1108,8 @@ static int enqueue_head(sqmc_gpu_ctx *c, const StepP &p, u64 step, long long n0,
   const size_t spawn_lds = std::max<size_t>(hb.B > 0 ? (size_t)BK_PART_LDS(hb.B) : 0, hq_blk > 0 ? (size_t)(TPB / 16) * bk_hii_terms_of(c->htab.nup, c->htab.ndn) * 8 : 0);
   // the blocks in front of the spawning ones (k_spawn): final sums, one per H_ii queue, eight projector rows each, the boundaries' one or two
   const int n_spare = (spawn_fin.on ? 1 : 0) + hq_blk + (pp.n_imp > 0 ? nblk(prj_row_waves(pp.n_imp), TPB / 64) : 0) + bk_boundary_blocks(hb);
+  c->nh[0] = dev_n ? 1 : 0; c->nh[1] = offsets_producer; c->nh[2] = hb.parent_hint ? 1 : 0;
+  c->nh[3] = (spawn_kind(c) != SPAWN_UNIFORM || spawn_fuse) ? 1 : 0; c->nh[4] = n_spare; c->nh[5] = spawn_kind(c);      // (SPAWN_LAUNCH_K: every proposal but the uniform one has the FUSE form only)
   if (nfree > 0) {
     if (s0)
       SPAWN_LAUNCH_EXT(spawn_kind(c), spawn_fuse, spawn_diag(c), dim3((unsigned)(nblk(nfree) + n_spare)), dim3(TPB), spawn_lds, st, s0, s1, 0, c->dev, c->w, c->d_child_off, c->d_wchild,
@@ -1338,7 +1345,7 @@ static int step_tail_impl(sqmc_gpu_ctx *c, const StepP &p_in, long long n0, long
       else hipLaunchKernelGGL(k_anneal_bucket, dim3(nb), dim3(BK_AT), 0, st, BUCKET_ARGS);
 #undef BUCKET_ARGS
       c->bk_steps++;
-      c->head_offsets_done = (go.child_off != nullptr); c->head_offsets_bucket = true;
+      c->head_offsets_done = (go.child_off != nullptr); c->head_offsets_bucket = true; c->head_offsets_split = false;
       c->scount_B = ba.B; c->scount_buf = ba.kb ? c->head_kb_use : -1; c->scount_pos = c->pos_flip;
     } else if (c->psit_on) { c->scount_B = 0; if (items <= 2) ANNEAL_LAUNCH_(2, 1); else ANNEAL_LAUNCH_(3, 1); }      // hf_to_psit: everything outside C(T); the C(T) segment is finished below
     else if (anneal_split_ok(c, p, mode, nall, items, go.child_off != nullptr, use_mail)) {
@@ -1353,10 +1360,10 @@ static int step_tail_impl(sqmc_gpu_ctx *c, const StepP &p_in, long long n0, long
       if (items == 3) hipLaunchKernelGGL(k_anneal_place<3>, dim3(nb), dim3(TPB), 0, st, sg, c->m, c->d_loc_imp, (const u64 *)c->d_ct_hkey, (const u32 *)c->d_ct_hidx, c->ct_mask, (const double *)c->d_ct_num, (const double *)c->d_ct_den, c->d_partials, p, nb, go, (const DevScalars *)c->d_sc);
       else hipLaunchKernelGGL(k_anneal_place<4>, dim3(nb), dim3(TPB), 0, st, sg, c->m, c->d_loc_imp, (const u64 *)c->d_ct_hkey, (const u32 *)c->d_ct_hidx, c->ct_mask, (const double *)c->d_ct_num, (const double *)c->d_ct_den, c->d_partials, p, nb, go, (const DevScalars *)c->d_sc);
       if (t_anneal >= 0) hipEventRecord(c->ev1[t_anneal], st);
-      c->head_offsets_done = true; c->head_offsets_bucket = false;
+      c->head_offsets_done = true; c->head_offsets_bucket = false; c->head_offsets_split = true;
     }
     else { c->scount_B = 0; if (items == 1) ANNEAL_LAUNCH(1); else if (items == 2) ANNEAL_LAUNCH(2); else if (items == 3) ANNEAL_LAUNCH(3); else ANNEAL_LAUNCH(4);
-           c->head_offsets_done = (go.child_off != nullptr); c->head_offsets_bucket = false; }
+           c->head_offsets_done = (go.child_off != nullptr); c->head_offsets_bucket = false; c->head_offsets_split = false; }
 #undef ANNEAL_LAUNCH_
 #undef ANNEAL_LAUNCH
 #undef ANNEAL_ARGS
@@ -1575,6 +1582,7 @@ int sqmc_gpu_step(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double out[16]) {
     if (t_gate_scan >= 0) hipEventRecord(c->ev1[t_gate_scan], st);
     HIPCHK(hipEventRecord(c->e_fork, st)); c->fork_valid = true;
     cseq = ++c->cnt_seq;
+    c->nh[0] = 0; c->nh[1] = 5; c->nh[2] = 0; c->nh[3] = spawn_kind(c) != SPAWN_UNIFORM ? 1 : 0; c->nh[4] = 0; c->nh[5] = spawn_kind(c);
     if (M > n0) {
       if (t_spawn >= 0)
         SPAWN_LAUNCH_EXT(spawn_kind(c), 0, spawn_diag(c), dim3(nblk(M - n0)), dim3(TPB), 0, st, c->ev0[t_spawn], c->ev1[t_spawn], 0, c->dev, c->w, c->d_child_off, c->d_wchild,
@@ -1588,6 +1596,7 @@ int sqmc_gpu_step(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double out[16]) {
                          t_spawn >= 0 ? c->ev0[t_spawn] : nullptr, t_spawn >= 0 ? c->ev1[t_spawn] : nullptr, &cseq);
     if (r) return r;
   }
+  memcpy(c->lh, c->nh, sizeof(c->lh));      // (the tail below may enqueue the next step's head over nh)
   // ---- death/clone and the deterministic projection: side streams beside spawn + sort -- or nothing at all here when the
   //      bucket tail is going to do them itself (pipelined steps whose missing H_ii the head already filled and whose
   //      deterministic weights the last bucket tail left row by row)
@@ -1749,9 +1758,11 @@ int sqmc_gpu_annihilate(sqmc_gpu_ctx *c, const sqmc_step_params *sp, int64_t n_s
   return step_tail(c, p, n0, nall, false, out);
 }
 
-// Debugging aid, not part of the ABI in include/: the list the last semistochastic step (radix tail) stood on in front of its merge.
-// Resident weights after death/clone and the projection (the buffer the annihilation kernel read: the OTHER one now) and the step's
-// spawn records in creation order (weight 0: no walker).
+// Debugging aid, not part of the ABI in include/: the list the last semistochastic step stood on in front of its merge.
+// The step's spawn records in creation order (weight 0: no walker) are valid behind ANY tail, the last step of a pipelined
+// sqmc_gpu_run included (k_spawn's record array belongs to neither walker buffer, no tail writes it, and the last step of a run that
+// is not chained enqueues no further head).  The resident weights after death/clone and the projection (the buffer the annihilation
+// kernel read: the OTHER one now) are valid behind the radix tail only: the bucket tail does death/clone inside its own kernel.
 int sqmc_gpu_debug_premerge(sqmc_gpu_ctx *c, int64_t cap, int64_t *n0, int64_t *n_spawn, double *res_wt, uint64_t *sp_up, uint64_t *sp_dn, double *sp_wt, int8_t *sp_impd, int8_t *sp_init) {
   if (!c || !n0 || !n_spawn) return SQMC_ERR_BAD_ARG;
   hipStreamSynchronize(c->st);
@@ -1761,6 +1772,15 @@ int sqmc_gpu_debug_premerge(sqmc_gpu_ctx *c, int64_t cap, int64_t *n0, int64_t *
   std::vector<SpawnRec> r(*n_spawn);
   if (*n_spawn > 0 && hipMemcpy(r.data(), c->w.sp, *n_spawn * sizeof(SpawnRec), hipMemcpyDeviceToHost) != hipSuccess) return SQMC_ERR_HIP;
   for (long long i = 0; i < *n_spawn; i++) { sp_up[i] = r[i].up; sp_dn[i] = r[i].dn; sp_wt[i] = r[i].wt; sp_impd[i] = (int8_t)flg_impd((u32)r[i].flg); sp_init[i] = (int8_t)flg_init((u32)r[i].flg); }
+  return SQMC_OK;
+}
+
+// Debugging aid like sqmc_gpu_last_tail, not part of the ABI in include/: the head (gate, child offsets, k_spawn) the last sqmc_gpu_step
+// ran behind.  info: [0] 1 = enqueued ahead by the step before (pipelined), [1] the producer of the child offsets (see enqueue_head; 5:
+// k_replay_prepass), [2] 1 = k_spawn started from parent_hint, [3] 1 = k_spawn's FUSE form, [4] its spare blocks, [5] its proposal (SPAWN_*).
+int sqmc_gpu_debug_last_head(sqmc_gpu_ctx *c, int32_t info[6]) {
+  if (!c || !info) return SQMC_ERR_BAD_ARG;
+  for (int k = 0; k < 6; k++) info[k] = c->lh[k];
   return SQMC_OK;
 }
 
