@@ -251,7 +251,7 @@ static int shard_begin_impl(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double 
   HIPCHK(hipGetLastError());
   long long nch = 0;
   int wr = mail ? wait_mail(&c->h_mail->cnt_seq, cseq, st) : -1;
-  if (wr > 0) return fail(SQMC_ERR_HIP, std::string("step failed on the device: ") + hipGetErrorString((hipError_t)wr));
+  if (wr > 0) return mail_fail(wr);
   if (wr == 0) nch = (long long)c->h_mail->n_children;
   else if (n0 > 0) { u64 v; HIPCHK(hipMemcpyAsync(&v, &c->d_sc->n_children, 8, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st)); nch = (long long)v; }
   if (full_sync) HIPCHK(hipStreamSynchronize(st));      // the caller's collective library reads x_global on its own stream
@@ -590,7 +590,7 @@ static int shard_step_impl(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double o
     HIPCHK(hipGetLastError());
     volatile u64 *flag = (volatile u64 *)(c->h_cnt_all + ((P * ROW + 15) / 16) * 16);
     int wr = wait_mail(flag, qs, st);
-    if (wr > 0) return fail(SQMC_ERR_HIP, std::string("step failed on the device: ") + hipGetErrorString((hipError_t)wr));
+    if (wr > 0) return mail_fail(wr);
     if (wr < 0) HIPCHK(hipMemcpy(c->h_cnt_all, c->d_cnt_all, (size_t)P * ROW * 4, hipMemcpyDeviceToHost));
   }
   const u32 *all = c->h_cnt_all;

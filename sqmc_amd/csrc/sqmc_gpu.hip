@@ -938,6 +938,12 @@ static int wait_mail_(volatile u64 *flag, u64 expect, hipStream_t st) {
     __builtin_ia32_pause();
   }
 }
+static int mail_fail(int wr) { return fail(SQMC_ERR_HIP, std::string("step failed on the device: ") + hipGetErrorString((hipError_t)wr)); }      // wait_mail returned a hipError_t
+// the sums the mail carried, into h_sc: the first `nstats` of them, and with `counts` the walker counts and the bucket tail's flags too
+static void take_mail(sqmc_gpu_ctx *c, int nstats, bool counts) {
+  c->h_sc->err = (int)c->h_mail->err; for (int i = 0; i < nstats; i++) c->h_sc->stats[i] = c->h_mail->stats[i];
+  if (counts) { c->h_sc->tot2 = c->h_mail->tot2; c->h_sc->retry = (int)c->h_mail->retry; c->h_sc->bk_fill = (unsigned int)c->h_mail->bk_fill; }
+}
 // stage timers of the last step are read when the next step starts (or when they are asked for):
 // by then their events have completed and no extra synchronisation is paid inside the step
 static void collect_timers(sqmc_gpu_ctx *c) {
@@ -1206,27 +1212,30 @@ static bool anneal_split_ok(sqmc_gpu_ctx *c, const StepP &p, int mode, long long
   return true;
 }
 #define SQMC_INTERNAL_RETRY 1000      // step_tail_impl: the bucket tail gave up, nothing of it counts; run the radix tail
-static int step_tail_impl(sqmc_gpu_ctx *c, const StepP &p_in, long long n0, long long nall, bool join_side_stream, double out[16], bool allow_bucket) {
-  StepP p = p_in;
-  p.nimp_cap = c->d_loc_imp ? (int)std::max<long long>(c->n_imp_local, c->n_imp) : 0;     // what set_projector / shard_config allocated
-  hipStream_t st = c->st;
-  const long long M = c->mwalk;
-  const int mode = c->rng_mode; const u64 seed = c->seed64, step = c->step_no;
-  ScanWork sw[3];
-  for (int q = 0; q < 3; q++) { sw[q].state = c->d_scan_state + q * c->cap_tiles; sw[q].ticket = c->d_scan_ticket + q; sw[q].cap_tiles = c->cap_tiles; sw[q].self_clear = false; }
-  // ---- sort
-  TBEG(sort, st);
-  if (mode == SQMC_RNG_REPLAY)
-    hipLaunchKernelGGL(k_main_keys, dim3(nblk(n0)), dim3(TPB), 0, st, c->dev, c->w.up, c->w.dn, c->d_keys, c->d_vals, n0, c->pack);
-  SortWork so; so.k_alt = c->d_keys_alt; so.v_alt = c->d_vals_alt; so.hist = c->d_hist; so.rowtot = c->d_rowtot; so.cap = M;
-  u64 *skey = c->d_keys; u32 *perm = c->pack ? (u32 *)nullptr : c->d_vals;
-  static const long long merge_min = getenv("SQMC_MERGE_SORT_MIN") ? atoll(getenv("SQMC_MERGE_SORT_MIN")) : (1ll << 20);
-  // Short lists (the launch-bound regime): no global sort at all.  The spawns are partitioned block-locally into B key
-  // ranges whose splitters are resident walkers (sorted since the last step), and one block per range sorts, merges and
-  // annihilates its share in LDS (bucket_kernels.h).  Needs packed keys, the COUNTER discipline, ordered residents.
+// ---- The tail of a step, stage by stage.  What the stages share is a TailPlan on step_tail_impl's stack: each stage
+// ---- reads what the ones before it decided and writes its own part; nothing of it outlives the call.
+struct TailPlan {
+  StepP p; long long n0, nall; int mode; u64 seed, step;      // the inputs (p with nimp_cap set)
+  bool bucket; BucketArgs ba;                                  // tail_choose: the short-list tail and its partition
+  u64 *skey; u32 *perm;                                        // tail_sort: the sorted keys and, with unpacked keys, their permutation
+  int nbm; bool use_mail; u64 seq;                             // tail_join: this step's mail
+  int items, nb, n_ft; bool fuse_gate; GateOut go;             // anneal_plan (a plain walk's nb: tail_plain_chain)
+  bool stop_now;                                               // tail_receive: a collective stop outranks the bucket tail's re-run
+};
+static inline long long merge_sort_min() { static const long long v = getenv("SQMC_MERGE_SORT_MIN") ? atoll(getenv("SQMC_MERGE_SORT_MIN")) : (1ll << 20); return v; }
+static inline int bucket_holdoff_steps() { static const int hold = getenv("SQMC_BUCKET_HOLDOFF") ? atoi(getenv("SQMC_BUCKET_HOLDOFF")) : 8; return hold; }
+static inline void swap_walk_buffers(sqmc_gpu_ctx *c) {
+  std::swap(c->w.up, c->m.up); std::swap(c->w.dn, c->m.dn); std::swap(c->w.wt, c->m.wt); std::swap(c->w.flg, c->m.flg);
+  std::swap(c->w.me, c->m.me); std::swap(c->w.en, c->m.en); std::swap(c->w.ed, c->m.ed); std::swap(c->w.irk, c->m.irk);
+}
+// 1. choose the tail.  Short lists (the launch-bound regime): no global sort at all.  The spawns are partitioned block-locally into B key
+// ranges whose splitters are resident walkers (sorted since the last step), and one block per range sorts, merges and
+// annihilates its share in LDS (bucket_kernels.h).  Needs packed keys, the COUNTER discipline, ordered residents.
+static int tail_choose(sqmc_gpu_ctx *c, TailPlan &t, bool allow_bucket) {
+  const StepP &p = t.p; const long long n0 = t.n0, nall = t.nall, M = c->mwalk; hipStream_t st = c->st;
+  const long long merge_min = merge_sort_min();
   static const long long bucket_max = getenv("SQMC_BUCKET_MAX") ? atoll(getenv("SQMC_BUCKET_MAX")) : (1ll << 20);
-  BucketArgs ba; memset(&ba, 0, sizeof(ba));
-  bool bucket = false;
+  BucketArgs &ba = t.ba; bool &bucket = t.bucket;
   const BucketArgs head_ba = c->head_ba; c->head_ba.B = 0;             // consumed (or ignored) by this tail
   c->last_nall = nall; c->dbg_n0 = n0; c->dbg_nall = nall;
   if (allow_bucket && bucket_static_ok(c, p) && c->residents_sorted && nall > n0 && nall < bucket_max && nall < merge_min && n0 >= 64) {
@@ -1266,8 +1275,18 @@ static int step_tail_impl(sqmc_gpu_ctx *c, const StepP &p_in, long long n0, long
     int rs = launch_side_kernels(c, p, n0, true); if (rs) return rs;
   }
   c->lt_kind = bucket ? 1 : 0; c->lt_items = 0; c->lt_pack = c->pack; c->lt_merge = 0;
-  if (bucket) {
-  } else if (p.semi && c->residents_sorted && nall >= merge_min) {
+  return SQMC_OK;
+}
+// 2. sort: nothing (bucket), the spawns alone and a merge (long lists), or the whole list
+static void tail_sort(sqmc_gpu_ctx *c, TailPlan &t) {
+  const StepP &p = t.p; const long long n0 = t.n0, nall = t.nall; hipStream_t st = c->st;
+  if (t.mode == SQMC_RNG_REPLAY)          // (a REPLAY walk takes no bucket tail: tail_choose has put nothing on the stream)
+    hipLaunchKernelGGL(k_main_keys, dim3(nblk(n0)), dim3(TPB), 0, st, c->dev, c->w.up, c->w.dn, c->d_keys, c->d_vals, n0, c->pack);
+  SortWork so; so.k_alt = c->d_keys_alt; so.v_alt = c->d_vals_alt; so.hist = c->d_hist; so.rowtot = c->d_rowtot; so.cap = c->mwalk;
+  u64 *&skey = t.skey; u32 *&perm = t.perm;
+  skey = c->d_keys; perm = c->pack ? (u32 *)nullptr : c->d_vals;
+  if (t.bucket) {
+  } else if (p.semi && c->residents_sorted && nall >= merge_sort_min()) {
     c->lt_merge = (nall > n0) ? 1 : 0;
     // Large lists: the walkers [0, n0) are in order already (every step leaves them so), so only the spawns
     // [n0, nall) are sorted and one stable merge (walker before spawns on equal keys, spawns in creation order)
@@ -1285,120 +1304,156 @@ static int step_tail_impl(sqmc_gpu_ctx *c, const StepP &p_in, long long n0, long
     device_radix_sort(skey, perm, nall, c->key_bits, so, st, c->pack ? 32 : 0);
     if (skey != c->d_keys) { c->d_keys_alt = c->d_keys; c->d_keys = skey; if (!c->pack) { c->d_vals_alt = c->d_vals; c->d_vals = perm; } }
   }
-  TEND(sort, st);
-  // ---- join: from here on weights are read
-  if (join_side_stream) { HIPCHK(hipStreamWaitEvent(st, c->e_join, 0)); if (p.semi && !c->d_grow && !getenv("SQMC_NO_ST3")) HIPCHK(hipStreamWaitEvent(st, c->e_join3, 0)); }
-  const int nbm = nblk(nall);
-  const bool use_mail = (c->comm == nullptr);          // with a communicator the sums are all-reduced on the device first
-  const u64 seq = ++c->mail_seq;
-  int nb, n_ft = 0;
-  bool fuse_gate = false;
-  if (p.semi) {
-    // one kernel from the sorted list to the new walker arrays; the buffers swap roles afterwards
-    // timed by the kernel's own start/stop timestamps (hipExtLaunchKernelGGL events) at every timing level: the
-    // per-launch time bench.py reports for the roofline of this, the longest kernel on the critical path
-    int t_anneal = -1;
-    if (kernel_events_on(c, step) && c->nt < NTIMERS) { t_anneal = c->nt++; c->tname[t_anneal] = "anneal"; }
-    static const int items_env = getenv("SQMC_ANNEAL_ITEMS") ? atoi(getenv("SQMC_ANNEAL_ITEMS")) : 0;
-    // small lists want many tiles, large ones short look-back chains; 4 slots per thread spill 31 registers at the 4 waves per SIMD
-    // the kernel wants (3: 8), which only pays from ~10^7 slots on (measured: 0.449 against 0.458 ms/step at 2.5e6 slots, 3.44 against 3.35 at 1.7e7)
-    int items = items_env ? items_env : (nall < (1ll << 20) ? 2 : (nall < (1ll << 23) ? 3 : 4));
-    if (items < 3 && getenv("SQMC_ANNEAL_SPLIT_MIN") && nall >= atoll(getenv("SQMC_ANNEAL_SPLIT_MIN"))) items = 3;      // (tests: the two-kernel form exists for 3 and 4 slots per thread)
-    if (c->psit_on) items = items <= 2 ? 2 : 3;          // the two shapes k_anneal<., 1> is instantiated with
-    nb = n_ft = bucket ? ba.B : (int)((nall + (long long)TPB * items - 1) / ((long long)TPB * items));
-    if (!bucket) c->lt_items = items;
-    // pipelined steps: the kernel also does the next step's gate (keys, child counts, child weights) as it places a walker
-    static const bool no_fuse = getenv("SQMC_NO_GATE_FUSION") != nullptr;
-    static const bool no_psit_fuse = getenv("SQMC_PSIT_NO_GATE_FUSION") != nullptr;
-    static const bool no_wide_fuse = getenv("SQMC_NO_WIDE_KEY_GATE_FUSION") != nullptr;      // keys wider than 32 bits (the electron gas): fused as well, the slot index in its own array
-    fuse_gate = c->pipeline_next && (c->pack || (!c->psit_on && !no_wide_fuse && !bucket)) && !no_fuse && !(c->psit_on && no_psit_fuse);
-    GateOut go; memset(&go, 0, sizeof(go));
-    if (c->psit_on) { go.ps_of = c->d_ps_of; go.ps_raw = c->d_ps_raw; }
-    if (fuse_gate) {
-      go.on = 1; go.keys = (skey == c->d_keys) ? c->d_keys_alt : c->d_keys;      // never the buffer the kernel reads its sorted words from
-      go.vals = (skey == c->d_keys) ? c->d_vals_alt : c->d_vals; go.pack = c->pack;
-      go.nchild = c->d_nchild; go.wchild = c->d_wchild; go.cutoff = p.cutoff; go.step_next = step + 1;
-      static const bool no_off = getenv("SQMC_BUCKET_NO_OFFSETS") != nullptr;
-      static const bool no_shard_off = getenv("SQMC_SHARD_NO_OFFSETS") != nullptr;
-      if (bucket && (use_mail || !no_shard_off) && !no_off && c->n_imp < (1ll << 18) && c->last_wabs > 0 && c->last_wabs < 4.0e6) go.child_off = c->d_child_off;     // 24 bits of the look-back word hold the children
-      // the radix tail of an unsharded pipelined step carries the child offsets too, in a look-back of their own (walk_kernels.h)
-      static const bool no_roff = getenv("SQMC_RADIX_NO_OFFSETS") != nullptr;
-      if (!bucket && use_mail && !c->d_grow && mode == SQMC_RNG_COUNTER && !no_roff && !c->psit_on) go.child_off = c->d_child_off;      // (hf_to_psit: the C(T) segment's counts come from a later kernel: the head scans)
-      static const bool no_hint = getenv("SQMC_NO_PARENT_HINT") != nullptr;
-      if (go.child_off && use_mail && !c->d_grow && !no_hint) go.bpar = c->d_bpar;
-    }
-    c->head_bpar_ok = go.bpar != nullptr;
-#define ANNEAL_ARGS c->w, c->m, skey, perm, c->d_loc_imp, c->d_ct_hkey, c->d_ct_hidx, c->ct_mask, c->d_ct_num, c->d_ct_den, c->d_partials, c->d_wabs_part, n0, nall, p,  \
-                    c->invalid_key, c->pack, mode, seed, step, c->d_sc, c->d_fstate, c->d_fstate + c->cap_ftiles, c->d_fticket, go
-#define ANNEAL_LAUNCH_(I, P) do { if (t_anneal >= 0) hipExtLaunchKernelGGL((k_anneal<I, P, 0>), dim3(nb), dim3(TPB), 0, st, c->ev0[t_anneal], c->ev1[t_anneal], 0, ANNEAL_ARGS, AnnealStage{}); \
-                                  else hipLaunchKernelGGL((k_anneal<I, P, 0>), dim3(nb), dim3(TPB), 0, st, ANNEAL_ARGS, AnnealStage{}); } while (0)
-#define ANNEAL_LAUNCH(I) ANNEAL_LAUNCH_(I, 0)
-    if (bucket) {
-      FusedSide fs; memset(&fs, 0, sizeof(fs));
-      fs.on = c->side_pending ? 1 : 0; fs.y = c->d_prj_y;
-      fs.x_in = c->d_prj_xs[c->xs_cur]; fs.x_out = c->d_prj_xs[c->xs_cur ^ 1];
-      static const bool no_fs = getenv("SQMC_NO_FUSED_SIDE") != nullptr;
-      if (c->pipeline_next && p.semi && !no_fs) c->head_prj_x = fs.x_out;      // the head enqueued below may multiply the projector into it
-#define BUCKET_ARGS c->w, c->m, (const u64 *)c->d_keys, c->d_loc_imp, c->d_ct_hkey, c->d_ct_hidx, c->ct_mask, c->d_ct_num, c->d_ct_den, c->d_partials, c->d_wabs_part, \
-                    n0, nall - n0, p, c->invalid_key, seed, step, c->d_sc, ba, go, fs, c->dev
-      if (t_anneal >= 0) hipExtLaunchKernelGGL(k_anneal_bucket, dim3(nb), dim3(BK_AT), 0, st, c->ev0[t_anneal], c->ev1[t_anneal], 0, BUCKET_ARGS);
-      else hipLaunchKernelGGL(k_anneal_bucket, dim3(nb), dim3(BK_AT), 0, st, BUCKET_ARGS);
-#undef BUCKET_ARGS
-      c->bk_steps++;
-      c->head_offsets_done = (go.child_off != nullptr); c->head_offsets_bucket = true; c->head_offsets_split = false;
-      c->scount_B = ba.B; c->scount_buf = ba.kb ? c->head_kb_use : -1; c->scount_pos = c->pos_flip;
-    } else if (c->psit_on) { c->scount_B = 0; if (items <= 2) ANNEAL_LAUNCH_(2, 1); else ANNEAL_LAUNCH_(3, 1); }      // hf_to_psit: everything outside C(T); the C(T) segment is finished below
-    else if (anneal_split_ok(c, p, mode, nall, items, go.child_off != nullptr, use_mail)) {
-      // long lists: fold + round + a compaction inside every tile, a scan of the tiles' counts, then every tile to its place: no tile waits
-      // for the slowest tile in front of it (18.7 of a tile's 44 us at 10^6 walkers, tools/anneal_prof.py)
-      c->scount_B = 0;
-      const AnnealStage sg = c->stage;
-      if (t_anneal >= 0) hipEventRecord(c->ev0[t_anneal], st);
-      if (items == 3) hipLaunchKernelGGL((k_anneal<3, 0, 1>), dim3(nb), dim3(TPB), 0, st, ANNEAL_ARGS, sg);
-      else hipLaunchKernelGGL((k_anneal<4, 0, 1>), dim3(nb), dim3(TPB), 0, st, ANNEAL_ARGS, sg);
-      hipLaunchKernelGGL(k_anneal_split_scan, dim3((nb + 4 * TPB - 1) / (4 * TPB)), dim3(TPB), 0, st, (const u64 *)sg.cnt_a, (const u64 *)sg.cnt_b, sg.off_a, sg.off_b, (int)nb, c->d_sc);
-      if (items == 3) hipLaunchKernelGGL(k_anneal_place<3>, dim3(nb), dim3(TPB), 0, st, sg, c->m, c->d_loc_imp, (const u64 *)c->d_ct_hkey, (const u32 *)c->d_ct_hidx, c->ct_mask, (const double *)c->d_ct_num, (const double *)c->d_ct_den, c->d_partials, p, nb, go, (const DevScalars *)c->d_sc);
-      else hipLaunchKernelGGL(k_anneal_place<4>, dim3(nb), dim3(TPB), 0, st, sg, c->m, c->d_loc_imp, (const u64 *)c->d_ct_hkey, (const u32 *)c->d_ct_hidx, c->ct_mask, (const double *)c->d_ct_num, (const double *)c->d_ct_den, c->d_partials, p, nb, go, (const DevScalars *)c->d_sc);
-      if (t_anneal >= 0) hipEventRecord(c->ev1[t_anneal], st);
-      c->head_offsets_done = true; c->head_offsets_bucket = false; c->head_offsets_split = true;
-    }
-    else { c->scount_B = 0; if (items == 1) ANNEAL_LAUNCH(1); else if (items == 2) ANNEAL_LAUNCH(2); else if (items == 3) ANNEAL_LAUNCH(3); else ANNEAL_LAUNCH(4);
-           c->head_offsets_done = (go.child_off != nullptr); c->head_offsets_bucket = false; c->head_offsets_split = false; }
-#undef ANNEAL_LAUNCH_
-#undef ANNEAL_LAUNCH
-#undef ANNEAL_ARGS
-    if (fuse_gate && go.keys == c->d_keys_alt) { std::swap(c->d_keys, c->d_keys_alt); if (!c->pack) std::swap(c->d_vals, c->d_vals_alt); }      // the next step's spawn kernel appends its keys behind the walkers'
-    std::swap(c->w.up, c->m.up); std::swap(c->w.dn, c->m.dn); std::swap(c->w.wt, c->m.wt); std::swap(c->w.flg, c->m.flg);
-    std::swap(c->w.me, c->m.me); std::swap(c->w.en, c->m.en); std::swap(c->w.ed, c->m.ed); std::swap(c->w.irk, c->m.irk);
-    if (c->psit_on) {          // do_walk.f90:2394-2462, 2487, 2590-2598, 2701-2722 on the C(T) segment of the NEW list
-      if (c->psit_shard) { int rx = psit_shard_tinv(c, go.ps_raw); if (rx) return rx; }      // 2394-2442 over ranks: the T^-1 partials of all of them
-      TBEG(psit_fin, st);
-      hipLaunchKernelGGL(k_psit_finish, dim3(PSIT_FB), dim3(TPB), 0, st, c->psit, c->w.wt, c->w.flg, p, c->d_ps_part, go, seed);
-      TEND(psit_fin, st);
-    }
-  } else {
-    TBEG(merge, st);
-    hipLaunchKernelGGL(k_merge, dim3(nbm), dim3(TPB), 0, st, c->w, c->m, skey, perm, c->d_flags, c->d_wabs_part, n0, nall, p, c->invalid_key, c->pack);
-    device_excl_scan_u64(c->d_flags, c->d_pos, nall, &c->d_sc->tot1, sw[1], st);
-    TEND(merge, st);
-    TBEG(round, st);
-    const bool serial_join = getenv("SQMC_SERIAL_JOIN") != nullptr;      // read per call: the one-lane k_join (REPLAY's kernel) on a COUNTER walk, for tests
-    if (mode == SQMC_RNG_COUNTER && !serial_join) {
-      // the arrays of the rounding pass behind it are idle: the chunks' candidates (|w|, draw key | index) and their counts go there
-      const unsigned nchunks = (unsigned)((nall + JP_TILE - 1) / JP_TILE);
-      hipLaunchKernelGGL(k_join_gather, dim3(nchunks), dim3(TPB), 0, st, c->m, c->d_flags, c->d_pos, nall, p, (double *)c->d_flags2, c->d_pos2, c->d_jcnt);
-      hipLaunchKernelGGL(k_join_par, dim3(2), dim3(JP_T), 0, st, c->m, (const double *)c->d_flags2, (const u64 *)c->d_pos2, (const u32 *)c->d_jcnt, nall, p, seed, step);
-    }
-    else hipLaunchKernelGGL(k_join, dim3(1), dim3(TPB), 0, st, c->m, c->d_flags, c->d_pos, nall, p, mode, seed, step, c->d_sc);
-    hipLaunchKernelGGL(k_round, dim3(nblk(nall)), dim3(TPB), 0, st, c->m, c->d_flags, c->d_pos, c->d_flags2, nall, p, mode, seed, step, c->d_sc, skey, c->pack);
-    device_excl_scan_u64(c->d_flags2, c->d_pos2, nall, &c->d_sc->tot2, sw[2], st);
-    TEND(round, st);
-    nb = std::min(nblk(nall), 2048);
-    TBEG(compact, st);
-    hipLaunchKernelGGL(k_compact, dim3(nb), dim3(TPB), 0, st, c->m, c->w, c->d_flags2, c->d_pos2, c->d_loc_imp, skey, c->d_ct_hkey, c->d_ct_hidx, c->ct_mask,
-                       c->d_ct_num, c->d_ct_den, nall, p, c->d_partials, c->pack);
-    TEND(compact, st);
+}
+// 3. join the side streams: from here on weights are read.  The step takes its mail's sequence number here, behind the last early return
+// that leaves the step untouched.
+static int tail_join(sqmc_gpu_ctx *c, TailPlan &t, bool join_side_stream) {
+  hipStream_t st = c->st;
+  if (join_side_stream) { HIPCHK(hipStreamWaitEvent(st, c->e_join, 0)); if (t.p.semi && !c->d_grow && !getenv("SQMC_NO_ST3")) HIPCHK(hipStreamWaitEvent(st, c->e_join3, 0)); }
+  t.nbm = nblk(t.nall);
+  t.use_mail = (c->comm == nullptr);          // with a communicator the sums are all-reduced on the device first
+  t.seq = ++c->mail_seq;
+  return SQMC_OK;
+}
+// 4a. semistochastic annihilation, what the kernel fuses: one kernel goes from the sorted list to the new walker arrays, and on
+// pipelined steps does the next step's gate, child offsets and parent hints on the way
+static void anneal_plan(sqmc_gpu_ctx *c, TailPlan &t) {
+  const StepP &p = t.p; const long long nall = t.nall; const int mode = t.mode; const u64 step = t.step;
+  const bool bucket = t.bucket, use_mail = t.use_mail; const BucketArgs &ba = t.ba; u64 *const skey = t.skey;
+  int &items = t.items, &nb = t.nb, &n_ft = t.n_ft; bool &fuse_gate = t.fuse_gate; GateOut &go = t.go;
+  static const int items_env = getenv("SQMC_ANNEAL_ITEMS") ? atoi(getenv("SQMC_ANNEAL_ITEMS")) : 0;
+  // small lists want many tiles, large ones short look-back chains; 4 slots per thread spill 31 registers at the 4 waves per SIMD
+  // the kernel wants (3: 8), which only pays from ~10^7 slots on (measured: 0.449 against 0.458 ms/step at 2.5e6 slots, 3.44 against 3.35 at 1.7e7)
+  items = items_env ? items_env : (nall < (1ll << 20) ? 2 : (nall < (1ll << 23) ? 3 : 4));
+  if (items < 3 && getenv("SQMC_ANNEAL_SPLIT_MIN") && nall >= atoll(getenv("SQMC_ANNEAL_SPLIT_MIN"))) items = 3;      // (tests: the two-kernel form exists for 3 and 4 slots per thread)
+  if (c->psit_on) items = items <= 2 ? 2 : 3;          // the two shapes k_anneal<., 1> is instantiated with
+  nb = n_ft = bucket ? ba.B : (int)((nall + (long long)TPB * items - 1) / ((long long)TPB * items));
+  if (!bucket) c->lt_items = items;
+  // pipelined steps: the kernel also does the next step's gate (keys, child counts, child weights) as it places a walker
+  static const bool no_fuse = getenv("SQMC_NO_GATE_FUSION") != nullptr;
+  static const bool no_psit_fuse = getenv("SQMC_PSIT_NO_GATE_FUSION") != nullptr;
+  static const bool no_wide_fuse = getenv("SQMC_NO_WIDE_KEY_GATE_FUSION") != nullptr;      // keys wider than 32 bits (the electron gas): fused as well, the slot index in its own array
+  fuse_gate = c->pipeline_next && (c->pack || (!c->psit_on && !no_wide_fuse && !bucket)) && !no_fuse && !(c->psit_on && no_psit_fuse);
+  if (c->psit_on) { go.ps_of = c->d_ps_of; go.ps_raw = c->d_ps_raw; }
+  if (fuse_gate) {
+    go.on = 1; go.keys = (skey == c->d_keys) ? c->d_keys_alt : c->d_keys;      // never the buffer the kernel reads its sorted words from
+    go.vals = (skey == c->d_keys) ? c->d_vals_alt : c->d_vals; go.pack = c->pack;
+    go.nchild = c->d_nchild; go.wchild = c->d_wchild; go.cutoff = p.cutoff; go.step_next = step + 1;
+    static const bool no_off = getenv("SQMC_BUCKET_NO_OFFSETS") != nullptr;
+    static const bool no_shard_off = getenv("SQMC_SHARD_NO_OFFSETS") != nullptr;
+    if (bucket && (use_mail || !no_shard_off) && !no_off && c->n_imp < (1ll << 18) && c->last_wabs > 0 && c->last_wabs < 4.0e6) go.child_off = c->d_child_off;     // 24 bits of the look-back word hold the children
+    // the radix tail of an unsharded pipelined step carries the child offsets too, in a look-back of their own (walk_kernels.h)
+    static const bool no_roff = getenv("SQMC_RADIX_NO_OFFSETS") != nullptr;
+    if (!bucket && use_mail && !c->d_grow && mode == SQMC_RNG_COUNTER && !no_roff && !c->psit_on) go.child_off = c->d_child_off;      // (hf_to_psit: the C(T) segment's counts come from a later kernel: the head scans)
+    static const bool no_hint = getenv("SQMC_NO_PARENT_HINT") != nullptr;
+    if (go.child_off && use_mail && !c->d_grow && !no_hint) go.bpar = c->d_bpar;
   }
+  c->head_bpar_ok = go.bpar != nullptr;
+}
+extern "C++" {      // (templates cannot have the C linkage of the block around them)
+// one launch; with an event pair it is timed by the kernel's own start/stop timestamps
+template <auto Kern, typename... A> static inline void launch_timed(dim3 grid, dim3 block, hipStream_t st, hipEvent_t e0, hipEvent_t e1, const A &... a) {
+  if (e0) hipExtLaunchKernelGGL(Kern, grid, block, 0, st, e0, e1, 0, a...);
+  else hipLaunchKernelGGL(Kern, grid, block, 0, st, a...);
+}
+// k_anneal over the whole sorted list: I slots per thread, P: the hf_to_psit form, S: the first kernel of the two-kernel form (staging into sg)
+template <int I, int P, int S> static void launch_k_anneal(sqmc_gpu_ctx *c, const TailPlan &t, hipEvent_t e0, hipEvent_t e1, const AnnealStage &sg) {
+  launch_timed<k_anneal<I, P, S>>(dim3(t.nb), dim3(TPB), c->st, e0, e1, c->w, c->m, t.skey, t.perm, c->d_loc_imp, c->d_ct_hkey, c->d_ct_hidx, c->ct_mask, c->d_ct_num, c->d_ct_den,
+                                  c->d_partials, c->d_wabs_part, t.n0, t.nall, t.p, c->invalid_key, c->pack, t.mode, t.seed, t.step, c->d_sc, c->d_fstate, c->d_fstate + c->cap_ftiles,
+                                  c->d_fticket, t.go, sg);
+}
+// the second kernel of the two-kernel form: every tile of the staging buffer to its place
+template <int I> static void launch_anneal_place(sqmc_gpu_ctx *c, const TailPlan &t, const AnnealStage &sg) {
+  hipLaunchKernelGGL(k_anneal_place<I>, dim3(t.nb), dim3(TPB), 0, c->st, sg, c->m, c->d_loc_imp, (const u64 *)c->d_ct_hkey, (const u32 *)c->d_ct_hidx, c->ct_mask, (const double *)c->d_ct_num,
+                     (const double *)c->d_ct_den, c->d_partials, t.p, t.nb, t.go, (const DevScalars *)c->d_sc);
+}
+}
+// the short-list tail: one block per key range; with `fs.on` it does death/clone and the deterministic projection too
+static void launch_anneal_bucket(sqmc_gpu_ctx *c, const TailPlan &t, const FusedSide &fs, hipEvent_t e0, hipEvent_t e1) {
+  launch_timed<k_anneal_bucket>(dim3(t.nb), dim3(BK_AT), c->st, e0, e1, c->w, c->m, (const u64 *)c->d_keys, c->d_loc_imp, c->d_ct_hkey, c->d_ct_hidx, c->ct_mask, c->d_ct_num, c->d_ct_den,
+                                c->d_partials, c->d_wabs_part, t.n0, t.nall - t.n0, t.p, c->invalid_key, t.seed, t.step, c->d_sc, t.ba, t.go, fs, c->dev);
+}
+// 4b. semistochastic annihilation, the launch: one of four forms, each with its book-keeping for the next head; the buffers swap roles afterwards.
+// Timed by the kernel's own start/stop timestamps (hipExtLaunchKernelGGL events) at every timing level: the per-launch time bench.py
+// reports for the roofline of this, the longest kernel on the critical path
+static int anneal_launch(sqmc_gpu_ctx *c, TailPlan &t) {
+  const StepP &p = t.p; hipStream_t st = c->st; const int items = t.items; const GateOut &go = t.go;
+  int t_anneal = -1;
+  if (kernel_events_on(c, t.step) && c->nt < NTIMERS) { t_anneal = c->nt++; c->tname[t_anneal] = "anneal"; }
+  hipEvent_t e0 = t_anneal >= 0 ? c->ev0[t_anneal] : nullptr, e1 = t_anneal >= 0 ? c->ev1[t_anneal] : nullptr;
+  if (t.bucket) {
+    FusedSide fs; memset(&fs, 0, sizeof(fs));
+    fs.on = c->side_pending ? 1 : 0; fs.y = c->d_prj_y;
+    fs.x_in = c->d_prj_xs[c->xs_cur]; fs.x_out = c->d_prj_xs[c->xs_cur ^ 1];
+    static const bool no_fs = getenv("SQMC_NO_FUSED_SIDE") != nullptr;
+    if (c->pipeline_next && p.semi && !no_fs) c->head_prj_x = fs.x_out;      // the head enqueued below may multiply the projector into it
+    launch_anneal_bucket(c, t, fs, e0, e1);
+    c->bk_steps++;
+    c->head_offsets_done = (go.child_off != nullptr); c->head_offsets_bucket = true; c->head_offsets_split = false;
+    c->scount_B = t.ba.B; c->scount_buf = t.ba.kb ? c->head_kb_use : -1; c->scount_pos = c->pos_flip;
+  } else if (c->psit_on) {      // hf_to_psit: everything outside C(T); the C(T) segment is finished below
+    c->scount_B = 0;
+    if (items <= 2) launch_k_anneal<2, 1, 0>(c, t, e0, e1, AnnealStage{}); else launch_k_anneal<3, 1, 0>(c, t, e0, e1, AnnealStage{});
+  } else if (anneal_split_ok(c, p, t.mode, t.nall, items, go.child_off != nullptr, t.use_mail)) {
+    // long lists: fold + round + a compaction inside every tile, a scan of the tiles' counts, then every tile to its place: no tile waits
+    // for the slowest tile in front of it (18.7 of a tile's 44 us at 10^6 walkers, tools/anneal_prof.py)
+    c->scount_B = 0;
+    const AnnealStage sg = c->stage; const int nb = t.nb;
+    if (e0) hipEventRecord(e0, st);
+    if (items == 3) launch_k_anneal<3, 0, 1>(c, t, nullptr, nullptr, sg); else launch_k_anneal<4, 0, 1>(c, t, nullptr, nullptr, sg);
+    hipLaunchKernelGGL(k_anneal_split_scan, dim3((nb + 4 * TPB - 1) / (4 * TPB)), dim3(TPB), 0, st, (const u64 *)sg.cnt_a, (const u64 *)sg.cnt_b, sg.off_a, sg.off_b, (int)nb, c->d_sc);
+    if (items == 3) launch_anneal_place<3>(c, t, sg); else launch_anneal_place<4>(c, t, sg);
+    if (e0) hipEventRecord(e1, st);
+    c->head_offsets_done = true; c->head_offsets_bucket = false; c->head_offsets_split = true;
+  } else {
+    c->scount_B = 0;
+    if (items == 1) launch_k_anneal<1, 0, 0>(c, t, e0, e1, AnnealStage{}); else if (items == 2) launch_k_anneal<2, 0, 0>(c, t, e0, e1, AnnealStage{});
+    else if (items == 3) launch_k_anneal<3, 0, 0>(c, t, e0, e1, AnnealStage{}); else launch_k_anneal<4, 0, 0>(c, t, e0, e1, AnnealStage{});
+    c->head_offsets_done = (go.child_off != nullptr); c->head_offsets_bucket = false; c->head_offsets_split = false;
+  }
+  if (t.fuse_gate && go.keys == c->d_keys_alt) { std::swap(c->d_keys, c->d_keys_alt); if (!c->pack) std::swap(c->d_vals, c->d_vals_alt); }      // the next step's spawn kernel appends its keys behind the walkers'
+  swap_walk_buffers(c);
+  if (c->psit_on) {          // do_walk.f90:2394-2462, 2487, 2590-2598, 2701-2722 on the C(T) segment of the NEW list
+    if (c->psit_shard) { int rx = psit_shard_tinv(c, go.ps_raw); if (rx) return rx; }      // 2394-2442 over ranks: the T^-1 partials of all of them
+    TBEG(psit_fin, st);
+    hipLaunchKernelGGL(k_psit_finish, dim3(PSIT_FB), dim3(TPB), 0, st, c->psit, c->w.wt, c->w.flg, p, c->d_ps_part, go, t.seed);
+    TEND(psit_fin, st);
+  }
+  return SQMC_OK;
+}
+// 5. the plain walk's chain: merge equal determinants, join the small weights, round, compact
+static void tail_plain_chain(sqmc_gpu_ctx *c, TailPlan &t) {
+  const StepP &p = t.p; const long long n0 = t.n0, nall = t.nall; const int mode = t.mode, nbm = t.nbm; const u64 seed = t.seed, step = t.step;
+  hipStream_t st = c->st; u64 *const skey = t.skey; u32 *const perm = t.perm; int &nb = t.nb;
+  ScanWork sw[3];
+  for (int q = 0; q < 3; q++) { sw[q].state = c->d_scan_state + q * c->cap_tiles; sw[q].ticket = c->d_scan_ticket + q; sw[q].cap_tiles = c->cap_tiles; sw[q].self_clear = false; }
+  TBEG(merge, st);
+  hipLaunchKernelGGL(k_merge, dim3(nbm), dim3(TPB), 0, st, c->w, c->m, skey, perm, c->d_flags, c->d_wabs_part, n0, nall, p, c->invalid_key, c->pack);
+  device_excl_scan_u64(c->d_flags, c->d_pos, nall, &c->d_sc->tot1, sw[1], st);
+  TEND(merge, st);
+  TBEG(round, st);
+  const bool serial_join = getenv("SQMC_SERIAL_JOIN") != nullptr;      // read per call: the one-lane k_join (REPLAY's kernel) on a COUNTER walk, for tests
+  if (mode == SQMC_RNG_COUNTER && !serial_join) {
+    // the arrays of the rounding pass behind it are idle: the chunks' candidates (|w|, draw key | index) and their counts go there
+    const unsigned nchunks = (unsigned)((nall + JP_TILE - 1) / JP_TILE);
+    hipLaunchKernelGGL(k_join_gather, dim3(nchunks), dim3(TPB), 0, st, c->m, c->d_flags, c->d_pos, nall, p, (double *)c->d_flags2, c->d_pos2, c->d_jcnt);
+    hipLaunchKernelGGL(k_join_par, dim3(2), dim3(JP_T), 0, st, c->m, (const double *)c->d_flags2, (const u64 *)c->d_pos2, (const u32 *)c->d_jcnt, nall, p, seed, step);
+  }
+  else hipLaunchKernelGGL(k_join, dim3(1), dim3(TPB), 0, st, c->m, c->d_flags, c->d_pos, nall, p, mode, seed, step, c->d_sc);
+  hipLaunchKernelGGL(k_round, dim3(nblk(nall)), dim3(TPB), 0, st, c->m, c->d_flags, c->d_pos, c->d_flags2, nall, p, mode, seed, step, c->d_sc, skey, c->pack);
+  device_excl_scan_u64(c->d_flags2, c->d_pos2, nall, &c->d_sc->tot2, sw[2], st);
+  TEND(round, st);
+  nb = std::min(nblk(nall), 2048);
+  TBEG(compact, st);
+  hipLaunchKernelGGL(k_compact, dim3(nb), dim3(TPB), 0, st, c->m, c->w, c->d_flags2, c->d_pos2, c->d_loc_imp, skey, c->d_ct_hkey, c->d_ct_hidx, c->ct_mask,
+                     c->d_ct_num, c->d_ct_den, nall, p, c->d_partials, c->pack);
+  TEND(compact, st);
+}
+// 6. the final sums, the mail and the next step's head: who adds the partials up (k_finish, the next gate's first block, or the sharded
+// head's gather kernel), who posts the mail, and what the head enqueued here is told about this tail
+static int tail_sums_and_head(sqmc_gpu_ctx *c, TailPlan &t) {
+  const StepP &p = t.p; const long long n0 = t.n0, nall = t.nall; const int mode = t.mode, nb = t.nb, nbm = t.nbm, n_ft = t.n_ft; const u64 step = t.step, seq = t.seq;
+  const bool bucket = t.bucket, use_mail = t.use_mail, fuse_gate = t.fuse_gate; hipStream_t st = c->st;
   FinArgs fa;
   fa.partials = c->d_partials; fa.nblocks = nb; fa.wabs_part = c->d_wabs_part; fa.nwabs = p.semi ? nb : nbm; fa.mode = mode;
   fa.scan_state = c->d_scan_state; fa.scan_ticket = c->d_scan_ticket; fa.n_scan_words = (int)(3 * c->cap_tiles);
@@ -1441,66 +1496,74 @@ static int step_tail_impl(sqmc_gpu_ctx *c, const StepP &p_in, long long n0, long
     if (rh) return rh;
     c->head_ready = true; c->head_p = p;
   }
-  {
-    int wr = wait_mail(&c->h_mail->seq, seq, st);
-    if (wr > 0) return fail(SQMC_ERR_HIP, std::string("step failed on the device: ") + hipGetErrorString((hipError_t)wr));
-    if (wr < 0) {            // stream drained without the mail: read the scalars the slow way
-      HIPCHK(hipMemcpy(c->h_sc, c->d_sc, sizeof(DevScalars), hipMemcpyDeviceToHost));
-    } else { c->h_sc->tot2 = c->h_mail->tot2; c->h_sc->err = (int)c->h_mail->err; for (int i = 0; i < 16; i++) c->h_sc->stats[i] = c->h_mail->stats[i];
-             c->h_sc->retry = (int)c->h_mail->retry; c->h_sc->bk_fill = (unsigned int)c->h_mail->bk_fill; }
-  }
-  const bool stop_now = !use_mail && c->h_sc->err != 0;      // a collective stop outranks a re-run: every rank returns the status, none reduces again
-  if (bucket && !use_mail && !stop_now && (c->h_sc->retry & 2) && !(c->h_sc->retry & 1)) {
+  return SQMC_OK;
+}
+// 7. receive: wait for the mail and take the step's sums from it
+static int tail_receive(sqmc_gpu_ctx *c, TailPlan &t) {
+  hipStream_t st = c->st;
+  int wr = wait_mail(&c->h_mail->seq, t.seq, st);
+  if (wr > 0) return mail_fail(wr);
+  if (wr < 0) HIPCHK(hipMemcpy(c->h_sc, c->d_sc, sizeof(DevScalars), hipMemcpyDeviceToHost));      // stream drained without the mail: read the scalars the slow way
+  else take_mail(c, 16, true);
+  t.stop_now = !t.use_mail && c->h_sc->err != 0;      // a collective stop outranks a re-run: every rank returns the status, none reduces again
+  if (t.bucket && !t.use_mail && !t.stop_now && (c->h_sc->retry & 2) && !(c->h_sc->retry & 1)) {
     // In-library sharded step: ANOTHER rank's bucket tail gave up.  The sums that were just all-reduced contain its unfinished ones:
     // every rank reduces once more after that rank has re-run its tail -- this rank contributes the same local sums again (redl).
     const u64 tot2_first = c->h_sc->tot2; double loc[16]; for (int i = 0; i < 16; i++) loc[i] = c->h_sc->stats[i];
     int rr = comm_allreduce_stats(c); if (rr) return rr;
     const u64 seq2 = ++c->mail_seq;
     hipLaunchKernelGGL(k_post_mail, dim3(1), dim3(64), 0, st, c->d_sc, c->d_mail, seq2);
-    int wr = wait_mail(&c->h_mail->seq, seq2, st);
-    if (wr > 0) return fail(SQMC_ERR_HIP, std::string("step failed on the device: ") + hipGetErrorString((hipError_t)wr));
+    wr = wait_mail(&c->h_mail->seq, seq2, st);
+    if (wr > 0) return mail_fail(wr);
     if (wr < 0) HIPCHK(hipMemcpy(c->h_sc, c->d_sc, sizeof(DevScalars), hipMemcpyDeviceToHost));
-    else { c->h_sc->err = (int)c->h_mail->err; for (int i = 0; i < 7; i++) c->h_sc->stats[i] = c->h_mail->stats[i]; }
+    else take_mail(c, 7, false);
     for (int i = 7; i < 16; i++) c->h_sc->stats[i] = loc[i];          // the local figures and the walker counts are this rank's own, from its own (valid) tail:
     c->h_sc->tot2 = tot2_first; c->h_sc->retry = 0;                    // the head enqueued behind it has cleared the device copies since
     c->shard_y_ok = false; c->shard_x_ready = false;                   // ... and its projection used weights the other rank had not finished: the step redoes it
-    { static const int hold = getenv("SQMC_BUCKET_HOLDOFF") ? atoi(getenv("SQMC_BUCKET_HOLDOFF")) : 8; c->bk_holdoff = hold; }
+    c->bk_holdoff = bucket_holdoff_steps();
   }
-  if (bucket && !stop_now) {
-    if (c->h_sc->retry & 1) {
-      // A bucket outgrew its block.  The kernel wrote only the other walker buffer and scratch; the head of the next step,
-      // if it was enqueued, saw the flag and did nothing.  Undo the host's bookkeeping and let the caller run the radix tail.
-      drop_head(c);
-      hipStreamSynchronize(st);
-      hipMemset(c->d_fstate, 0, 2 * c->cap_ftiles * 8); hipMemset(c->d_fticket, 0, 4);
-      hipMemset(&c->d_sc->retry, 0, sizeof(int)); hipMemset(&c->d_sc->bk_fill, 0, sizeof(unsigned int));
-      c->h_sc->retry = 0;
-      std::swap(c->w.up, c->m.up); std::swap(c->w.dn, c->m.dn); std::swap(c->w.wt, c->m.wt); std::swap(c->w.flg, c->m.flg);
-      std::swap(c->w.me, c->m.me); std::swap(c->w.en, c->m.en); std::swap(c->w.ed, c->m.ed); std::swap(c->w.irk, c->m.irk);
-      if (fuse_gate) std::swap(c->d_keys, c->d_keys_alt);
-      c->pipeline_next = false; c->bk_retries++; c->head_offsets_done = false; c->shard_y_ok = false; c->shard_x_ready = false;
-      // The boundaries are learnt anew -- from this attempt: every bucket left its count of spawns, also the ones that gave up (with
-      // equal-residents boundaries the spawn-rich key ranges hold 4x the mean), and the list they were counted in is the input again.
-      static const bool no_learn = getenv("SQMC_BUCKET_NO_RETRY_LEARN") != nullptr;
-      const int B_failed = c->scount_B, set_failed = c->scount_buf;
-      bool learnt = false;
-      if (!no_learn && !c->d_grow && c->comm == nullptr && B_failed > 0 && B_failed <= BK_REBAL_MAXB && n0 >= 16ll * B_failed && !ba.force_retry) {
-        BucketArgs rb; memset(&rb, 0, sizeof(rb));
-        int out = 0; while (out == set_failed) out++;
-        rb.B = B_failed; rb.scount = c->d_bscount;
-        rb.kb_prev = set_failed >= 0 ? c->d_bkb + set_failed * (BK_MAXB + 1) : (const u32 *)nullptr;
-        rb.pos_prev = set_failed >= 0 ? c->d_bpos + c->scount_pos * (BK_MAXB + 1) : (const u32 *)nullptr;
-        rb.kb_out = c->d_bkb + out * (BK_MAXB + 1); rb.hint_out = c->d_bhint + out * (BK_MAXB + 1);
-        hipLaunchKernelGGL(k_bucket_boundaries, dim3(2), dim3(BK_T), 0, st, (const u64 *)c->d_keys, n0, rb);
-        c->kb_B[0] = c->kb_B[1] = c->kb_B[2] = 0; c->kb_B[out] = B_failed; c->kb_next = out; learnt = true;
-      } else { c->kb_B[0] = c->kb_B[1] = c->kb_B[2] = 0; c->kb_next = -1; }
-      c->scount_B = 0; c->scount_buf = -1;
-      { static const int hold = getenv("SQMC_BUCKET_HOLDOFF") ? atoi(getenv("SQMC_BUCKET_HOLDOFF")) : 8; c->bk_holdoff = (learnt && set_failed < 0) ? 1 : hold; }
-      return SQMC_INTERNAL_RETRY;
-    }
+  return SQMC_OK;
+}
+// 8. bucket roll-back.  A bucket outgrew its block.  The kernel wrote only the other walker buffer and scratch; the head of the next step,
+// if it was enqueued, saw the flag and did nothing.  Undo the host's bookkeeping and let the caller run the radix tail.
+static int tail_rollback(sqmc_gpu_ctx *c, TailPlan &t) {
+  if (!t.bucket || t.stop_now) return SQMC_OK;
+  if (!(c->h_sc->retry & 1)) {
     if (c->h_sc->bk_fill > 850) c->bk_holdoff = 4;         // thin head-room: radix tail for a few steps
+    return SQMC_OK;
   }
-  c->timers_pending = kernel_events_on(c, step);
+  hipStream_t st = c->st; const long long n0 = t.n0;
+  drop_head(c);
+  hipStreamSynchronize(st);
+  hipMemset(c->d_fstate, 0, 2 * c->cap_ftiles * 8); hipMemset(c->d_fticket, 0, 4);
+  hipMemset(&c->d_sc->retry, 0, sizeof(int)); hipMemset(&c->d_sc->bk_fill, 0, sizeof(unsigned int));
+  c->h_sc->retry = 0;
+  swap_walk_buffers(c);
+  if (t.fuse_gate) std::swap(c->d_keys, c->d_keys_alt);
+  c->pipeline_next = false; c->bk_retries++; c->head_offsets_done = false; c->shard_y_ok = false; c->shard_x_ready = false;
+  // The boundaries are learnt anew -- from this attempt: every bucket left its count of spawns, also the ones that gave up (with
+  // equal-residents boundaries the spawn-rich key ranges hold 4x the mean), and the list they were counted in is the input again.
+  static const bool no_learn = getenv("SQMC_BUCKET_NO_RETRY_LEARN") != nullptr;
+  const int B_failed = c->scount_B, set_failed = c->scount_buf;
+  bool learnt = false;
+  if (!no_learn && !c->d_grow && c->comm == nullptr && B_failed > 0 && B_failed <= BK_REBAL_MAXB && n0 >= 16ll * B_failed && !t.ba.force_retry) {
+    BucketArgs rb; memset(&rb, 0, sizeof(rb));
+    int out = 0; while (out == set_failed) out++;
+    rb.B = B_failed; rb.scount = c->d_bscount;
+    rb.kb_prev = set_failed >= 0 ? c->d_bkb + set_failed * (BK_MAXB + 1) : (const u32 *)nullptr;
+    rb.pos_prev = set_failed >= 0 ? c->d_bpos + c->scount_pos * (BK_MAXB + 1) : (const u32 *)nullptr;
+    rb.kb_out = c->d_bkb + out * (BK_MAXB + 1); rb.hint_out = c->d_bhint + out * (BK_MAXB + 1);
+    hipLaunchKernelGGL(k_bucket_boundaries, dim3(2), dim3(BK_T), 0, st, (const u64 *)c->d_keys, n0, rb);
+    c->kb_B[0] = c->kb_B[1] = c->kb_B[2] = 0; c->kb_B[out] = B_failed; c->kb_next = out; learnt = true;
+  } else { c->kb_B[0] = c->kb_B[1] = c->kb_B[2] = 0; c->kb_next = -1; }
+  c->scount_B = 0; c->scount_buf = -1;
+  c->bk_holdoff = (learnt && set_failed < 0) ? 1 : bucket_holdoff_steps();
+  return SQMC_INTERNAL_RETRY;
+}
+// 9. commit the step
+static int tail_commit(sqmc_gpu_ctx *c, const TailPlan &t, double out[16]) {
+  const StepP &p = t.p;
+  c->timers_pending = kernel_events_on(c, t.step);
   c->step_no++;
   if (c->h_sc->err) {          // raised on the device (sharded in-library steps: by any rank, all-reduced)
     drop_head(c);
@@ -1510,13 +1573,31 @@ static int step_tail_impl(sqmc_gpu_ctx *c, const StepP &p_in, long long n0, long
   }
   const long long nfinal = (long long)(c->h_sc->tot2 & 0xFFFFFFFFull), nimp = (long long)(c->h_sc->tot2 >> 32);
   c->nwalk = nfinal; c->residents_sorted = true;
-  if (bucket && p.semi) { c->xs_cur ^= 1; c->xs_valid = true; } else c->xs_valid = false;
+  if (t.bucket && p.semi) { c->xs_cur ^= 1; c->xs_valid = true; } else c->xs_valid = false;
   c->side_pending = false;
   for (int i = 0; i < 16; i++) out[i] = c->h_sc->stats[i];
   c->last_wabs = out[1];
   if (nfinal == 0) { drop_head(c); return fail(SQMC_ERR_NO_WALKERS, "my_nwalk=0"); }
   if (p.semi && nimp != (c->shard_n > 1 || c->d_grow ? c->n_imp_local : c->n_imp)) { drop_head(c); return fail(SQMC_ERR_IMP_BROKEN, "locations of my imp broken"); }
   return SQMC_OK;
+}
+static int step_tail_impl(sqmc_gpu_ctx *c, const StepP &p_in, long long n0, long long nall, bool join_side_stream, double out[16], bool allow_bucket) {
+  TailPlan t{};
+  t.p = p_in; t.p.nimp_cap = c->d_loc_imp ? (int)std::max<long long>(c->n_imp_local, c->n_imp) : 0;     // what set_projector / shard_config allocated
+  t.n0 = n0; t.nall = nall; t.mode = c->rng_mode; t.seed = c->seed64; t.step = c->step_no;
+  hipStream_t st = c->st;
+  int r;
+  TBEG(sort, st);          // (brackets the partition of a bucket tail too)
+  if ((r = tail_choose(c, t, allow_bucket))) return r;
+  tail_sort(c, t);
+  TEND(sort, st);
+  if ((r = tail_join(c, t, join_side_stream))) return r;
+  if (t.p.semi) { anneal_plan(c, t); if ((r = anneal_launch(c, t))) return r; }
+  else tail_plain_chain(c, t);
+  if ((r = tail_sums_and_head(c, t))) return r;
+  if ((r = tail_receive(c, t))) return r;
+  if ((r = tail_rollback(c, t))) return r;          // SQMC_INTERNAL_RETRY: the caller runs the radix tail on the same input
+  return tail_commit(c, t, out);
 }
 
 static int step_tail(sqmc_gpu_ctx *c, const StepP &p, long long n0, long long nall, bool join_side_stream, double out[16]) {
@@ -1611,7 +1692,7 @@ int sqmc_gpu_step(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double out[16]) {
   long long nch;
   if (M > n0) {
     int wr = wait_mail(&c->h_mail->cnt_seq, cseq, st);
-    if (wr > 0) return fail(SQMC_ERR_HIP, std::string("step failed on the device: ") + hipGetErrorString((hipError_t)wr));
+    if (wr > 0) return mail_fail(wr);
     if (wr < 0) { u64 v; HIPCHK(hipMemcpy(&v, &c->d_sc->n_children, 8, hipMemcpyDeviceToHost)); nch = (long long)v; }
     else nch = (long long)c->h_mail->n_children;
   } else { u64 v; HIPCHK(hipMemcpyAsync(&v, &c->d_sc->n_children, 8, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st)); nch = (long long)v; }
