@@ -159,12 +159,9 @@ static int shard_begin_impl(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double 
   if (!sp->semistochastic && (c->n_imp > 0 || c->n_imp_local > 0)) return fail(SQMC_ERR_BAD_ARG, "sharded plain walk: no projector may be set (sqmc_gpu_shard_config with no rows)");
   if (c->mwalk <= 0) return fail(SQMC_ERR_BAD_ARG, "no walker arrays");
   hipStream_t st = c->st;
-  StepP p; p.tau = sp->tau; p.e_trial = sp->e_trial; p.rfi = sp->reweight_factor_inv; p.r_init = sp->r_initiator; p.min_wt = sp->min_wt;
-  p.cutoff = sp->always_spawn_cutoff_wt; p.ipow = sp->initiator_power; p.imind = sp->initiator_min_distance; p.cti = sp->c_t_initiator;
-  p.semi = sp->semistochastic; p.reached = sp->reached_w_abs_gen;
+  const StepP p = step_params(c, sp);
   if (c->psit_on) {
     if (!sp->semistochastic) return fail(SQMC_ERR_BAD_ARG, "hf_to_psit needs a semistochastic step");
-    p.koff = c->dev.ps.koff; p.nct = c->dev.ps.n_ct;
     if (c->nwalk < p.nct) return fail(SQMC_ERR_BAD_ARG, "hf_to_psit: the walker list does not hold this rank's C(T) share");
   }
   const long long n0 = c->nwalk, M = c->mwalk;
@@ -188,13 +185,7 @@ static int shard_begin_impl(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double 
   if (c->head_ready) {
     // gate + scan + spawn of this step already run behind the last step's mail (pipelined head of sqmc_gpu_shard_run);
     // with one stream they simply sit in front of this step's death/clone and projection in stream order
-    c->head_ready = false;
-    const StepP &h = c->head_p;
-    if (n0 <= 0 || M <= n0 || h.tau != p.tau || h.cutoff != p.cutoff || h.semi != p.semi || h.cti != p.cti) {
-      hipStreamSynchronize(st);
-      return fail(SQMC_ERR_BAD_ARG, "internal: the pipelined head of this sharded step does not fit it");
-    }
-    cseq = c->head_cseq;
+    int rt = take_head(c, n0 > 0 && M > n0 && head_fits(c->head_p, p), "internal: the pipelined head of this sharded step does not fit it", -1, -1, &cseq); if (rt) return rt;
     if (spawn_events_on(c, c->step_no, p.semi) && c->nt < NTIMERS) { const int t = c->nt++; c->tname[t] = "spawn"; std::swap(c->ev0[t], c->hev[2]); std::swap(c->ev1[t], c->hev[3]); }
   } else {
     cseq = ++c->cnt_seq;
@@ -208,8 +199,7 @@ static int shard_begin_impl(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double 
     if (n0 > 0) {
       TBEG(spawn, st);
       if (M > n0)      // first: it posts the child count to the host mailbox as soon as it starts
-        SPAWN_LAUNCH(spawn_kind(c), 0, spawn_diag(c), dim3(nblk(M - n0)), dim3(TPB), 0, st, c->dev, c->w, c->d_child_off, c->d_wchild, c->d_child_state, c->d_keys, c->d_vals,
-                           n0, M, p, c->rng_mode, c->seed64, c->step_no, c->invalid_key, (const DevScalars *)c->d_sc, c->d_mail, cseq, c->pack, 0, shard_owner_out(c), BucketArgs{}, FinArgs{}, PrjPre{}, 0);
+        launch_spawn(c, spawn_kind(c), 0, (unsigned)nblk(M - n0), 0, nullptr, nullptr, p, c->step_no, n0, cseq, 0, shard_owner_out(c), BucketArgs{}, FinArgs{}, PrjPre{}, 0);
       TEND(spawn, st);
     }
   }
@@ -257,7 +247,7 @@ static int shard_begin_impl(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double 
   if (full_sync) HIPCHK(hipStreamSynchronize(st));      // the caller's collective library reads x_global on its own stream
   const long long spc = c->dev.hb.on ? 2 : 1;          // walker slots per child (fast_heatbath: two), as in sqmc_gpu_step
   if (n0 + spc * nch > M) {      // (k_spawn checked the same on the device and wrote nothing, a pipelined head's included)
-    hipMemset(c->d_scan_state, 0, 3 * c->cap_tiles * 8); hipMemset(c->d_scan_ticket, 0, 3 * 4);
+    reset_scan_words(c);
     return fail(SQMC_ERR_MWALK, "nwalk>MWALK");
   }
   c->shard_n0 = n0; c->shard_nch = nch; c->shard_nslot = spc * nch;
@@ -327,13 +317,10 @@ static int shard_finish_impl(sqmc_gpu_ctx *c, const sqmc_step_params *sp, const 
                              const u64 *self_rec = nullptr, long long self_lo = 0, long long self_hi = 0) {
   if (!c || !sp || !out || n_recv < 0) return fail(SQMC_ERR_BAD_ARG, "bad argument");
   hipStream_t st = c->st;
-  StepP p; p.tau = sp->tau; p.e_trial = sp->e_trial; p.rfi = sp->reweight_factor_inv; p.r_init = sp->r_initiator; p.min_wt = sp->min_wt;
-  p.cutoff = sp->always_spawn_cutoff_wt; p.ipow = sp->initiator_power; p.imind = sp->initiator_min_distance; p.cti = sp->c_t_initiator;
-  p.semi = sp->semistochastic; p.reached = sp->reached_w_abs_gen;
-  if (c->psit_on) { p.koff = c->dev.ps.koff; p.nct = c->dev.ps.n_ct; }
+  const StepP p = step_params(c, sp);
   const long long n0 = c->shard_n0;
   if (n0 + n_recv > c->mwalk) {
-    hipMemset(c->d_scan_state, 0, 3 * c->cap_tiles * 8); hipMemset(c->d_scan_ticket, 0, 3 * 4);
+    reset_scan_words(c);
     return fail(SQMC_ERR_MWALK, "nwalk>MWALK");
   }
   if (n_recv > 0)
@@ -341,7 +328,7 @@ static int shard_finish_impl(sqmc_gpu_ctx *c, const sqmc_step_params *sp, const 
   if (n0 + n_recv == 0) {           // an empty shard stays empty this step
     if (join) HIPCHK(hipStreamWaitEvent(st, c->e_join, 0));
     for (int i = 0; i < 16; i++) out[i] = 0.0;
-    hipMemset(c->d_scan_state, 0, 3 * c->cap_tiles * 8); hipMemset(c->d_scan_ticket, 0, 3 * 4);
+    reset_scan_words(c);
     if (c->psit_shard) {            // still a party to the exchange of the T^-1 partials: nothing to add
       HIPCHK(hipMemsetAsync(c->d_ps_tx, 0, (c->shard_n + 1) * 8, st));
       int rx = psit_shard_exchange(c); if (rx) return rx;
@@ -352,10 +339,9 @@ static int shard_finish_impl(sqmc_gpu_ctx *c, const sqmc_step_params *sp, const 
       // The collectives of the ranks that hold walkers, in their order: the sums; the coming step's deterministic weights in front of
       // the pipelined head (enqueued before anybody has read the sums); the sums once more if some rank's bucket tail gave up and re-ran.
       const bool head_x = c->pipeline_next && !c->comm2 && c->n_imp > 0 && p.semi;
-      static const bool two_calls = getenv("SQMC_SHARD_SPLIT_ALLREDUCE") != nullptr;
       c->shard_x_ready = false; c->shard_y_ok = false;
       for (int round = 0; round < 2; round++) {
-        if (round == 0 && head_x && !two_calls) {          // one call carries both
+        if (round == 0 && head_x && !shard_split_allreduce()) {          // one call carries both
           int rp = shard_head_project(c, true, true); if (rp) return rp;
           HIPCHK(hipMemcpyAsync(c->h_sc->red, c->d_xg + c->n_imp, 8 * 8, hipMemcpyDeviceToHost, st));
         } else {
@@ -607,7 +593,7 @@ static int shard_step_impl(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double o
   }
   if (gstat) {
     hipStreamSynchronize(st); if (side || diag_side) hipStreamSynchronize(c->st2);
-    hipMemset(c->d_scan_state, 0, 3 * c->cap_tiles * 8); hipMemset(c->d_scan_ticket, 0, 3 * 4);
+    reset_scan_words(c);
     if (local == gstat) return fail(gstat, local_msg.empty() ? g_err : local_msg);
     return fail(gstat, gstat == SQMC_ERR_MWALK ? "nwalk>MWALK (on some rank)" : "another rank stopped the step");
   }
@@ -710,11 +696,8 @@ int sqmc_gpu_set_hf_to_psit_shard(sqmc_gpu_ctx *c, int64_t n_ct_local, const int
 static int psit_shard_project(sqmc_gpu_ctx *c, const sqmc_step_params *sp, const double *xg) {
   hipStream_t st = c->st;
   const PsitArgs &a = c->psit;
-  if (c->n_imp_local > 0) {
-    PrjPre pp; memset(&pp, 0, sizeof(pp));
-    pp.n_imp = (int)c->n_imp_local; pp.ptr = c->d_prj_ptr; pp.col = c->d_prj_col; pp.val = c->d_prj_val; pp.x = xg; pp.y = a.dw_imp; pp.grow = c->d_grow;
-    hipLaunchKernelGGL(k_psit_imp_rows, dim3(nblk(c->n_imp_local, TPB / 64)), dim3(TPB), 0, st, pp);
-  }
+  if (c->n_imp_local > 0)
+    hipLaunchKernelGGL(k_psit_imp_rows, dim3(nblk(c->n_imp_local, TPB / 64)), dim3(TPB), 0, st, prj_pre(c, xg, a.dw_imp, true));
   if (a.n_ct > 0) hipLaunchKernelGGL(k_psit_ct_col, dim3(nblk(a.n_ct)), dim3(TPB), 0, st, a, (const double *)c->w.wt, xg);
   hipLaunchKernelGGL(k_psit_rows_fin_shard, dim3(1), dim3(TPB), 0, st, a, xg, sp->tau, sp->e_trial);
   if (a.n_ct > 0) hipLaunchKernelGGL(k_psit_apply, dim3(nblk(a.n_ct)), dim3(TPB), 0, st, a, c->w.wt, sp->tau, sp->e_trial);

@@ -266,6 +266,12 @@ static void abandon_head(sqmc_gpu_ctx *c);
 static void psit_off(sqmc_gpu_ctx *c);
 static int shard_head_project(sqmc_gpu_ctx *c, bool with_sums, bool empty, const FinArgs *fin = nullptr);      // abi_shard.inc
 static int psit_shard_tinv(sqmc_gpu_ctx *c, const double *ps_raw);                                               // abi_shard.inc
+// the three look-back sets of the scans (state words and tickets) back to zero: at allocation, and wherever a step ends before the finishing
+// block that re-zeroes them has run.  Both memsets are issued whatever the first returns; only the allocation looks at the result.
+static hipError_t reset_scan_words(sqmc_gpu_ctx *c) {
+  const hipError_t e0 = hipMemset(c->d_scan_state, 0, 3 * c->cap_tiles * 8), e1 = hipMemset(c->d_scan_ticket, 0, 3 * 4);
+  return e0 != hipSuccess ? e0 : e1;
+}
 
 
 #include "walk_kernels.h"
@@ -362,7 +368,7 @@ static int init_common(sqmc_gpu_ctx *c, int norb, int nup, int ndn, int rng_mode
     HIPCHK(hipMalloc(&c->d_flags2, M * 8)); HIPCHK(hipMalloc(&c->d_pos2, M * 8)); HIPCHK(hipMalloc(&c->d_jcnt, (M / 2048 + 2) * 4));
     c->cap_tiles = (M + SCAN_TILE - 1) / SCAN_TILE + 1;
     HIPCHK(hipMalloc(&c->d_scan_state, 3 * c->cap_tiles * 8)); HIPCHK(hipMalloc(&c->d_scan_ticket, 3 * 4));
-    HIPCHK(hipMemset(c->d_scan_state, 0, 3 * c->cap_tiles * 8)); HIPCHK(hipMemset(c->d_scan_ticket, 0, 3 * 4));
+    HIPCHK(reset_scan_words(c));
     c->cap_ftiles = std::max<long long>(nblk(M) + 1, BK_MAXB + 1);
     c->segoff_cap = ((std::min<long long>(M, 1ll << 20) + BK_T - 1) / BK_T + 1) * (BK_MAXB + 1);
     HIPCHK(hipMalloc(&c->d_segoff, c->segoff_cap * sizeof(unsigned short)));
@@ -961,11 +967,17 @@ static OwnerOut shard_owner_out(sqmc_gpu_ctx *c) {
   c->owner_ready = true;
   return OwnerOut{c->d_flags, (u32 *)c->d_flags2, c->shard_n, c->owner_mode};
 }
-// The head of a step: spawn gate + child offsets + k_spawn (COUNTER discipline).  With dev_n the
-// walker count is read on the device (sc->nwalk, written by k_finish of the step before) and n0 is
-// only an upper bound that sizes the grids: the pipelined launch behind k_finish of the previous
-// step, before the host has read that step's sums.  g0/g1 and s0/s1 (may be null) time gate+scan
-// and k_spawn; the child count goes to the host mailbox under sequence number *cseq.
+// the PrjPre of this context's projector: y = A x over all rows, or (sharded) over the rows this rank owns, row grow[i] of A into y[i]
+static PrjPre prj_pre(const sqmc_gpu_ctx *c, const double *x, double *y, bool sharded = false) {
+  PrjPre pp; memset(&pp, 0, sizeof(pp));
+  pp.n_imp = (int)(sharded ? c->n_imp_local : c->n_imp); pp.ptr = c->d_prj_ptr; pp.col = c->d_prj_col; pp.val = c->d_prj_val; pp.x = x; pp.y = y;
+  if (sharded) pp.grow = c->d_grow;
+  return pp;
+}
+// switches read once per process that more than one function asks for
+static inline long long merge_sort_min() { static const long long v = getenv("SQMC_MERGE_SORT_MIN") ? atoll(getenv("SQMC_MERGE_SORT_MIN")) : (1ll << 20); return v; }
+static inline bool no_fused_side() { static const bool v = getenv("SQMC_NO_FUSED_SIDE") != nullptr; return v; }
+static inline bool shard_split_allreduce() { static const bool v = getenv("SQMC_SHARD_SPLIT_ALLREDUCE") != nullptr; return v; }
 // what does not change from step to step about the short-list (bucket) tail
 static inline bool bucket_static_ok(const sqmc_gpu_ctx *c, const StepP &p) {
   static const int bucket_env = getenv("SQMC_ANNEAL_ITEMS") ? 0 : (getenv("SQMC_BUCKET") ? atoi(getenv("SQMC_BUCKET")) : 1);      // a forced tile shape asks for the radix tail's kernel
@@ -1000,38 +1012,53 @@ static inline long long bucket_count(long long nall) {
   if (B > conc && nall <= conc * (long long)(bk_target + bk_target / 4)) B = conc;
   return B < 1 ? 1 : (B > BK_MAXB ? BK_MAXB : B);
 }
-static int enqueue_head(sqmc_gpu_ctx *c, const StepP &p, u64 step, long long n0, bool dev_n, hipEvent_t g0, hipEvent_t g1, hipEvent_t s0, hipEvent_t s1, u64 *cseq,
-                        const FinArgs *fin = nullptr, bool gate_done = false) {
-  hipStream_t st = c->st;
-  const long long M = c->mwalk;
-  ScanWork sw0; sw0.state = c->d_scan_state; sw0.ticket = c->d_scan_ticket; sw0.cap_tiles = c->cap_tiles; sw0.self_clear = false;
-  FinArgs fa; memset(&fa, 0, sizeof(fa)); if (fin) fa = *fin;
-  if (g0) hipEventRecord(g0, st);
-  FinArgs spawn_fin; memset(&spawn_fin, 0, sizeof(spawn_fin));
-  PrjPre pp; memset(&pp, 0, sizeof(pp));
+// ---- The head of a step, stage by stage.  What the stages share is a HeadPlan on enqueue_head's stack, as the tail's share a
+// ---- TailPlan; nothing of it is stored in the context.  What the tail that enqueues a head tells it, and what a head leaves for the step
+// ---- and tail behind it, travels in context fields: each stage's comment names the ones it consumes and the ones it leaves.
+struct HeadPlan {
+  StepP p; u64 step; long long n0; bool dev_n; hipEvent_t g0, g1, s0, s1; bool gate_done; FinArgs fa;      // the inputs (fa: the finish that rides on this head, or all zero)
+  int offsets_producer;                                        // head_offsets: who wrote the child offsets (sqmc_gpu_debug_last_head)
+  PrjPre pp;                                                   // head_projection: the product k_spawn's spare blocks make (n_imp = 0: none)
+  FinArgs spawn_fin;                                           // head_offsets: the final sums k_spawn carries in one spare block
+  bool tail_fills, early; u64 *cseq; OwnerOut oo;              // head_fork_and_early_hii
+  BucketArgs hb; int hq_blk;                                   // head_partition
+  int spawn_fuse; size_t spawn_lds; int n_spare;               // head_spawn
+};
+// 1. the deterministic projection's matrix-vector part, for k_spawn's spare blocks.  In-library sharded step (one communicator): the
+// all-reduce of the deterministic weights needs nothing the host still has to decide either.  It goes in front of k_spawn, whose spare
+// blocks then multiply this rank's rows of the projector into the result; the step itself only adds the last line.  (Decided by
+// quantities every rank shares: the collectives keep their order.)  Unsharded, behind a bucket tail: that tail's deterministic weights,
+// row by row, are this step's x.  Consumes head_sums_ride, head_fin, head_prj_x; leaves head_y_done, shard_y_ok, shard_x_ready.
+static int head_projection(sqmc_gpu_ctx *c, HeadPlan &h) {
   c->head_y_done = false;
   c->shard_y_ok = false;
-  // who writes the child offsets this head's k_spawn searches: 0 k_gate + scan, 1 the fused gate + the scan that carries the final sums,
-  // 2 k_anneal's own look-back, 3 k_anneal_bucket, 4 k_anneal<., 0, 1> + k_anneal_place (5: k_replay_prepass, sqmc_gpu_step)
-  const int offsets_producer = !gate_done ? 0 : (!c->head_offsets_done ? 1 : (c->head_offsets_bucket ? 3 : (c->head_offsets_split ? 4 : 2)));
-  if (dev_n && c->d_grow && c->comm && !c->comm2 && c->n_imp > 0 && p.semi) {
-    // In-library sharded step (one communicator): the all-reduce of the deterministic weights needs nothing the host still has to
-    // decide either.  It goes in front of k_spawn, whose spare blocks then multiply this rank's rows of the projector into the
-    // result; the step itself only adds the last line.  (Decided by quantities every rank shares: the collectives keep their order.)
+  if (h.dev_n && c->d_grow && c->comm && !c->comm2 && c->n_imp > 0 && h.p.semi) {
     int rp = shard_head_project(c, c->head_sums_ride, false, c->head_sums_ride ? &c->head_fin : nullptr); if (rp) return rp;
-    pp.n_imp = (int)c->n_imp_local; pp.ptr = c->d_prj_ptr; pp.col = c->d_prj_col; pp.val = c->d_prj_val; pp.x = c->d_xg; pp.y = c->d_prj_y; pp.grow = c->d_grow;
+    h.pp = prj_pre(c, c->d_xg, c->d_prj_y, true);
     c->shard_y_ok = true; c->shard_x_ready = true;
   }
-  if (dev_n && c->head_prj_x && c->n_imp > 0 && !c->d_grow) {       // the tail that enqueues this head is a bucket tail: its deterministic weights, row by row, are this step's x
-    pp.n_imp = (int)c->n_imp; pp.ptr = c->d_prj_ptr; pp.col = c->d_prj_col; pp.val = c->d_prj_val; pp.x = c->head_prj_x; pp.y = c->d_prj_y;
+  if (h.dev_n && c->head_prj_x && c->n_imp > 0 && !c->d_grow) {
+    h.pp = prj_pre(c, c->head_prj_x, c->d_prj_y);
     c->head_y_done = true;
   }
   c->head_prj_x = nullptr;
+  return SQMC_OK;
+}
+// 2. the child offsets k_spawn searches, and who adds up the sums of the step before.  Three ways: they are there already (the tail wrote
+// them: the sums ride in k_spawn's spare block behind a bucket tail, else k_finish runs beside k_spawn on the side stream); the gate is
+// done (the scan carries the sums and works on look-back set scan_flip); neither (k_gate, which carries them, and the scan on set 0).
+// Consumes head_offsets_done/bucket/split; leaves scan_used[], scan_flip.
+static int head_offsets(sqmc_gpu_ctx *c, HeadPlan &h) {
+  hipStream_t st = c->st; const StepP &p = h.p; const u64 step = h.step; const long long n0 = h.n0; const bool dev_n = h.dev_n, gate_done = h.gate_done; const FinArgs &fa = h.fa;
+  ScanWork sw0; sw0.state = c->d_scan_state; sw0.ticket = c->d_scan_ticket; sw0.cap_tiles = c->cap_tiles; sw0.self_clear = false;
+  // who writes the child offsets this head's k_spawn searches: 0 k_gate + scan, 1 the fused gate + the scan that carries the final sums,
+  // 2 k_anneal's own look-back, 3 k_anneal_bucket, 4 k_anneal<., 0, 1> + k_anneal_place (5: k_replay_prepass, replay_head)
+  h.offsets_producer = !gate_done ? 0 : (!c->head_offsets_done ? 1 : (c->head_offsets_bucket ? 3 : (c->head_offsets_split ? 4 : 2)));
   if (gate_done && c->head_offsets_done) {
     // the bucket tail of the step before wrote keys, child weights, child OFFSETS and their total: nothing to scan.  That
     // step's final sums ride on k_spawn as one extra block.
     c->head_offsets_done = false;
-    if (c->head_offsets_bucket) spawn_fin = fa;
+    if (c->head_offsets_bucket) h.spawn_fin = fa;
     else if (fa.on) {
       // long lists: k_spawn keeps the registers and LDS of its plain form, and the one block that adds up thousands of tile partials
       // (20 us at 10^6 walkers, 80 at 10^7) runs BESIDE it on the side stream, as it ran beside the scan; the next tail joins that
@@ -1054,43 +1081,48 @@ static int enqueue_head(sqmc_gpu_ctx *c, const StepP &p, u64 step, long long n0,
     c->scan_used[0] = device_excl_scan_u64(c->d_nchild, c->d_child_off, n0, &c->d_sc->n_children, sw0, st, dev_n ? &c->d_sc->nwalk : nullptr, ScanNoExtra(), dev_n ? &c->d_sc->retry : nullptr);
     c->scan_flip = 1;          // set 0 stays dirty until a finish re-zeroes it: a gate-fused head that follows works on set 1
   }
-  if (g1) hipEventRecord(g1, st);
-  // ---- spawn goes out first: the host is the slower side at the start of a step, and k_spawn
-  //      is on the critical path (exactly one k_spawn launch inside this timer: the per-launch time
-  //      bench.py reports, taken from the kernel's own start/stop timestamps).  It is launched
-  //      over the whole free capacity with a device-side child count and posts that count to the
-  //      host mailbox as soon as it starts.
-  const bool tail_fills = dev_n && c->tail_fills_hii && !c->d_grow;
+  return SQMC_OK;
+}
+// 3. the fork for the side streams and, on pipelined heads, the early H_ii: the diagonal elements of the determinants the last step created
+// depend on nothing the host still has to decide: a kernel on the side stream computes them now, beside the scan and k_spawn; death/clone
+// later finds them cached.  (Doing this in spare blocks of k_spawn instead saves the cross-stream join but costs k_spawn its occupancy
+// through the extra LDS: 122 against 110 us per step at 10^5 walkers, and 35 % more spawn time at 10^6-10^7 -- taken out again.)
+// Behind a bucket tail there is nothing to fill: that kernel computes the H_ii of the determinants it creates, and the step runs on one
+// stream (no fork, no join: every cross-stream wait costs 5-12 us on the critical path at 10^5 walkers).  The child count's sequence
+// number and the owner keys' arrays are taken here, behind the fork, where they always were: nothing between here and k_spawn reads them.
+// Consumes tail_fills_hii; leaves fork_valid, head_hii, head_hii_joined, cnt_seq, owner_ready.
+static int head_fork_and_early_hii(sqmc_gpu_ctx *c, HeadPlan &h) {
+  const bool dev_n = h.dev_n;
+  const bool tail_fills = h.tail_fills = dev_n && c->tail_fills_hii && !c->d_grow;
   c->tail_fills_hii = false;
-  if (!tail_fills) HIPCHK(hipEventRecord(c->e_fork, st));
+  if (!tail_fills) HIPCHK(hipEventRecord(c->e_fork, c->st));
   c->fork_valid = !tail_fills;
-  // pipelined head: the diagonal elements of the determinants the last step created depend on nothing the host still has to
-  // decide: a kernel on the side stream computes them now, beside the scan and k_spawn; death/clone later finds them cached.
-  // (Doing this in spare blocks of k_spawn instead saves the cross-stream join but costs k_spawn its occupancy through the extra
-  // LDS: 122 against 110 us per step at 10^5 walkers, and 35 % more spawn time at 10^6-10^7 -- taken out again.)
   static const bool no_early = getenv("SQMC_NO_EARLY_HII") != nullptr;
-  // Behind a bucket tail there is nothing to fill: that kernel computes the H_ii of the determinants it creates, and the step
-  // runs on one stream (no fork, no join: every cross-stream wait costs 5-12 us on the critical path at 10^5 walkers).
   // (long lists: k_spawn and the sort are longer than both passes of k_diag together, and the early pass only takes resources from
   //  k_spawn -- 0.449 -> 0.444 ms at 10^6 walkers, 3.15 -> 3.10 ms at 10^7 without it)
-  const bool early = dev_n && !c->d_grow && !no_early && !tail_fills && c->last_nall < (1ll << 20);
+  const bool early = h.early = dev_n && !c->d_grow && !no_early && !tail_fills && c->last_nall < (1ll << 20);
   if (early) {
     HIPCHK(hipStreamWaitEvent(c->st2, c->e_fork, 0));
-    hipLaunchKernelGGL(k_diag, dim3(nblk(n0)), dim3(TPB), 0, c->st2, c->dev, c->w.up, c->w.dn, c->w.wt, c->w.flg, c->w.me, n0, p, c->d_sc, 1);
+    hipLaunchKernelGGL(k_diag, dim3(nblk(h.n0)), dim3(TPB), 0, c->st2, c->dev, c->w.up, c->w.dn, c->w.wt, c->w.flg, c->w.me, h.n0, h.p, c->d_sc, 1);
     HIPCHK(hipEventRecord(c->e_join, c->st2));          // a tail that does death/clone itself still has to wait for these
   }
   c->head_hii = early || tail_fills; c->head_hii_joined = tail_fills;
-  *cseq = ++c->cnt_seq;
-  const OwnerOut oo = shard_owner_out(c);
-  // short lists: k_spawn groups its children by key range as it emits them (the bucket tail then needs no partition kernel).
-  // The list's length is not known yet: the last step's sizes it; the tail checks that everything fitted before it relies on it.
-  BucketArgs hb; memset(&hb, 0, sizeof(hb));
+  *h.cseq = ++c->cnt_seq;
+  h.oo = shard_owner_out(c);
+  return SQMC_OK;
+}
+// 4. the partition k_spawn makes.  Short lists: k_spawn groups its children by key range as it emits them (the bucket tail then needs no
+// partition kernel).  The list's length is not known yet: the last step's sizes it; the tail checks that everything fitted before it
+// relies on it.  The tail takes over head_ba, the copy made BEFORE the parent hints and the H_ii queues are added: it describes the
+// partition only.  Consumes head_bpar_ok, hii_deferred_B (and the boundary sets through choose_boundaries); leaves head_kb_use, head_ba.
+static void head_partition(sqmc_gpu_ctx *c, HeadPlan &h) {
+  const bool dev_n = h.dev_n; const long long n0 = h.n0, M = c->mwalk;
+  BucketArgs &hb = h.hb; memset(&hb, 0, sizeof(hb));
   {
-    static const long long merge_min = getenv("SQMC_MERGE_SORT_MIN") ? atoll(getenv("SQMC_MERGE_SORT_MIN")) : (1ll << 20);
     static const bool no_fuse = getenv("SQMC_BUCKET_NO_SPAWN_FUSION") != nullptr;
     const long long n_known = dev_n ? c->nwalk : n0;                   // dev_n: the walkers of the step that is finishing, not of this one -- close
     const long long est = c->last_nall > 0 ? c->last_nall : 0;
-    if (!no_fuse && !c->d_grow && bucket_static_ok(c, p) && c->residents_sorted && c->bk_holdoff == 0 && est > 0 && est < merge_min && est < (1ll << 20) && n_known >= 256) {      // sharded steps: the children a rank anneals are not the ones it spawned
+    if (!no_fuse && !c->d_grow && bucket_static_ok(c, h.p) && c->residents_sorted && c->bk_holdoff == 0 && est > 0 && est < merge_sort_min() && est < (1ll << 20) && n_known >= 256) {      // sharded steps: the children a rank anneals are not the ones it spawned
       long long B = bucket_count(est); if (B > n_known / 2) B = n_known / 2;
       if (B >= 1) {
         hb.B = (int)B; hb.words = c->d_flags; hb.segoff = c->d_segoff; hb.state = c->d_fstate; hb.ticket = c->d_fticket;
@@ -1101,39 +1133,70 @@ static int enqueue_head(sqmc_gpu_ctx *c, const StepP &p, u64 step, long long n0,
     }
     c->head_ba = hb;
   }
-  if (gate_done && c->head_bpar_ok && dev_n) hb.parent_hint = c->d_bpar;      // the tail that enqueues this head wrote the child offsets and, beside them, every block's first parent
+  if (h.gate_done && c->head_bpar_ok && dev_n) hb.parent_hint = c->d_bpar;      // the tail that enqueues this head wrote the child offsets and, beside them, every block's first parent
   c->head_bpar_ok = false;
-  int hq_blk = 0;
-  if (dev_n && tail_fills && c->hii_deferred_B > 0) {      // the tail left the new determinants' H_ii to this kernel: one spare block per bucket's queue
-    hb.hq_cnt = c->d_hq_cnt; hb.hq_pos = c->d_hq_pos; hb.hq_B = c->hii_deferred_B; hb.hq_nblk = hq_blk = c->hii_deferred_B;
+  h.hq_blk = 0;
+  if (dev_n && h.tail_fills && c->hii_deferred_B > 0) {      // the tail left the new determinants' H_ii to this kernel: one spare block per bucket's queue
+    hb.hq_cnt = c->d_hq_cnt; hb.hq_pos = c->d_hq_pos; hb.hq_B = c->hii_deferred_B; hb.hq_nblk = h.hq_blk = c->hii_deferred_B;
     c->head_ba.hq_cnt = nullptr; c->head_ba.hq_pos = nullptr; c->head_ba.hq_nblk = 0;      // (the copy the tail takes over describes the partition only)
   }
   c->hii_deferred_B = 0;
-  const long long nfree = dev_n ? M : M - n0;          // dev_n: nothing is known about the count but that it is >= 0
-  const int spawn_fuse = (hb.B > 0 || spawn_fin.on || pp.n_imp > 0 || c->shard_y_ok || hq_blk > 0) ? 1 : 0;
-  const size_t spawn_lds = std::max<size_t>(hb.B > 0 ? (size_t)BK_PART_LDS(hb.B) : 0, hq_blk > 0 ? (size_t)(TPB / 16) * bk_hii_terms_of(c->htab.nup, c->htab.ndn) * 8 : 0);
+}
+// The one k_spawn launch there is (the only expansion of the SPAWN_LAUNCH macros): the proposal's form, plain or FUSE, with the diagnostics'
+// words or without; with an event pair it is timed by the kernel's own start/stop timestamps.  grid counts the spare blocks in.
+static void launch_spawn(sqmc_gpu_ctx *c, int kind, int fuse, unsigned grid, size_t lds, hipEvent_t e0, hipEvent_t e1, const StepP &p, u64 step, long long n0, u64 cseq, int dev_n,
+                         const OwnerOut &oo, const BucketArgs &hb, const FinArgs &fin, const PrjPre &pp, int n_spare) {
+  hipStream_t st = c->st; const long long M = c->mwalk;
+  if (e0)
+    SPAWN_LAUNCH_EXT(kind, fuse, spawn_diag(c), dim3(grid), dim3(TPB), lds, st, e0, e1, 0, c->dev, c->w, c->d_child_off, c->d_wchild,
+                          c->d_child_state, c->d_keys, c->d_vals, n0, M, p, c->rng_mode, c->seed64, step, c->invalid_key, (const DevScalars *)c->d_sc, c->d_mail, cseq, c->pack, dev_n, oo, hb, fin, pp, n_spare);
+  else
+    SPAWN_LAUNCH(kind, fuse, spawn_diag(c), dim3(grid), dim3(TPB), lds, st, c->dev, c->w, c->d_child_off, c->d_wchild, c->d_child_state, c->d_keys, c->d_vals,
+                       n0, M, p, c->rng_mode, c->seed64, step, c->invalid_key, (const DevScalars *)c->d_sc, c->d_mail, cseq, c->pack, dev_n, oo, hb, fin, pp, n_spare);
+}
+// 5. k_spawn.  It goes out first: the host is the slower side at the start of a step, and k_spawn is on the critical path (exactly one
+// k_spawn launch inside the s0/s1 timer: the per-launch time bench.py reports, taken from the kernel's own start/stop timestamps).  It
+// is launched over the whole free capacity with a device-side child count and posts that count to the host mailbox as soon as it starts.
+// Consumes shard_y_ok (this head's own); leaves nh[], spawned_valid.
+static int head_spawn(sqmc_gpu_ctx *c, HeadPlan &h) {
+  hipStream_t st = c->st; const bool dev_n = h.dev_n; const BucketArgs &hb = h.hb;
+  const long long nfree = dev_n ? c->mwalk : c->mwalk - h.n0;          // dev_n: nothing is known about the count but that it is >= 0
+  h.spawn_fuse = (hb.B > 0 || h.spawn_fin.on || h.pp.n_imp > 0 || c->shard_y_ok || h.hq_blk > 0) ? 1 : 0;
+  h.spawn_lds = std::max<size_t>(hb.B > 0 ? (size_t)BK_PART_LDS(hb.B) : 0, h.hq_blk > 0 ? (size_t)(TPB / 16) * bk_hii_terms_of(c->htab.nup, c->htab.ndn) * 8 : 0);
   // the blocks in front of the spawning ones (k_spawn): final sums, one per H_ii queue, eight projector rows each, the boundaries' one or two
-  const int n_spare = (spawn_fin.on ? 1 : 0) + hq_blk + (pp.n_imp > 0 ? nblk(prj_row_waves(pp.n_imp), TPB / 64) : 0) + bk_boundary_blocks(hb);
-  c->nh[0] = dev_n ? 1 : 0; c->nh[1] = offsets_producer; c->nh[2] = hb.parent_hint ? 1 : 0;
-  c->nh[3] = (spawn_kind(c) != SPAWN_UNIFORM || spawn_fuse) ? 1 : 0; c->nh[4] = n_spare; c->nh[5] = spawn_kind(c);      // (SPAWN_LAUNCH_K: every proposal but the uniform one has the FUSE form only)
-  if (nfree > 0) {
-    if (s0)
-      SPAWN_LAUNCH_EXT(spawn_kind(c), spawn_fuse, spawn_diag(c), dim3((unsigned)(nblk(nfree) + n_spare)), dim3(TPB), spawn_lds, st, s0, s1, 0, c->dev, c->w, c->d_child_off, c->d_wchild,
-                            c->d_child_state, c->d_keys, c->d_vals, n0, M, p, c->rng_mode, c->seed64, step, c->invalid_key, (const DevScalars *)c->d_sc, c->d_mail, *cseq, c->pack, dev_n ? 1 : 0, oo, hb, spawn_fin, pp, n_spare);
-    else
-      SPAWN_LAUNCH(spawn_kind(c), spawn_fuse, spawn_diag(c), dim3((unsigned)(nblk(nfree) + n_spare)), dim3(TPB), spawn_lds, st, c->dev, c->w, c->d_child_off, c->d_wchild, c->d_child_state, c->d_keys, c->d_vals,
-                         n0, M, p, c->rng_mode, c->seed64, step, c->invalid_key, (const DevScalars *)c->d_sc, c->d_mail, *cseq, c->pack, dev_n ? 1 : 0, oo, hb, spawn_fin, pp, n_spare);
-  } else if (s0) { hipEventRecord(s0, st); hipEventRecord(s1, st); }
+  h.n_spare = (h.spawn_fin.on ? 1 : 0) + h.hq_blk + (h.pp.n_imp > 0 ? nblk(prj_row_waves(h.pp.n_imp), TPB / 64) : 0) + bk_boundary_blocks(hb);
+  c->nh[0] = dev_n ? 1 : 0; c->nh[1] = h.offsets_producer; c->nh[2] = hb.parent_hint ? 1 : 0;
+  c->nh[3] = (spawn_kind(c) != SPAWN_UNIFORM || h.spawn_fuse) ? 1 : 0; c->nh[4] = h.n_spare; c->nh[5] = spawn_kind(c);      // (SPAWN_LAUNCH_K: every proposal but the uniform one has the FUSE form only)
+  if (nfree > 0)
+    launch_spawn(c, spawn_kind(c), h.spawn_fuse, (unsigned)(nblk(nfree) + h.n_spare), h.spawn_lds, h.s0, h.s1, h.p, h.step, h.n0, *h.cseq, dev_n ? 1 : 0, h.oo, hb, h.spawn_fin, h.pp, h.n_spare);
+  else if (h.s0) { hipEventRecord(h.s0, st); hipEventRecord(h.s1, st); }
   HIPCHK(hipEventRecord(c->e_spawned, st)); c->spawned_valid = true;
   HIPCHK(hipGetLastError());
   return SQMC_OK;
+}
+// The head of a step: spawn gate + child offsets + k_spawn (COUNTER discipline).  With dev_n the walker count is read on the device
+// (sc->nwalk, written by k_finish of the step before) and n0 is only an upper bound that sizes the grids: the pipelined launch behind
+// k_finish of the previous step, before the host has read that step's sums.  g0/g1 and s0/s1 (may be null) time everything in front of
+// the fork (projection, gate, scan) and k_spawn; the child count goes to the host mailbox under sequence number *cseq.
+static int enqueue_head(sqmc_gpu_ctx *c, const StepP &p, u64 step, long long n0, bool dev_n, hipEvent_t g0, hipEvent_t g1, hipEvent_t s0, hipEvent_t s1, u64 *cseq,
+                        const FinArgs *fin = nullptr, bool gate_done = false) {
+  HeadPlan h{};
+  h.p = p; h.step = step; h.n0 = n0; h.dev_n = dev_n; h.g0 = g0; h.g1 = g1; h.s0 = s0; h.s1 = s1; h.cseq = cseq; h.gate_done = gate_done; if (fin) h.fa = *fin;
+  int r;
+  if (g0) hipEventRecord(g0, c->st);
+  if ((r = head_projection(c, h))) return r;
+  if ((r = head_offsets(c, h))) return r;
+  if (g1) hipEventRecord(g1, c->st);
+  if ((r = head_fork_and_early_hii(c, h))) return r;
+  head_partition(c, h);
+  return head_spawn(c, h);
 }
 // a pipelined head whose step will not run (the step before it failed): drain it and reset what it touched
 static void drop_head(sqmc_gpu_ctx *c) {
   if (!c->head_ready) return;
   c->head_ready = false;
   hipStreamSynchronize(c->st); hipStreamSynchronize(c->st2);
-  hipMemset(c->d_scan_state, 0, 3 * c->cap_tiles * 8); hipMemset(c->d_scan_ticket, 0, 3 * 4);
+  reset_scan_words(c);
   c->scan_used[0] = c->scan_used[1] = 0;
 }
 static void abandon_head(sqmc_gpu_ctx *c) {
@@ -1170,9 +1233,7 @@ static int launch_side_kernels(sqmc_gpu_ctx *c, const StepP &p, long long n0, bo
     // the transformed projector over C(T), the Psi_T locations; then the three updates slot by slot in the reference's order
     PsitArgs &a = c->psit;
     hipLaunchKernelGGL(k_prj_gather, dim3(nblk(c->n_imp)), dim3(TPB), 0, st3, c->w.wt, c->d_loc_imp, c->d_prj_x, c->n_imp);
-    PrjPre pp; memset(&pp, 0, sizeof(pp));
-    pp.n_imp = (int)c->n_imp; pp.ptr = c->d_prj_ptr; pp.col = c->d_prj_col; pp.val = c->d_prj_val; pp.x = c->d_prj_x; pp.y = a.dw_imp;
-    hipLaunchKernelGGL(k_psit_imp_rows, dim3(nblk(c->n_imp, TPB / 64)), dim3(TPB), 0, st3, pp);
+    hipLaunchKernelGGL(k_psit_imp_rows, dim3(nblk(c->n_imp, TPB / 64)), dim3(TPB), 0, st3, prj_pre(c, c->d_prj_x, a.dw_imp));
     hipLaunchKernelGGL(k_psit_ct_col, dim3(nblk(a.n_ct)), dim3(TPB), 0, st3, a, (const double *)c->w.wt, (const double *)c->w.wt);
     hipLaunchKernelGGL(k_psit_ct_terms, dim3((unsigned)((a.n_ct + 4095) / 4096)), dim3(64), 0, st3, a, (const double *)c->w.wt);
     hipLaunchKernelGGL(k_psit_rows_fin, dim3(1), dim3(TPB), 0, st3, a, (const double *)c->w.wt, p.tau, p.e_trial);
@@ -1222,7 +1283,6 @@ struct TailPlan {
   int items, nb, n_ft; bool fuse_gate; GateOut go;             // anneal_plan (a plain walk's nb: tail_plain_chain)
   bool stop_now;                                               // tail_receive: a collective stop outranks the bucket tail's re-run
 };
-static inline long long merge_sort_min() { static const long long v = getenv("SQMC_MERGE_SORT_MIN") ? atoll(getenv("SQMC_MERGE_SORT_MIN")) : (1ll << 20); return v; }
 static inline int bucket_holdoff_steps() { static const int hold = getenv("SQMC_BUCKET_HOLDOFF") ? atoi(getenv("SQMC_BUCKET_HOLDOFF")) : 8; return hold; }
 static inline void swap_walk_buffers(sqmc_gpu_ctx *c) {
   std::swap(c->w.up, c->m.up); std::swap(c->w.dn, c->m.dn); std::swap(c->w.wt, c->m.wt); std::swap(c->w.flg, c->m.flg);
@@ -1385,8 +1445,7 @@ static int anneal_launch(sqmc_gpu_ctx *c, TailPlan &t) {
     FusedSide fs; memset(&fs, 0, sizeof(fs));
     fs.on = c->side_pending ? 1 : 0; fs.y = c->d_prj_y;
     fs.x_in = c->d_prj_xs[c->xs_cur]; fs.x_out = c->d_prj_xs[c->xs_cur ^ 1];
-    static const bool no_fs = getenv("SQMC_NO_FUSED_SIDE") != nullptr;
-    if (c->pipeline_next && p.semi && !no_fs) c->head_prj_x = fs.x_out;      // the head enqueued below may multiply the projector into it
+    if (c->pipeline_next && p.semi && !no_fused_side()) c->head_prj_x = fs.x_out;      // the head enqueued below may multiply the projector into it
     launch_anneal_bucket(c, t, fs, e0, e1);
     c->bk_steps++;
     c->head_offsets_done = (go.child_off != nullptr); c->head_offsets_bucket = true; c->head_offsets_split = false;
@@ -1472,8 +1531,7 @@ static int tail_sums_and_head(sqmc_gpu_ctx *c, TailPlan &t) {
   // Sharded in-library step: do_walk.f90:2778-2790, the sums every rank needs.  In a pipelined run with one communicator the next
   // step's deterministic weights are all-reduced straight behind them (enqueue_head): one call carries both, and the kernel that
   // gathers the weights does the final sums in its first block (decided by quantities all ranks share)
-  static const bool two_calls = getenv("SQMC_SHARD_SPLIT_ALLREDUCE") != nullptr;
-  c->head_sums_ride = !use_mail && c->pipeline_next && c->d_grow && !c->comm2 && c->n_imp > 0 && p.semi && !two_calls;
+  c->head_sums_ride = !use_mail && c->pipeline_next && c->d_grow && !c->comm2 && c->n_imp > 0 && p.semi && !shard_split_allreduce();
   TBEG(estimate, st);
   if (c->head_sums_ride) c->head_fin = fa;
   else if (!fin_in_gate) hipLaunchKernelGGL(k_finish, dim3(1), dim3(TPB), 0, st, fa, c->d_sc);
@@ -1606,104 +1664,115 @@ static int step_tail(sqmc_gpu_ctx *c, const StepP &p, long long n0, long long na
   return r;
 }
 
+// ---- One step from the host's side: the pieces sqmc_gpu_step is made of; the sharded step and sqmc_gpu_annihilate share some.
+// the device copy of the caller's parameters, with the hf_to_psit key offset and segment length; what a door refuses stays at the door
+static StepP step_params(const sqmc_gpu_ctx *c, const sqmc_step_params *sp) {
+  StepP p; p.tau = sp->tau; p.e_trial = sp->e_trial; p.rfi = sp->reweight_factor_inv; p.r_init = sp->r_initiator; p.min_wt = sp->min_wt;
+  p.cutoff = sp->always_spawn_cutoff_wt; p.ipow = sp->initiator_power; p.imind = sp->initiator_min_distance; p.cti = sp->c_t_initiator;
+  p.semi = sp->semistochastic; p.reached = sp->reached_w_abs_gen;
+  if (c->psit_on) { p.koff = c->dev.ps.koff; p.nct = c->dev.ps.n_ct; }
+  return p;
+}
+// was the enqueued head launched with the parameters this step comes with?  (the ones gate, scan and spawn depend on)
+static inline bool head_fits(const StepP &h, const StepP &p) { return h.tau == p.tau && h.cutoff == p.cutoff && h.semi == p.semi && h.cti == p.cti; }
+// a host that calls step by step (the reference's own loop does work between steps) and has promised to come back with the
+// same tau and cutoff (sqmc_gpu_set_chained_runs): this step enqueues the next one's head, as the steps of sqmc_gpu_run do
+// (run_steps decides for its own steps, by a rule of its own)
+static void step_pipeline_decision(sqmc_gpu_ctx *c, const sqmc_step_params *sp) {
+  if (!c->in_run) c->pipeline_next = c->chained_runs && sp->reached_w_abs_gen == 2 && c->rng_mode != SQMC_RNG_REPLAY && !getenv("SQMC_NO_PIPELINE");
+  static const bool psit_no_pipe = getenv("SQMC_PSIT_NO_PIPELINE") != nullptr;      // hf_to_psit: the head (gate, scan, spawn) behind the tail like any other step's; the gate stays a kernel of its own
+  if (c->psit_on && psit_no_pipe) c->pipeline_next = false;
+  if (c->sdiag_on) c->pipeline_next = false;      // spawn diagnostics: a head enqueued ahead would count proposals of a step that may never be returned
+}
+// gate + scan + spawn of this step already run behind k_finish of the last one (pipelined head): they only depend on parameters that are
+// constant once the target population has been reached.  The step takes the head's mail number and, for the timers it has (slots or
+// -1), the events the head was timed with.  Consumes head_ready, head_cseq, hev[].
+static int take_head(sqmc_gpu_ctx *c, bool fits, const char *misfit, int t_gate_scan, int t_spawn, u64 *cseq) {
+  c->head_ready = false;
+  if (!fits) { hipStreamSynchronize(c->st); return fail(SQMC_ERR_BAD_ARG, misfit); }
+  *cseq = c->head_cseq;
+  if (t_gate_scan >= 0) { std::swap(c->ev0[t_gate_scan], c->hev[0]); std::swap(c->ev1[t_gate_scan], c->hev[1]); }
+  if (t_spawn >= 0) { std::swap(c->ev0[t_spawn], c->hev[2]); std::swap(c->ev1[t_spawn], c->hev[3]); }
+  return SQMC_OK;
+}
+// the head of a REPLAY step: gate and child offsets on one lane (the kernel also clears the step's device scalars), the fork, the plain
+// k_spawn.  Leaves fork_valid, cnt_seq, nh[].
+static int replay_head(sqmc_gpu_ctx *c, const StepP &p, u64 step, long long n0, int t_gate_scan, int t_spawn, u64 *cseq) {
+  hipStream_t st = c->st; const long long M = c->mwalk;
+  if (t_gate_scan >= 0) hipEventRecord(c->ev0[t_gate_scan], st);
+  hipLaunchKernelGGL(k_replay_prepass, dim3(1), dim3(64), 0, st, c->d_tab, c->w.up, c->w.dn, c->w.wt, c->d_nchild, c->d_wchild, c->d_child_off,
+                     c->d_child_state, n0, (M - n0) / (c->dev.hb.on ? 2 : 1), p, c->d_sc, c->dev);
+  if (t_gate_scan >= 0) hipEventRecord(c->ev1[t_gate_scan], st);
+  HIPCHK(hipEventRecord(c->e_fork, st)); c->fork_valid = true;
+  *cseq = ++c->cnt_seq;
+  c->nh[0] = 0; c->nh[1] = 5; c->nh[2] = 0; c->nh[3] = spawn_kind(c) != SPAWN_UNIFORM ? 1 : 0; c->nh[4] = 0; c->nh[5] = spawn_kind(c);
+  if (M > n0)
+    launch_spawn(c, spawn_kind(c), 0, (unsigned)nblk(M - n0), 0, t_spawn >= 0 ? c->ev0[t_spawn] : nullptr, t_spawn >= 0 ? c->ev1[t_spawn] : nullptr, p, step, n0, *cseq, 0,
+                 OwnerOut{nullptr, nullptr, 0, 0}, BucketArgs{}, FinArgs{}, PrjPre{}, 0);
+  else if (t_spawn >= 0) { hipEventRecord(c->ev0[t_spawn], st); hipEventRecord(c->ev1[t_spawn], st); }
+  return SQMC_OK;
+}
+// death/clone and the deterministic projection: side streams beside spawn + sort -- or nothing at all here when the bucket tail is going
+// to do them itself (pipelined steps whose missing H_ii the head already filled and whose deterministic weights the last bucket tail
+// left row by row).  Consumes head_hii, head_y_done, head_ba.B (read only), xs_valid; leaves side_pending, head_hii_joined.
+static int step_side_kernels(sqmc_gpu_ctx *c, const StepP &p, long long n0, bool from_head) {
+  c->side_pending = !no_fused_side() && from_head && c->head_hii && c->head_y_done && c->xs_valid && p.semi && bucket_static_ok(c, p) && c->bk_holdoff == 0 && c->head_ba.B > 0;
+  c->head_hii = false;
+  if (!c->side_pending) c->head_hii_joined = false;
+  return c->side_pending ? SQMC_OK : launch_side_kernels(c, p, n0, false);
+}
+// the child count, from the mailbox (or the slow way when there was no k_spawn launch), and the check that the children fit
+static int step_child_count(sqmc_gpu_ctx *c, long long n0, u64 cseq, long long *nch) {
+  hipStream_t st = c->st; const long long M = c->mwalk;
+  if (M > n0) {
+    int wr = wait_mail(&c->h_mail->cnt_seq, cseq, st);
+    if (wr > 0) return mail_fail(wr);
+    if (wr < 0) { u64 v; HIPCHK(hipMemcpy(&v, &c->d_sc->n_children, 8, hipMemcpyDeviceToHost)); *nch = (long long)v; }
+    else *nch = (long long)c->h_mail->n_children;
+  } else { u64 v; HIPCHK(hipMemcpyAsync(&v, &c->d_sc->n_children, 8, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st)); *nch = (long long)v; }
+  const long long spc = c->dev.hb.on ? 2 : 1;          // walker slots per child (fast_heatbath: two)
+  if (n0 + spc * *nch > M) {
+    hipStreamSynchronize(st); hipStreamSynchronize(c->st2); hipStreamSynchronize(c->st3);
+    reset_scan_words(c);
+    return fail(SQMC_ERR_MWALK, "nwalk>MWALK");
+  }
+  return SQMC_OK;
+}
 int sqmc_gpu_step(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double out[16]) {
   if (!c || !sp || !out) return fail(SQMC_ERR_BAD_ARG, "null argument");
   if (c->mwalk <= 0 || c->nwalk <= 0) return fail(SQMC_ERR_NO_WALKERS, "my_nwalk=0");
   if (c->d_grow) return fail(SQMC_ERR_BAD_ARG, "context is configured for sharded steps: use sqmc_gpu_shard_begin/pack/finish");
   if (sp->semistochastic && (c->n_imp <= 0 || !c->d_prj_ptr)) return fail(SQMC_ERR_BAD_ARG, "semistochastic step without projector");
   if (!c->d_ct_up) return fail(SQMC_ERR_BAD_ARG, "C(T) table not set");
-  hipStream_t st = c->st;
-  StepP p; p.tau = sp->tau; p.e_trial = sp->e_trial; p.rfi = sp->reweight_factor_inv; p.r_init = sp->r_initiator; p.min_wt = sp->min_wt;
-  p.cutoff = sp->always_spawn_cutoff_wt; p.ipow = sp->initiator_power; p.imind = sp->initiator_min_distance; p.cti = sp->c_t_initiator;
-  p.semi = sp->semistochastic; p.reached = sp->reached_w_abs_gen;
+  const StepP p = step_params(c, sp);
   if (c->psit_on) {
     if (!sp->semistochastic) return fail(SQMC_ERR_BAD_ARG, "hf_to_psit needs a semistochastic step");
     if (c->dev.hb.on) return fail(SQMC_ERR_UNSUPPORTED, "hf_to_psit with proposal_method fast_heatbath is not built");
     if (c->dev.cs.on) return fail(SQMC_ERR_UNSUPPORTED, "hf_to_psit with proposal_method CauchySchwarz is not built");
-    p.koff = c->dev.ps.koff; p.nct = c->dev.ps.n_ct;
     if (c->nwalk < p.nct) return fail(SQMC_ERR_BAD_ARG, "hf_to_psit: the walker list does not hold the C(T) segment");
   }
-  const long long n0 = c->nwalk, M = c->mwalk;
-  const int mode = c->rng_mode; const u64 seed = c->seed64, step = c->step_no;
-  // a host that calls step by step (the reference's own loop does work between steps) and has promised to come back with the
-  // same tau and cutoff (sqmc_gpu_set_chained_runs): this step enqueues the next one's head, as the steps of sqmc_gpu_run do
-  if (!c->in_run) c->pipeline_next = c->chained_runs && sp->reached_w_abs_gen == 2 && mode != SQMC_RNG_REPLAY && !getenv("SQMC_NO_PIPELINE");
-  { static const bool psit_no_pipe = getenv("SQMC_PSIT_NO_PIPELINE") != nullptr;      // hf_to_psit: the head (gate, scan, spawn) behind the tail like any other step's; the gate stays a kernel of its own
-    if (c->psit_on && psit_no_pipe) c->pipeline_next = false; }
-  if (c->sdiag_on) c->pipeline_next = false;      // spawn diagnostics: a head enqueued ahead would count proposals of a step that may never be returned
+  const long long n0 = c->nwalk;
+  const int mode = c->rng_mode; const u64 step = c->step_no;
+  step_pipeline_decision(c, sp);
   collect_timers(c);
   c->nt = 0;
-  hipStream_t st2 = c->st2;
-  int t_gate_scan = -1, t_spawn = -1;
+  int t_gate_scan = -1, t_spawn = -1, r;
   if (c->timing >= 2 && c->nt < NTIMERS) { t_gate_scan = c->nt++; c->tname[t_gate_scan] = "gate_scan"; }
   if (spawn_events_on(c, step, p.semi) && c->nt < NTIMERS) { t_spawn = c->nt++; c->tname[t_spawn] = "spawn"; }
   u64 cseq;
-  if (c->head_ready) {                 // chained runs: the caller came back with other parameters than it left with
-    const StepP &h0 = c->head_p;
-    if (h0.tau != p.tau || h0.cutoff != p.cutoff || h0.semi != p.semi || h0.cti != p.cti || mode == SQMC_RNG_REPLAY) abandon_head(c);
-  }
+  const bool head_ok = c->head_ready && head_fits(c->head_p, p) && mode != SQMC_RNG_REPLAY;
+  if (c->head_ready && !head_ok) abandon_head(c);          // chained runs: the caller came back with other parameters than it left with
   const bool from_head = c->head_ready;
-  if (c->head_ready) {
-    // gate + scan + spawn of this step already run behind k_finish of the last one (pipelined head):
-    // they only depend on parameters that are constant once the target population has been reached
-    c->head_ready = false;
-    const StepP &h = c->head_p;
-    if (h.tau != p.tau || h.cutoff != p.cutoff || h.semi != p.semi || h.cti != p.cti || mode == SQMC_RNG_REPLAY) {
-      hipStreamSynchronize(st);
-      return fail(SQMC_ERR_BAD_ARG, "internal: the pipelined head of this step was launched with other parameters");
-    }
-    cseq = c->head_cseq;
-    if (t_gate_scan >= 0) { std::swap(c->ev0[t_gate_scan], c->hev[0]); std::swap(c->ev1[t_gate_scan], c->hev[1]); }
-    if (t_spawn >= 0) { std::swap(c->ev0[t_spawn], c->hev[2]); std::swap(c->ev1[t_spawn], c->hev[3]); }
-  } else if (mode == SQMC_RNG_REPLAY) {
-    // ---- gate / child offsets (the gate kernel also clears the step's device scalars)
-    if (t_gate_scan >= 0) hipEventRecord(c->ev0[t_gate_scan], st);
-    hipLaunchKernelGGL(k_replay_prepass, dim3(1), dim3(64), 0, st, c->d_tab, c->w.up, c->w.dn, c->w.wt, c->d_nchild, c->d_wchild, c->d_child_off,
-                       c->d_child_state, n0, (M - n0) / (c->dev.hb.on ? 2 : 1), p, c->d_sc, c->dev);
-    if (t_gate_scan >= 0) hipEventRecord(c->ev1[t_gate_scan], st);
-    HIPCHK(hipEventRecord(c->e_fork, st)); c->fork_valid = true;
-    cseq = ++c->cnt_seq;
-    c->nh[0] = 0; c->nh[1] = 5; c->nh[2] = 0; c->nh[3] = spawn_kind(c) != SPAWN_UNIFORM ? 1 : 0; c->nh[4] = 0; c->nh[5] = spawn_kind(c);
-    if (M > n0) {
-      if (t_spawn >= 0)
-        SPAWN_LAUNCH_EXT(spawn_kind(c), 0, spawn_diag(c), dim3(nblk(M - n0)), dim3(TPB), 0, st, c->ev0[t_spawn], c->ev1[t_spawn], 0, c->dev, c->w, c->d_child_off, c->d_wchild,
-                              c->d_child_state, c->d_keys, c->d_vals, n0, M, p, mode, seed, step, c->invalid_key, (const DevScalars *)c->d_sc, c->d_mail, cseq, c->pack, 0, OwnerOut{nullptr, nullptr, 0, 0}, BucketArgs{}, FinArgs{}, PrjPre{}, 0);
-      else
-        SPAWN_LAUNCH(spawn_kind(c), 0, spawn_diag(c), dim3(nblk(M - n0)), dim3(TPB), 0, st, c->dev, c->w, c->d_child_off, c->d_wchild, c->d_child_state, c->d_keys, c->d_vals,
-                           n0, M, p, mode, seed, step, c->invalid_key, (const DevScalars *)c->d_sc, c->d_mail, cseq, c->pack, 0, OwnerOut{nullptr, nullptr, 0, 0}, BucketArgs{}, FinArgs{}, PrjPre{}, 0);
-    } else if (t_spawn >= 0) { hipEventRecord(c->ev0[t_spawn], st); hipEventRecord(c->ev1[t_spawn], st); }
-  } else {
-    int r = enqueue_head(c, p, step, n0, false, t_gate_scan >= 0 ? c->ev0[t_gate_scan] : nullptr, t_gate_scan >= 0 ? c->ev1[t_gate_scan] : nullptr,
-                         t_spawn >= 0 ? c->ev0[t_spawn] : nullptr, t_spawn >= 0 ? c->ev1[t_spawn] : nullptr, &cseq);
-    if (r) return r;
-  }
+  if (from_head) r = take_head(c, head_ok, "internal: the pipelined head of this step was launched with other parameters", t_gate_scan, t_spawn, &cseq);
+  else if (mode == SQMC_RNG_REPLAY) r = replay_head(c, p, step, n0, t_gate_scan, t_spawn, &cseq);
+  else r = enqueue_head(c, p, step, n0, false, t_gate_scan >= 0 ? c->ev0[t_gate_scan] : nullptr, t_gate_scan >= 0 ? c->ev1[t_gate_scan] : nullptr,
+                        t_spawn >= 0 ? c->ev0[t_spawn] : nullptr, t_spawn >= 0 ? c->ev1[t_spawn] : nullptr, &cseq);
+  if (r) return r;
   memcpy(c->lh, c->nh, sizeof(c->lh));      // (the tail below may enqueue the next step's head over nh)
-  // ---- death/clone and the deterministic projection: side streams beside spawn + sort -- or nothing at all here when the
-  //      bucket tail is going to do them itself (pipelined steps whose missing H_ii the head already filled and whose
-  //      deterministic weights the last bucket tail left row by row)
-  {
-    static const bool no_fused_side = getenv("SQMC_NO_FUSED_SIDE") != nullptr;
-    c->side_pending = !no_fused_side && from_head && c->head_hii && c->head_y_done && c->xs_valid && p.semi && bucket_static_ok(c, p) && c->bk_holdoff == 0 && c->head_ba.B > 0;
-    c->head_hii = false;
-    if (!c->side_pending) c->head_hii_joined = false;
-    if (!c->side_pending) { int r = launch_side_kernels(c, p, n0, false); if (r) return r; }
-  }
-  // ---- the child count, from the mailbox (or the slow way when there was no k_spawn launch)
+  if ((r = step_side_kernels(c, p, n0, from_head))) return r;
   long long nch;
-  if (M > n0) {
-    int wr = wait_mail(&c->h_mail->cnt_seq, cseq, st);
-    if (wr > 0) return mail_fail(wr);
-    if (wr < 0) { u64 v; HIPCHK(hipMemcpy(&v, &c->d_sc->n_children, 8, hipMemcpyDeviceToHost)); nch = (long long)v; }
-    else nch = (long long)c->h_mail->n_children;
-  } else { u64 v; HIPCHK(hipMemcpyAsync(&v, &c->d_sc->n_children, 8, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st)); nch = (long long)v; }
-  const long long spc = c->dev.hb.on ? 2 : 1;          // walker slots per child (fast_heatbath: two)
-  if (n0 + spc * nch > M) {
-    hipStreamSynchronize(st); hipStreamSynchronize(st2); hipStreamSynchronize(c->st3);
-    hipMemset(c->d_scan_state, 0, 3 * c->cap_tiles * 8); hipMemset(c->d_scan_ticket, 0, 3 * 4);
-    return fail(SQMC_ERR_MWALK, "nwalk>MWALK");
-  }
-  const long long nall = n0 + spc * nch;
-  return step_tail(c, p, n0, nall, !(c->side_pending && c->head_hii_joined), out);       // nothing ran on the side streams when the tail does that work itself and the H_ii came out of k_spawn
+  if ((r = step_child_count(c, n0, cseq, &nch))) return r;
+  return step_tail(c, p, n0, n0 + (c->dev.hb.on ? 2 : 1) * nch, !(c->side_pending && c->head_hii_joined), out);       // nothing ran on the side streams when the tail does that work itself and the H_ii came out of k_spawn
 }
 
 int sqmc_gpu_shard_step(sqmc_gpu_ctx *c, const sqmc_step_params *sp, double out[16]);
@@ -1821,10 +1890,8 @@ int sqmc_gpu_annihilate(sqmc_gpu_ctx *c, const sqmc_step_params *sp, int64_t n_s
   const u64 lim = c->htab.orb_mask;
   for (long long i = 0; i < n_spawn; i++) if ((up[i] & ~lim) || (dn[i] & ~lim)) return fail(SQMC_ERR_BAD_ARG, "determinant has bits beyond norb");
   hipStream_t st = c->st;
-  StepP p; p.tau = sp->tau; p.e_trial = sp->e_trial; p.rfi = sp->reweight_factor_inv; p.r_init = sp->r_initiator; p.min_wt = sp->min_wt;
-  p.cutoff = sp->always_spawn_cutoff_wt; p.ipow = sp->initiator_power; p.imind = sp->initiator_min_distance; p.cti = sp->c_t_initiator;
-  p.semi = sp->semistochastic; p.reached = sp->reached_w_abs_gen;
-  if (c->psit_on) { if (!sp->semistochastic) return fail(SQMC_ERR_BAD_ARG, "hf_to_psit needs a semistochastic step"); p.koff = c->dev.ps.koff; p.nct = c->dev.ps.n_ct; }
+  const StepP p = step_params(c, sp);
+  if (c->psit_on && !sp->semistochastic) return fail(SQMC_ERR_BAD_ARG, "hf_to_psit needs a semistochastic step");
   collect_timers(c);
   c->nt = 0;
   HIPCHK(hipStreamSynchronize(st));
