@@ -716,6 +716,38 @@ int sqmc_gpu_rotate_integrals(sqmc_gpu_ctx *ctx, const double *rot, double *inte
  * Device memory: norb^4 doubles for G and up to 512 norb^2 for the partial tiles. */
 int sqmc_gpu_orbital_gradient(sqmc_gpu_ctx *ctx, const double *one_rdm, const double *two_rdm_sf, double *fock_out, double *grad_out,
                               double *hdiag_out);
+/* no counterpart in the reference: the one-index transformation of the context's integrals by a real norb x norb matrix kappa
+ * (kappa[a norb + P] = kappa_aP, the layout of rot), the first-order coefficient in t of sqmc_gpu_rotate_integrals(I + t kappa):
+ *   h~_PQ    = sum_a kappa_aP h_aQ + sum_b kappa_bQ h_Pb
+ *   (PQ|RS)~ = sum_a kappa_aP (aQ|RS) + sum_b kappa_bQ (Pb|RS) + sum_c kappa_cR (PQ|cS) + sum_d kappa_dS (PQ|Rd),   E_nuc~ = 0.0
+ * It keeps the 8-fold symmetry for any kappa.  integrals_out: n_integrals + 1 doubles in the layout of sqmc_chem_cfg::integrals,
+ * addressed by the context's combine_2; the nuclear-energy slot and every slot combine_2 does not address are 0.0.  A half pass
+ * over orbital pairs forms the first two terms (two fma chains in ascending index from 0.0, then added), a second pass adds the
+ * half-transformed table to its transpose; one owner per entry, no floating-point atomics: the same bits call to call, exactly
+ * linear under a scaling by a power of two, all +0.0 for kappa = 0.  Any finite real kappa (antisymmetry is not required here).
+ * Chem contexts only: heg, hubbard2 and hubbardk return SQMC_ERR_UNSUPPORTED, as does a combine_2 sqmc_gpu_rotate_integrals
+ * refuses.  A null pointer or a non-finite entry: SQMC_ERR_BAD_ARG.  A refused or failed call leaves integrals_out untouched.
+ * Device memory: (norb (norb + 1) / 2)^2 doubles of work space. */
+int sqmc_gpu_one_index_transform(sqmc_gpu_ctx *ctx, const double *kappa, double *integrals_out);
+/* no counterpart in the reference: the resident plan of a second-order orbital step.  prepare makes the checks of
+ * sqmc_gpu_orbital_gradient on the same two matrices, uploads them and the pair table once, computes F, the gradient and the
+ * diagonal Hessian once and owns the work space of a Hessian-vector product (the partial tiles of the Fock GEMM, the work buffer
+ * and the table of the one-index transformation, the transformed Fock matrix).  A refused or failed prepare leaves plan_out
+ * untouched and holds nothing.  The plan borrows ctx: free it before sqmc_gpu_finalize. */
+typedef struct sqmc_orbopt_plan sqmc_orbopt_plan;
+int sqmc_gpu_orbopt_prepare(sqmc_gpu_ctx *ctx, const double *one_rdm, const double *two_rdm_sf, sqmc_orbopt_plan **plan_out);
+/* what prepare computed, bit for bit what sqmc_gpu_orbital_gradient returns on the same inputs; any output may be NULL, not all */
+int sqmc_gpu_orbopt_gradient(sqmc_orbopt_plan *plan, double *fock_out, double *grad_out, double *hdiag_out);
+/* the orbital Hessian of the fixed-coefficient energy applied to an antisymmetric kappa (kappa[a norb + P] = kappa_aP):
+ *   sigma[p + norb q] = d2/ds dt E(exp(s kappa + t (e_p e_q^T - e_q e_p^T))) at s = t = 0
+ *                     = 2 (F~[p,q] - F~[q,p]) + 1/2 ((kappa g)[p,q] - (g kappa)[p,q]),
+ * F~ the Fock formula of sqmc_gpu_orbital_gradient on the one-index-transformed table, g the gradient at kappa = 0; rotations as
+ * sqmc_gpu_rotate_integrals'.  sigma(K_pq)[p,q] is hdiag[p,q].  norb^2 doubles go in and norb^2 come back.  Fixed order of
+ * additions, no atomics: the same bits call to call and plan to plan; sigma[p,q] == -sigma[q,p], a 0.0 diagonal, no -0.0.
+ * SQMC_ERR_BAD_ARG: a null argument, a non-finite entry, a kappa that is not exactly antisymmetric (kappa[p,q] != -kappa[q,p] or a
+ * non-zero diagonal).  A refused or failed call leaves sigma_out untouched and the plan usable. */
+int sqmc_gpu_orbopt_hessian_vector(sqmc_orbopt_plan *plan, const double *kappa, double *sigma_out);
+int sqmc_gpu_orbopt_free(sqmc_orbopt_plan *plan);
 /* replaces: get_zeroth_order_variational_greens_function (hci.f90:3849-4050) without its file output: the Green's function of a
  * variational wavefunction sum c_i |i> of energy e0 with the diagonal of H as the zeroth-order Hamiltonian of the N+-1 electron
  * spaces, spin-summed, at the frequencies w[0 .. n_w - 1]:

@@ -28,7 +28,7 @@ EXPORTS = [
     "sqmc_gpu_shard_begin", "sqmc_gpu_shard_pack", "sqmc_gpu_shard_finish", "sqmc_gpu_shard_finish_psit", "sqmc_gpu_comm_unique_id", "sqmc_gpu_comm_init", "sqmc_gpu_comm_size",
     "sqmc_gpu_shard_step", "sqmc_gpu_shard_run", "sqmc_gpu_shard_time_split", "sqmc_gpu_get_rng", "sqmc_gpu_set_rng", "sqmc_gpu_tail_stats", "sqmc_gpu_last_tail", "sqmc_gpu_slowest_steps", "sqmc_gpu_set_chained_runs", "sqmc_gpu_spmv_prepare", "sqmc_gpu_davidson",
     "sqmc_gpu_spmv_apply", "sqmc_gpu_spmv_free", "sqmc_gpu_spmv_plan_submatrix", "sqmc_gpu_build_spmv_plan", "sqmc_gpu_spmv_sym_upper", "sqmc_gpu_hamiltonian_batch",
-    "sqmc_gpu_propose_batch", "sqmc_gpu_hamiltonian_chem_batch", "sqmc_gpu_build_sparse_ham", "sqmc_gpu_hci_connections", "sqmc_gpu_hci_connections_slice", "sqmc_gpu_hci_pt2", "sqmc_gpu_hci_pt2_stochastic_prepare", "sqmc_gpu_hci_pt2_stochastic_sample", "sqmc_gpu_hci_pt2_stochastic_stats", "sqmc_gpu_hci_pt2_stochastic_free", "sqmc_gpu_hci_set_active_space", "sqmc_gpu_diag_update_batch", "sqmc_gpu_hci_set_diag_update", "sqmc_gpu_hci_connections_record", "sqmc_gpu_hci_1rdm", "sqmc_gpu_hci_1rdm_pt", "sqmc_gpu_hci_2rdm", "sqmc_gpu_rotate_integrals", "sqmc_gpu_orbital_gradient", "sqmc_gpu_hci_greens_function", "sqmc_gpu_free", "sqmc_gpu_set_timing", "sqmc_gpu_get_timing",
+    "sqmc_gpu_propose_batch", "sqmc_gpu_hamiltonian_chem_batch", "sqmc_gpu_build_sparse_ham", "sqmc_gpu_hci_connections", "sqmc_gpu_hci_connections_slice", "sqmc_gpu_hci_pt2", "sqmc_gpu_hci_pt2_stochastic_prepare", "sqmc_gpu_hci_pt2_stochastic_sample", "sqmc_gpu_hci_pt2_stochastic_stats", "sqmc_gpu_hci_pt2_stochastic_free", "sqmc_gpu_hci_set_active_space", "sqmc_gpu_diag_update_batch", "sqmc_gpu_hci_set_diag_update", "sqmc_gpu_hci_connections_record", "sqmc_gpu_hci_1rdm", "sqmc_gpu_hci_1rdm_pt", "sqmc_gpu_hci_2rdm", "sqmc_gpu_rotate_integrals", "sqmc_gpu_orbital_gradient", "sqmc_gpu_one_index_transform", "sqmc_gpu_orbopt_prepare", "sqmc_gpu_orbopt_gradient", "sqmc_gpu_orbopt_hessian_vector", "sqmc_gpu_orbopt_free", "sqmc_gpu_hci_greens_function", "sqmc_gpu_free", "sqmc_gpu_set_timing", "sqmc_gpu_get_timing",
     "sqmc_gpu_set_spawn_diagnostics", "sqmc_gpu_reset_spawn_diagnostics", "sqmc_gpu_get_spawn_diagnostics", "sqmc_gpu_debug_bucket_boundaries",
 ]
 
@@ -772,6 +772,77 @@ def _gpuchem_orbital_gradient(self, one_rdm, two_rdm_sf, outputs="all"):
     return {b: a.reshape((n, n), order="F") for b, a in out.items()}
 
 
+def _gpuchem_one_index_transform(self, kappa):
+    """sqmc_gpu_one_index_transform: the first-order coefficient in t of rotate_integrals(I + t kappa) as a packed array of
+    n_integrals + 1 doubles addressed by the same combine_2 (the nuclear-energy slot is 0.0).  kappa: (norb, norb), [a, P] as rot;
+    any finite real matrix."""
+    k = _f64(kappa)
+    if k.shape != (self.norb, self.norb):
+        raise ValueError("one_index_transform: kappa must be (norb, norb) = (%d, %d), got %r" % (self.norb, self.norb, k.shape))
+    out = np.zeros(len(self._tabs[3]) if len(self._tabs) > 3 else 1)      # (the library refuses a context without an integral table)
+    self.L.sqmc_gpu_one_index_transform.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    _chk(self.L.sqmc_gpu_one_index_transform(self.h, _p(k), _p(out)))
+    return out
+
+
+class OrbOptPlan:
+    """sqmc_gpu_orbopt_prepare / _gradient / _hessian_vector / _free: the density matrices of GpuChem.orbital_gradient resident on the
+    device, F, gradient and hdiag computed once, and the orbital Hessian of the fixed-coefficient energy applied to antisymmetric
+    matrices.  The plan borrows the context g: close it before g."""
+
+    def __init__(self, g, one_rdm, two_rdm_sf):
+        self.L, self.norb, self.h = g.L, g.norb, None
+        n = g.norb
+        d = np.asarray(one_rdm, np.float64)
+        gg = np.asarray(two_rdm_sf, np.float64)
+        if d.shape != (n, n) or gg.shape != (n,) * 4:
+            raise ValueError("orbopt_plan: one_rdm must be (norb, norb) and two_rdm_sf (norb,) * 4 with norb = %d, got %r and %r" % (n, d.shape, gg.shape))
+        d, gg = np.ascontiguousarray(d.reshape(-1, order="F")), np.ascontiguousarray(gg.reshape(-1, order="F"))
+        self.L.sqmc_gpu_orbopt_prepare.argtypes = [C.c_void_p] * 4
+        self.L.sqmc_gpu_orbopt_gradient.argtypes = [C.c_void_p] * 4
+        self.L.sqmc_gpu_orbopt_hessian_vector.argtypes = [C.c_void_p] * 3
+        self.L.sqmc_gpu_orbopt_free.argtypes = [C.c_void_p]
+        h = C.c_void_p()
+        _chk(self.L.sqmc_gpu_orbopt_prepare(g.h, _p(d), _p(gg), C.byref(h)))
+        self.h, self.g = h, g
+
+    def gradient(self, outputs="all"):
+        """GpuChem.orbital_gradient's dict on the plan's matrices, the same bits, without another upload or kernel"""
+        n = self.norb
+        names = _ORBOPT_OUT if outputs == "all" else (outputs,) if isinstance(outputs, str) else tuple(outputs)
+        if not names or any(b not in _ORBOPT_OUT for b in names):
+            raise ValueError("OrbOptPlan.gradient: outputs must be 'all' or among 'fock', 'gradient', 'hdiag'")
+        out = {b: np.zeros(n * n) for b in _ORBOPT_OUT if b in names}
+        _chk(self.L.sqmc_gpu_orbopt_gradient(self.h, *[_p(out[b]) if b in out else None for b in _ORBOPT_OUT]))
+        return {b: a.reshape((n, n), order="F") for b, a in out.items()}
+
+    def hessian_vector(self, kappa):
+        """sigma[p, q] = d2 E(exp(s kappa + t K_pq)) / ds dt at 0 for an exactly antisymmetric (norb, norb) kappa"""
+        n = self.norb
+        k = _f64(kappa)
+        if k.shape != (n, n):
+            raise ValueError("OrbOptPlan.hessian_vector: kappa must be (norb, norb) = (%d, %d), got %r" % (n, n, k.shape))
+        out = np.zeros(n * n)
+        _chk(self.L.sqmc_gpu_orbopt_hessian_vector(self.h, _p(k), _p(out)))
+        return out.reshape((n, n), order="F")
+
+    def close(self):
+        if self.h:
+            self.L.sqmc_gpu_orbopt_free(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _gpuchem_orbopt_plan(self, one_rdm, two_rdm_sf):
+    """an OrbOptPlan on this context's integrals (close it before the context)"""
+    return OrbOptPlan(self, one_rdm, two_rdm_sf)
+
+
 def _gpuchem_greens_function(self, up, dn, coeffs, e0, w, fermi_sign=False, parts="both"):
     """sqmc_gpu_hci_greens_function (get_zeroth_order_variational_greens_function, hci.f90:3849-4050): (G_np1, G_nm1) of a determinant
     list in any order at the frequencies w, each an (n_w, norb, norb) array indexed [i_w, p, q] (0-based), spin-summed.  fermi_sign
@@ -980,3 +1051,5 @@ GpuChem.two_rdm = _gpuchem_two_rdm
 GpuChem.greens_function = _gpuchem_greens_function
 GpuChem.rotate_integrals = _gpuchem_rotate_integrals
 GpuChem.orbital_gradient = _gpuchem_orbital_gradient
+GpuChem.one_index_transform = _gpuchem_one_index_transform
+GpuChem.orbopt_plan = _gpuchem_orbopt_plan

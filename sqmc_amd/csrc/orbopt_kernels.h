@@ -1,5 +1,6 @@
 // orbopt_kernels.h -- the generalised Fock matrix, the orbital gradient and the diagonal orbital Hessian from the density matrices of
-// a chem context.  Compiled by orbopt_device.hip alone (a code object of its own), launched through orbopt_launch.h.
+// a chem context; behind them the one-index transformation of the integrals and the kernel that makes an orbital Hessian-vector
+// product of it (stated where they begin).  Compiled by orbopt_device.hip alone (a code object of its own), launched through orbopt_launch.h.
 //
 //   F[a,P]     = sum_r h[a,r] D[P,r] + sum_qrs (ar|qs) G[P,q,r,s]
 //   grad[p,q]  = 2 (F[p,q] - F[q,p])
@@ -140,4 +141,112 @@ __global__ void __launch_bounds__(ORB_HD_T) k_orb_hdiag(const double *__restrict
   one = fma(ints[hbase + pair[q * n + q]], D[p + n * p], one);
   one = fma(-2.0 * ints[hbase + pair[p * n + q]], D[q + n * p], one);
   hd[e] = (2.0 * (tot + one) - 2.0 * (F[p + n * p] + F[q + n * q])) + 0.0;
+}
+
+// ------------------------------------------------------------------------------------------------- the one-index transformation
+//   h~[P,Q]  = sum_a kap[a,P] h[a,Q] + sum_b kap[b,Q] h[P,b]
+//   (PQ|RS)~ = sum_a kap[a,P] (aQ|RS) + sum_b kap[b,Q] (Pb|RS) + sum_c kap[c,R] (PQ|cS) + sum_d kap[d,S] (PQ|Rd)
+// kap[a n + P] = kappa[a,P], any real matrix.  The result has the 8-fold symmetry of the integrals and goes into their packed layout.
+// The kernels number the npair = n (n + 1) / 2 pairs themselves, tri(p, q) = p (p + 1) / 2 + q for p >= q; pidx[tri(p, q)] = pair[p n + q]
+// addresses the tables.  Half pass, block rs:  work[tri(P, Q) npair + rs] = first two terms, with M_rs[p][q] = (pq|rs) and kappa in LDS
+// (2 n^2 doubles).  The last two terms are the first two with the pairs exchanged, so the symmetrising pass stores
+// work[PQ npair + RS] + work[RS npair + PQ] for RS <= PQ.  The one-body block is the half pass on M = h, stored where it belongs.
+// An entry of the half pass is (fma chain over a, ascending, from 0.0) + (fma chain over b, ascending, from 0.0); every entry has one
+// owner, no atomics.  M is symmetric, so both chains read their two factors along rows: Z[i][j] = sum_k X[k][i] Y[k][j].
+
+// acc[i][j] = sum_k X[k n + i0 + i] Y[k n + j0 + j], k ascending from 0.0; rows and columns beyond n read the last one (never stored)
+template <int TM>
+__device__ __forceinline__ void orb_xty(const double *__restrict__ X, const double *__restrict__ Y, int n, int i0, int j0, double (&acc)[TM][TM]) {
+  int ci[TM], cj[TM];
+#pragma unroll
+  for (int i = 0; i < TM; i++) { ci[i] = (i0 + i < n) ? i0 + i : n - 1; cj[i] = (j0 + i < n) ? j0 + i : n - 1; }
+#pragma unroll
+  for (int i = 0; i < TM; i++)
+#pragma unroll
+    for (int j = 0; j < TM; j++) acc[i][j] = 0.0;
+  for (int k = 0; k < n; k++) {
+    double x[TM], y[TM];
+#pragma unroll
+    for (int i = 0; i < TM; i++) { x[i] = X[k * n + ci[i]]; y[i] = Y[k * n + cj[i]]; }
+#pragma unroll
+    for (int i = 0; i < TM; i++)
+#pragma unroll
+      for (int j = 0; j < TM; j++) acc[i][j] = fma(x[i], y[j], acc[i][j]);
+  }
+}
+
+// grid: npair blocks (ONE = false: block rs writes column rs of work) or one block (ONE = true: the one-body block into dst = the
+// output table); ORB_T threads; dynamic LDS 2 n^2 doubles
+template <int TM, bool ONE>
+__global__ void __launch_bounds__(ORB_T) k_orb_oneidx_half(const double *__restrict__ ints, const int *__restrict__ pair, const int *__restrict__ pidx, int hbase,
+                                                            const double *__restrict__ kap, int n, double *__restrict__ dst) {
+  extern __shared__ double orb_lds[];
+  const int nn = n * n, blk = blockIdx.x;
+  const size_t npair = (size_t)n * (n + 1) / 2;
+  double *Kp = orb_lds, *M = orb_lds + nn;
+  const int prs = ONE ? 0 : pidx[blk];
+  for (int e = threadIdx.x; e < nn; e += ORB_T) {
+    Kp[e] = kap[e];
+    M[e] = ONE ? ints[hbase + pair[e]] : ints[orb_tri(pair[e], prs)];
+  }
+  __syncthreads();
+  const int nt = (n + TM - 1) / TM;
+  for (int tile = threadIdx.x; tile < nt * nt; tile += ORB_T) {
+    const int i0 = (tile / nt) * TM, j0 = (tile % nt) * TM;
+    if (j0 > i0) continue;                                  // no entry P >= Q in the tile
+    double c1[TM][TM], c2[TM][TM];
+    orb_xty<TM>(Kp, M, n, i0, j0, c1);                      // sum_a kap[a,P] M[a][Q]
+    orb_xty<TM>(M, Kp, n, i0, j0, c2);                      // sum_b M[b][P] kap[b,Q]
+#pragma unroll
+    for (int i = 0; i < TM; i++)
+#pragma unroll
+      for (int j = 0; j < TM; j++) {
+        const int P = i0 + i, Q = j0 + j;
+        if (P >= n || Q > P) continue;
+        const double v = c1[i][j] + c2[i][j];
+        if (ONE) dst[hbase + pair[P * n + Q]] = v;
+        else dst[(size_t)(P * (P + 1) / 2 + Q) * npair + blk] = v;
+      }
+  }
+}
+
+// grid: ntile (ntile + 1) / 2 blocks, ntile = ceil(npair / ORB_SYM_TILE), block b owns the tile (ti, tj), tj <= ti; ORB_T threads as
+// ORB_SYM_TILE columns x (ORB_T / ORB_SYM_TILE) rows.  The transposed tile goes through LDS (padded by one column), so that both
+// reads of work run along its rows.
+__global__ void __launch_bounds__(ORB_T) k_orb_oneidx_sym(const double *__restrict__ work, const int *__restrict__ pidx, int npair, double *__restrict__ out) {
+  constexpr int TS = ORB_SYM_TILE, ROWS = ORB_T / TS;
+  __shared__ double Bt[TS][TS + 1];
+  int ti = 0;
+  while ((ti + 1) * (ti + 2) / 2 <= (int)blockIdx.x) ti++;
+  const int tj = (int)blockIdx.x - ti * (ti + 1) / 2;
+  const int x = threadIdx.x % TS, y0 = threadIdx.x / TS;
+  for (int y = y0; y < TS; y += ROWS) {                     // Bt[y][x] = work[(tj TS + y) npair + ti TS + x]
+    const int row = tj * TS + y, col = ti * TS + x;
+    Bt[y][x] = (row < npair && col < npair) ? work[(size_t)row * npair + col] : 0.0;
+  }
+  __syncthreads();
+  for (int y = y0; y < TS; y += ROWS) {
+    const int PQ = ti * TS + y, RS = tj * TS + x;
+    if (PQ >= npair || RS > PQ) continue;
+    out[orb_tri(pidx[PQ], pidx[RS])] = work[(size_t)PQ * npair + RS] + Bt[x][y];
+  }
+}
+
+// sigma[p,q] = gt[p,q] + 1/2 ((kap g)[p,q] - (g kap)[p,q]),  gt[p,q] = 2 (Ft[p,q] - Ft[q,p]) the gradient formula on the Fock matrix
+// of the transformed table.  kap[a n + P] = kappa[a,P] (antisymmetric: the door has checked it), g[p + n q] the gradient at kappa = 0,
+// Ft and sigma indexed as g.  One thread per entry of the square; the thread of p < q owns sigma[p,q] and sigma[q,p] = its exact
+// negative, the thread of p == q the diagonal 0.0; the two chains run over k ascending from 0.0.
+__global__ void __launch_bounds__(ORB_T) k_orb_sigma(const double *__restrict__ Ft, const double *__restrict__ g, const double *__restrict__ kap, int n,
+                                                      double *__restrict__ sigma) {
+  const int nn = n * n, e = blockIdx.x * ORB_T + threadIdx.x;
+  if (e >= nn) return;
+  const int p = e % n, q = e / n;
+  if (p == q) { sigma[e] = 0.0; return; }
+  if (p > q) return;
+  double kg = 0.0, gk = 0.0;
+  for (int k = 0; k < n; k++) kg = fma(kap[p * n + k], g[k + n * q], kg);
+  for (int k = 0; k < n; k++) gk = fma(g[p + n * k], kap[k * n + q], gk);
+  const double v = 2.0 * (Ft[p + n * q] - Ft[q + n * p]) + 0.5 * (kg - gk);
+  sigma[p + n * q] = v + 0.0;
+  sigma[q + n * p] = -v + 0.0;
 }

@@ -1939,6 +1939,7 @@ int sqmc_gpu_debug_last_head(sqmc_gpu_ctx *c, int32_t info[6]) {
 #include "abi_greens.inc"
 #include "abi_rotate.inc"
 #include "abi_orbopt.inc"
+#include "abi_orbhess.inc"
 #include "abi_spawn_diag.inc"
 #include "davidson.inc"
 #include "heatbath_setup.inc"

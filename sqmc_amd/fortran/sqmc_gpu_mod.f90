@@ -26,6 +26,7 @@ module sqmc_gpu_mod
   public :: sqmc_gpu_set_hubbardk_space_sym, sqmc_gpu_hubbardk_sym_images, sqmc_gpu_debug_bucket_boundaries
   public :: sqmc_gpu_hci_1rdm, sqmc_gpu_hci_1rdm_pt, sqmc_gpu_hci_2rdm, sqmc_gpu_rotate_integrals, sqmc_gpu_orbital_gradient, sqmc_gpu_hci_greens_function
   public :: sqmc_gpu_spmv_plan_submatrix, sqmc_shell_sort_magnitude
+  public :: sqmc_gpu_one_index_transform, sqmc_gpu_orbopt_prepare, sqmc_gpu_orbopt_gradient, sqmc_gpu_orbopt_hessian_vector, sqmc_gpu_orbopt_free
   public :: sqmc_gpu_check
 
   integer(c_int), parameter, public :: SQMC_RNG_REPLAY = 0, SQMC_RNG_COUNTER = 1
@@ -219,6 +220,26 @@ module sqmc_gpu_mod
     ! indexed (a, P) / (p, q), or c_null_ptr for one that is not wanted (not all three).  Chem contexts only
     integer(c_int) function sqmc_gpu_orbital_gradient(ctx, one_rdm, two_rdm_sf, fock_out, grad_out, hdiag_out) bind(C, name='sqmc_gpu_orbital_gradient')
       import; type(c_ptr), value :: ctx; real(c_double), intent(in) :: one_rdm(*), two_rdm_sf(*); type(c_ptr), value :: fock_out, grad_out, hdiag_out
+    end function
+    ! the one-index transformation of the integrals by kappa(norb, norb), the first-order coefficient of sqmc_gpu_rotate_integrals
+    ! (identity + t kappa); the C side reads kappa[a norb + P] = kappa_aP, the layout of rot; integrals_out(0:n_integrals).  Chem contexts only
+    integer(c_int) function sqmc_gpu_one_index_transform(ctx, kappa, integrals_out) bind(C, name='sqmc_gpu_one_index_transform')
+      import; type(c_ptr), value :: ctx; real(c_double), intent(in) :: kappa(*); real(c_double), intent(out) :: integrals_out(*)
+    end function
+    ! the resident plan of a second-order orbital step: the matrices of sqmc_gpu_orbital_gradient uploaded once; F, the gradient and
+    ! the diagonal Hessian computed once.  The plan borrows ctx: free it before sqmc_gpu_finalize
+    integer(c_int) function sqmc_gpu_orbopt_prepare(ctx, one_rdm, two_rdm_sf, plan_out) bind(C, name='sqmc_gpu_orbopt_prepare')
+      import; type(c_ptr), value :: ctx; real(c_double), intent(in) :: one_rdm(*), two_rdm_sf(*); type(c_ptr), intent(out) :: plan_out
+    end function
+    integer(c_int) function sqmc_gpu_orbopt_gradient(plan, fock_out, grad_out, hdiag_out) bind(C, name='sqmc_gpu_orbopt_gradient')
+      import; type(c_ptr), value :: plan, fock_out, grad_out, hdiag_out
+    end function
+    ! sigma(norb, norb) indexed (p, q) = the orbital Hessian applied to the antisymmetric kappa (the C side reads kappa[a norb + P])
+    integer(c_int) function sqmc_gpu_orbopt_hessian_vector(plan, kappa, sigma_out) bind(C, name='sqmc_gpu_orbopt_hessian_vector')
+      import; type(c_ptr), value :: plan; real(c_double), intent(in) :: kappa(*); real(c_double), intent(out) :: sigma_out(*)
+    end function
+    integer(c_int) function sqmc_gpu_orbopt_free(plan) bind(C, name='sqmc_gpu_orbopt_free')
+      import; type(c_ptr), value :: plan
     end function
     ! get_zeroth_order_variational_greens_function (hci.f90:3849-4050) without its files: g_np1(n_w, norb, norb) and
     ! g_nm1(n_w, norb, norb) = c_loc of the arrays, or c_null_ptr for a half that is not wanted; fermi_sign = 0 is the reference

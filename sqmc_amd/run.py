@@ -308,28 +308,37 @@ def run_two_rdm(h, up, dn, wts, energy, p, path):
     return rows
 
 
-def run_optimize_orbitals(h, up, dn, wts, energy, p, path):
+def run_optimize_orbitals(h, up, dn, wts, energy, p, path, solver="diagonal"):
     """--optimize-orbitals [PATH]: one orbital-optimisation step on the variational wavefunction (host.optimize_orbitals_step; several
     states: their averaged matrices), its figures in print, and the rotated integrals written to PATH, a new file in the format of
-    FCIDUMP_eps_var=... (host.write_natorb_fcidump)"""
+    FCIDUMP_eps_var=... (host.write_natorb_fcidump).  solver "newton" (--orbopt-solver): the Newton-CG step on the device's
+    Hessian-vector products, with its count of products, why it stopped and the predicted beside the actual change."""
     from . import host as H
     if os.path.exists(path):                         # before any work is done, as --rotate-integrals
         raise FileExistsError("sqmc_amd: %s exists; the rotated integrals are written to a new file only" % path)
-    p("\nOrbital optimisation: one diagonal-Newton step from the 1-RDM and the 2-RDM of the variational wavefunction")
-    r = H.optimize_orbitals_step(h, up, dn, wts)
+    newton = solver == "newton"
+    p("\nOrbital optimisation: one %s step from the 1-RDM and the 2-RDM of the variational wavefunction" % ("Newton-CG" if newton else "diagonal-Newton"))
+    r = H.optimize_orbitals_step(h, up, dn, wts, solver="newton") if newton else H.optimize_orbitals_step(h, up, dn, wts)
     e_var = float(np.mean(np.asarray(energy, float)[:wts.shape[1]]))
     p(" Energy from the density matrices =%18.9f   Variational energy =%18.9f   difference =%10.2E" % (r["energy_before"], e_var, r["energy_before"] - e_var))
     p(" max|g| =%14.6E   ||g||_2 =%14.6E" % (r["max_gradient"], r["gradient_norm"]))
+    if newton:
+        p(" Hessian-vector products =%4d   stopped on: %s" % (r["cg_iterations"], r["cg_stop"]))
     p(" max|kappa| =%14.6E   backtracking scale =%12.8f" % (r["max_kappa"], r["scale"]))
     p(" Fixed-coefficient energy after the step =%18.9f   lowering =%10.2E" % (r["energy_after"], r["energy_after"] - r["energy_before"]))
+    if newton:
+        p(" Predicted change =%10.2E (of the step before backtracking)   actual change =%10.2E" % (r["predicted_change"], r["energy_after"] - r["energy_before"]))
     H.write_natorb_fcidump(path, h, r["integrals"])
     p("Rotated integrals written to " + path)
-    return dict(path=path, rotation=r["rotation"], integrals=r["integrals"], energy_before=r["energy_before"], energy_after=r["energy_after"],
-                max_gradient=r["max_gradient"], gradient_norm=r["gradient_norm"], max_kappa=r["max_kappa"], scale=r["scale"])
+    out = dict(path=path, rotation=r["rotation"], integrals=r["integrals"], energy_before=r["energy_before"], energy_after=r["energy_after"],
+               max_gradient=r["max_gradient"], gradient_norm=r["gradient_norm"], max_kappa=r["max_kappa"], scale=r["scale"])
+    if newton:
+        out.update(solver="newton", cg_iterations=r["cg_iterations"], cg_stop=r["cg_stop"], predicted_change=r["predicted_change"])
+    return out
 
 
 def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False, pt_diag_update=0, one_rdm_path=None, natorb_fcidump=None, greens_signed=False,
-            extrap_rebuild=False, two_rdm_path=None, optimize_orbitals=None):
+            extrap_rebuild=False, two_rdm_path=None, optimize_orbitals=None, orbopt_solver="diagonal"):
     """pt_on_device: the samples of the semistochastic PT are evaluated by the library (host.hci_pt2_stochastic on_device);
     pt_diag_update: 0 / 1 / 2, how the PT stage forms H_aa (host.hci_pt2); one_rdm_path: with &natorb get_natorbs = t, also save the
     1-RDM there as .npy; natorb_fcidump: with &natorb get_natorbs = t, rotate the integrals into the natural orbitals and write them
@@ -340,7 +349,12 @@ def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False, pt_diag
     extrapolation, the records of host.hci_extrapolation_energies.  two_rdm_path: after the variational stage, run_two_rdm; the result
     then holds two_rdm, its per-state records.  Without it the output is what it is without this argument.  optimize_orbitals: after
     the variational stage (and run_two_rdm), run_optimize_orbitals writing to this new file (True: FCIDUMP_opt_eps_var=<smallest
-    eps_var>); the result then holds optimize_orbitals.  Without it the output is what it is without this argument."""
+    eps_var>); the result then holds optimize_orbitals.  Without it the output is what it is without this argument.  orbopt_solver:
+    "diagonal" (the step as it always was) or "newton" (run_optimize_orbitals); only with optimize_orbitals."""
+    if orbopt_solver not in ("diagonal", "newton"):
+        raise SystemExit("--orbopt-solver: diagonal or newton")
+    if orbopt_solver != "diagonal" and not optimize_orbitals:
+        raise SystemExit("--orbopt-solver chooses the solver of --optimize-orbitals: give that too")
     if optimize_orbitals and (deck["hamiltonian_type"] == "heg" or deck.get("get_natorbs") or deck.get("n_energy_batch", 0) > 0):
         raise SystemExit("--optimize-orbitals runs between the variational and the PT stage of a chem deck: not with heg, &natorb get_natorbs or n_energy_batch > 0, which end elsewhere")
     if optimize_orbitals and deck["nelec"] < 2:
@@ -404,7 +418,7 @@ def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False, pt_diag
     if optimize_orbitals:
         if optimize_orbitals is True:
             optimize_orbitals = H.optorb_fcidump_name(min([eps_var] + deck["eps_var_sched"]))
-        optorb = run_optimize_orbitals(h, up, dn, np.asarray(wts, float).reshape(len(up), -1)[:, :n_states], energy, p, optimize_orbitals)
+        optorb = run_optimize_orbitals(h, up, dn, np.asarray(wts, float).reshape(len(up), -1)[:, :n_states], energy, p, optimize_orbitals, orbopt_solver)
         t0, t1 = t0 + (time.perf_counter() - t1), time.perf_counter()      # keep the stage out of both times of the last line
     greens = run_greens(deck, h, up, dn, wts, energy, p, greens_signed) if want_greens else None
     results = []
@@ -484,6 +498,9 @@ def main(argv=None):
                     "orbital-optimisation step from the 1-RDM and 2-RDM on the device (gradient, diagonal Hessian, backtracking on the fixed-coefficient energy), "
                     "print its figures and write the rotated integrals to PATH, a new file (default: FCIDUMP_opt_eps_var=<smallest eps_var>); refused with heg "
                     "decks, &natorb get_natorbs and n_energy_batch > 0, whose runs end elsewhere")
+    ap.add_argument("--orbopt-solver", choices=("diagonal", "newton"), default="diagonal", help="with --optimize-orbitals: the diagonal-Newton step (default) or "
+                    "a line-search Newton-CG step on the device's orbital Hessian-vector products; prints the number of products, why the solver stopped and "
+                    "the predicted beside the actual change")
     a = ap.parse_args(argv)
     text = open(a.input).read() if a.input else sys.stdin.read()
     lines = [l for l in text.splitlines() if l.strip() and not l.lstrip().startswith("!")]
@@ -494,7 +511,7 @@ def main(argv=None):
                         dtm_elems_in=a.dtm_elems_in, dtm_elems_out=a.dtm_elems_out, spawn_histograms=a.spawn_histograms)
     deck = parse_hci_deck(text)
     return run_hci(deck, a.fcidump, pt_on_device=a.pt_on_device, pt_diag_update=a.pt_diag_update, one_rdm_path=a.one_rdm, natorb_fcidump=a.rotate_integrals,
-                   greens_signed=a.greens_signed, extrap_rebuild=a.extrap_rebuild, two_rdm_path=a.two_rdm, optimize_orbitals=a.optimize_orbitals)
+                   greens_signed=a.greens_signed, extrap_rebuild=a.extrap_rebuild, two_rdm_path=a.two_rdm, optimize_orbitals=a.optimize_orbitals, orbopt_solver=a.orbopt_solver)
 
 
 if __name__ == "__main__":

@@ -6,7 +6,11 @@ Writes one JSON document (default profiles/orbopt_loop.json).
   natural orbitals     HCI -> 1-RDM -> host.natural_orbitals -> GpuChem.rotate_integrals -> ChemHost.with_integrals -> HCI -> ...
 
 Per iteration: E_var, the number of determinants, and for the optimised orbitals max|g|, the step's scale and the fixed-coefficient
-energies before and after it.  State 1 of a one-state run; nothing is promised about either loop, the record is what was measured."""
+energies before and after it.  State 1 of a one-state run; nothing is promised about either loop, the record is what was measured.
+
+--solver newton adds a third loop, "newton_orbitals": the same macro-iterations with host.optimize_orbitals_step(solver="newton"), the
+Newton-CG step on the device's Hessian-vector products, with its products, stop reason and predicted change per iteration (write it
+beside the other record: --out profiles/orbhess_loop.json)."""
 import argparse
 import json
 import os
@@ -24,6 +28,7 @@ from sqmc_amd import host as H      # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--iters", type=int, default=4)
 ap.add_argument("--eps-var", type=float, default=2e-3)
+ap.add_argument("--solver", choices=("diagonal", "newton"), default="diagonal")
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "orbopt_loop.json"))
 args = ap.parse_args()
 
@@ -48,10 +53,12 @@ def loop(kind):
         up, dn, w, e, secs = variational(host)
         row = {"iteration": it, "e_var": e, "ndets": int(len(up)), "variational_stage_wall_s": secs}
         t0 = time.perf_counter()
-        if kind == "optimised":
-            r = H.optimize_orbitals_step(host, up, dn, w)
+        if kind in ("optimised", "newton"):
+            r = H.optimize_orbitals_step(host, up, dn, w, solver="newton") if kind == "newton" else H.optimize_orbitals_step(host, up, dn, w)
             row.update({"max_gradient": r["max_gradient"], "gradient_norm": r["gradient_norm"], "max_kappa": r["max_kappa"], "scale": r["scale"],
                         "fixed_coefficient_energy_before": r["energy_before"], "fixed_coefficient_energy_after": r["energy_after"]})
+            if kind == "newton":
+                row.update({"hessian_vector_products": r["cg_iterations"], "cg_stop": r["cg_stop"], "predicted_change": r["predicted_change"]})
             packed = r["integrals"]
         else:
             D = H.hci_one_rdm(host, up, dn, w)
@@ -69,9 +76,11 @@ def loop(kind):
     return rows
 
 
-doc = {"tool": "tools/orbopt_loop.py", "command": "python tools/orbopt_loop.py --iters %d --eps-var %g" % (args.iters, args.eps_var),
+doc = {"tool": "tools/orbopt_loop.py", "command": "python tools/orbopt_loop.py --iters %d --eps-var %g%s" % (args.iters, args.eps_var, " --solver newton" if args.solver == "newton" else ""),
        "system": "C2_r1.24253 cc-pVDZ, 8 electrons in 26 orbitals, d2h, one state", "eps_var": args.eps_var, "device": torch.cuda.get_device_name(0),
        "min_hess": H.ORBOPT_MIN_HESS, "max_step": H.ORBOPT_MAX_STEP, "optimised_orbitals": loop("optimised"), "natural_orbitals": loop("natural")}
+if args.solver == "newton":
+    doc.update({"cg_tol": H.ORBOPT_CG_TOL, "max_cg": H.ORBOPT_MAX_CG, "newton_orbitals": loop("newton")})
 try:
     doc["commit"] = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip() or None
 except OSError:
