@@ -680,6 +680,32 @@ int sqmc_gpu_hci_1rdm_pt(sqmc_gpu_ctx *ctx, int64_t n_var, const uint64_t *var_u
  * electrons) or more.  A refused or failed call leaves all three arrays untouched. */
 int sqmc_gpu_hci_2rdm(sqmc_gpu_ctx *ctx, int64_t n_var, const uint64_t *var_up, const uint64_t *var_dn, const double *coeffs,
                       int32_t blocks, double *rdm_aa, double *rdm_bb, double *rdm_ab);
+/* no counterpart in the reference: the one-body transition density matrix of two coefficient vectors bra and ket over one
+ * determinant list, spin-summed, in the index convention of sqmc_gpu_hci_1rdm:
+ *   tdm[p + norb r] = <bra| a+_r a_p |ket> = sum_sigma sum_i sign ket_i bra_k,   orbitals 0-based,
+ * k = determinant i with the sigma electron moved p -> r and sign as there; the diagonal is sum_i bra_i ket_i over the determinants
+ * with p occupied, both spins added.  Nothing is renormalised: the trace is nelec <bra|ket>.  The block that owns (p, r), p < r,
+ * forms both entries from one search of the sorted ranks (tdm[p,r] += sign ket_i bra_k, tdm[r,p] += sign bra_i ket_k), chunks of
+ * the list in rank order are added in chunk order, up before dn, no floating-point atomics: an entry has the same bits run to run
+ * and for every order of the caller's list; swapping bra and ket transposes the matrix exactly; with bra == ket, entries (p, r)
+ * and (r, p) are both the bits of sqmc_gpu_hci_1rdm's entry (min, max).  orbital_symmetries: as in sqmc_gpu_hci_1rdm (filtered
+ * entries exactly 0.0, the others the unfiltered bits).  Every system type.  Refusals and error codes are those of
+ * sqmc_gpu_hci_1rdm (time_sym = 1, hubbardk with space_sym: SQMC_ERR_UNSUPPORTED; a repeated determinant, wrong electron numbers,
+ * an orbital beyond norb, a label outside 0..255: SQMC_ERR_BAD_ARG).  A refused or failed call leaves tdm untouched. */
+int sqmc_gpu_hci_1tdm(sqmc_gpu_ctx *ctx, int64_t n_var, const uint64_t *var_up, const uint64_t *var_dn, const double *bra, const double *ket,
+                      const int32_t *orbital_symmetries, double *tdm);
+/* no counterpart in the reference: the two-body transition density matrix of bra and ket over one determinant list, in the spin
+ * blocks, index order and flat index of sqmc_gpu_hci_2rdm:
+ *   tdm_aa = <bra| a+_{p up} a+_{q up} a_{s up} a_{r up} |ket>,  tdm_bb the same with dn,  tdm_ab = <bra| a+_{p up} a+_{q dn} a_{s dn} a_{r up} |ket>.
+ * Nothing is renormalised.  The records, their sort and the owner scheme are the 2-RDM's; a record carries the signed bra and the
+ * signed ket coefficient, and the owner of a pair of columns (A, B) keeps two sums for its one search, T[A,B] and T[B,A].  No
+ * floating-point atomics and a fixed order of additions: the same bits run to run, for every order of the list and whichever other
+ * blocks were asked for; T(bra, ket)[p,q,r,s] == T(ket, bra)[r,s,p,q] exactly; T(c, c) is the bytes of sqmc_gpu_hci_2rdm(c); the
+ * antisymmetries of aa / bb under p <-> q and r <-> s hold exactly; every entry no pair of determinants reaches is 0.0 and nothing
+ * is ever -0.0.  blocks, the refusals and the error codes are exactly those of sqmc_gpu_hci_2rdm.  A refused or failed call leaves
+ * all three arrays untouched. */
+int sqmc_gpu_hci_2tdm(sqmc_gpu_ctx *ctx, int64_t n_var, const uint64_t *var_up, const uint64_t *var_dn, const double *bra, const double *ket,
+                      int32_t blocks, double *tdm_aa, double *tdm_bb, double *tdm_ab);
 /* replaces: the integral rotation of generate_natorb_integrals (hci.f90:3683-3791): the context's one- and two-body integrals in
  * the orbitals  new_p = sum_k rot[k norb + p] old_k  (k, p 0-based, in the context's orbital order; row-major: the C-order memory of
  * the eigenvector matrix the 1-RDM is diagonalised into, the transpose of a column-major host's rdm(k, p)):

@@ -28,7 +28,7 @@ EXPORTS = [
     "sqmc_gpu_shard_begin", "sqmc_gpu_shard_pack", "sqmc_gpu_shard_finish", "sqmc_gpu_shard_finish_psit", "sqmc_gpu_comm_unique_id", "sqmc_gpu_comm_init", "sqmc_gpu_comm_size",
     "sqmc_gpu_shard_step", "sqmc_gpu_shard_run", "sqmc_gpu_shard_time_split", "sqmc_gpu_get_rng", "sqmc_gpu_set_rng", "sqmc_gpu_tail_stats", "sqmc_gpu_last_tail", "sqmc_gpu_slowest_steps", "sqmc_gpu_set_chained_runs", "sqmc_gpu_spmv_prepare", "sqmc_gpu_davidson",
     "sqmc_gpu_spmv_apply", "sqmc_gpu_spmv_free", "sqmc_gpu_spmv_plan_submatrix", "sqmc_gpu_build_spmv_plan", "sqmc_gpu_spmv_sym_upper", "sqmc_gpu_hamiltonian_batch",
-    "sqmc_gpu_propose_batch", "sqmc_gpu_hamiltonian_chem_batch", "sqmc_gpu_build_sparse_ham", "sqmc_gpu_hci_connections", "sqmc_gpu_hci_connections_slice", "sqmc_gpu_hci_pt2", "sqmc_gpu_hci_pt2_stochastic_prepare", "sqmc_gpu_hci_pt2_stochastic_sample", "sqmc_gpu_hci_pt2_stochastic_stats", "sqmc_gpu_hci_pt2_stochastic_free", "sqmc_gpu_hci_set_active_space", "sqmc_gpu_diag_update_batch", "sqmc_gpu_hci_set_diag_update", "sqmc_gpu_hci_connections_record", "sqmc_gpu_hci_1rdm", "sqmc_gpu_hci_1rdm_pt", "sqmc_gpu_hci_2rdm", "sqmc_gpu_rotate_integrals", "sqmc_gpu_orbital_gradient", "sqmc_gpu_one_index_transform", "sqmc_gpu_orbopt_prepare", "sqmc_gpu_orbopt_gradient", "sqmc_gpu_orbopt_hessian_vector", "sqmc_gpu_orbopt_free", "sqmc_gpu_hci_greens_function", "sqmc_gpu_free", "sqmc_gpu_set_timing", "sqmc_gpu_get_timing",
+    "sqmc_gpu_propose_batch", "sqmc_gpu_hamiltonian_chem_batch", "sqmc_gpu_build_sparse_ham", "sqmc_gpu_hci_connections", "sqmc_gpu_hci_connections_slice", "sqmc_gpu_hci_pt2", "sqmc_gpu_hci_pt2_stochastic_prepare", "sqmc_gpu_hci_pt2_stochastic_sample", "sqmc_gpu_hci_pt2_stochastic_stats", "sqmc_gpu_hci_pt2_stochastic_free", "sqmc_gpu_hci_set_active_space", "sqmc_gpu_diag_update_batch", "sqmc_gpu_hci_set_diag_update", "sqmc_gpu_hci_connections_record", "sqmc_gpu_hci_1rdm", "sqmc_gpu_hci_1rdm_pt", "sqmc_gpu_hci_2rdm", "sqmc_gpu_hci_1tdm", "sqmc_gpu_hci_2tdm", "sqmc_gpu_rotate_integrals", "sqmc_gpu_orbital_gradient", "sqmc_gpu_one_index_transform", "sqmc_gpu_orbopt_prepare", "sqmc_gpu_orbopt_gradient", "sqmc_gpu_orbopt_hessian_vector", "sqmc_gpu_orbopt_free", "sqmc_gpu_hci_greens_function", "sqmc_gpu_free", "sqmc_gpu_set_timing", "sqmc_gpu_get_timing",
     "sqmc_gpu_set_spawn_diagnostics", "sqmc_gpu_reset_spawn_diagnostics", "sqmc_gpu_get_spawn_diagnostics", "sqmc_gpu_debug_bucket_boundaries",
 ]
 
@@ -45,9 +45,9 @@ class SqmcGpuError(RuntimeError):
 def build_library(force=False):
     """hipcc cross-compiles for gfx950 without a GPU present."""
     csrc = os.path.join(_HERE, "csrc")
-    # three translation units: sqmc_gpu.hip includes every .h / .inc of csrc/ textually but rdm2_kernels.h and orbopt_kernels.h, which
-    # rdm2_device.hip and orbopt_device.hip compile into code objects of their own
-    units = [os.path.join(csrc, "sqmc_gpu.hip"), os.path.join(csrc, "rdm2_device.hip"), os.path.join(csrc, "orbopt_device.hip")]
+    # four translation units: sqmc_gpu.hip includes every .h / .inc of csrc/ textually but rdm2_kernels.h, orbopt_kernels.h and
+    # tdm_kernels.h, which rdm2_device.hip, orbopt_device.hip and tdm_device.hip compile into code objects of their own
+    units = [os.path.join(csrc, f) for f in ("sqmc_gpu.hip", "rdm2_device.hip", "orbopt_device.hip", "tdm_device.hip")]
     src = units + sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".h", ".inc"))) \
         + [os.path.join(_ROOT, "include", "sqmc_gpu.h")]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in src):
@@ -748,6 +748,40 @@ def _gpuchem_rotate_integrals(self, rot):
     return out
 
 
+def _gpuchem_one_tdm(self, up, dn, bra, ket, orbital_symmetries=None):
+    """sqmc_gpu_hci_1tdm: the spin-summed one-body transition density matrix of two coefficient vectors over one determinant list in
+    any order as an (norb, norb) array indexed as one_rdm's, a[p, r] = <bra| a+_r a_p |ket> (the electron moves p -> r; 0-based;
+    nothing is renormalised).  one_tdm(bra, ket) == one_tdm(ket, bra).T exactly.  orbital_symmetries: as in one_rdm"""
+    u, d, b, k = _u64(up), _u64(dn), _f64(bra), _f64(ket)
+    if not (len(u) == len(d) == len(b) == len(k)):
+        raise ValueError("up, dn, bra and ket differ in length")
+    sym = None if orbital_symmetries is None else np.ascontiguousarray(orbital_symmetries, np.int32)
+    if sym is not None and len(sym) != self.norb:
+        raise ValueError("orbital_symmetries must hold norb labels")
+    out = np.zeros(self.norb * self.norb)
+    self.L.sqmc_gpu_hci_1tdm.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 6
+    _chk(self.L.sqmc_gpu_hci_1tdm(self.h, len(u), _p(u), _p(d), _p(b), _p(k), None if sym is None else _p(sym), _p(out)))
+    return np.ascontiguousarray(out.reshape(self.norb, self.norb).T)          # flat index p + norb r
+
+
+def _gpuchem_two_tdm(self, up, dn, bra, ket, blocks="all"):
+    """sqmc_gpu_hci_2tdm: the spin blocks of the two-body transition density matrix of two coefficient vectors over one determinant
+    list in any order, a dict as two_rdm's: T_aa[p, q, r, s] = <bra| a+_{p up} a+_{q up} a_{s up} a_{r up} |ket>, T_bb the same with
+    dn, T_ab[p, q, r, s] = <bra| a+_{p up} a+_{q dn} a_{s dn} a_{r up} |ket> (0-based; nothing is renormalised).
+    two_tdm(bra, ket)[b] == two_tdm(ket, bra)[b].transpose(2, 3, 0, 1) and two_tdm(c, c) == two_rdm(c), both exactly"""
+    u, d, b, k = _u64(up), _u64(dn), _f64(bra), _f64(ket)
+    if not (len(u) == len(d) == len(b) == len(k)):
+        raise ValueError("up, dn, bra and ket differ in length")
+    names = ("aa", "bb", "ab") if blocks == "all" else (blocks,) if isinstance(blocks, str) else tuple(blocks)
+    if not names or any(x not in _RDM2_BLOCKS for x in names):
+        raise ValueError("two_tdm: blocks must be 'all' or among 'aa', 'bb', 'ab'")
+    out = {x: np.zeros(self.norb ** 4) for x in ("aa", "bb", "ab") if x in names}
+    self.L.sqmc_gpu_hci_2tdm.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 3
+    _chk(self.L.sqmc_gpu_hci_2tdm(self.h, len(u), _p(u), _p(d), _p(b), _p(k), sum(_RDM2_BLOCKS[x] for x in out),
+                                  *[_p(out[x]) if x in out else None for x in ("aa", "bb", "ab")]))
+    return {x: a.reshape((self.norb,) * 4, order="F") for x, a in out.items()}
+
+
 _ORBOPT_OUT = ("fock", "gradient", "hdiag")
 
 
@@ -1048,6 +1082,8 @@ GpuChem.hci_connections_record = _gpuchem_hci_connections_record
 GpuChem.one_rdm = _gpuchem_one_rdm
 GpuChem.one_rdm_pt = _gpuchem_one_rdm_pt
 GpuChem.two_rdm = _gpuchem_two_rdm
+GpuChem.one_tdm = _gpuchem_one_tdm
+GpuChem.two_tdm = _gpuchem_two_tdm
 GpuChem.greens_function = _gpuchem_greens_function
 GpuChem.rotate_integrals = _gpuchem_rotate_integrals
 GpuChem.orbital_gradient = _gpuchem_orbital_gradient

@@ -2,9 +2,10 @@
 // Textually included by sqmc_gpu.hip; not a standalone file.
 
 // the determinant list of a 1-RDM call on the device, in rank order; the list owns its buffers
-struct RdmList { DevScratch mem; long long n = 0; u64 *su = nullptr, *sd = nullptr, *skey = nullptr; double *sc = nullptr; explicit RdmList(hipStream_t st) : mem(st) {} };
-// checks, upload, ranks, sort, gather, repeats
-static int rdm_list_build(sqmc_gpu_ctx *c, const char *who, int64_t n, const uint64_t *up, const uint64_t *dn, const double *coeffs, RdmList &L) {
+struct RdmList { DevScratch mem; long long n = 0; u64 *su = nullptr, *sd = nullptr, *skey = nullptr; double *sc = nullptr, *sc2 = nullptr; explicit RdmList(hipStream_t st) : mem(st) {} };
+// checks, upload, ranks, sort, gather, repeats.  coeffs2: a second coefficient array over the same list (the transition matrices' bra)
+// or null; gathered by the same permutation into L.sc2
+static int rdm_list_build(sqmc_gpu_ctx *c, const char *who, int64_t n, const uint64_t *up, const uint64_t *dn, const double *coeffs, RdmList &L, const double *coeffs2 = nullptr) {
   const std::string w(who);
   if (n >= (1ll << 31)) return fail(SQMC_ERR_UNSUPPORTED, w + ": more than 2^31 determinants");
   const u64 lim = c->htab.norb >= 64 ? ~0ull : ((1ull << c->htab.norb) - 1ull);
@@ -15,17 +16,20 @@ static int rdm_list_build(sqmc_gpu_ctx *c, const char *who, int64_t n, const uin
   DevScratch work(st);                 // released before returning: caller-order copies, sort scratch, the repeat flag
   u64 *vu = work.take<u64>(n), *vd = work.take<u64>(n); double *vc = work.take<double>(n); int *flag = work.take<int>(1);
   u64 *su = L.mem.take<u64>(n), *sd = L.mem.take<u64>(n); double *sc = L.mem.take<double>(n);
+  double *vc2 = coeffs2 ? work.take<double>(n) : nullptr, *sc2 = coeffs2 ? L.mem.take<double>(n) : nullptr;
   if (!work.ok() || !L.mem.ok()) return hip_fail(who, work.ok() ? L.mem.err() : work.err());
   HIPDOOR(who, hipMemcpy(vu, up, n * 8, hipMemcpyHostToDevice)); HIPDOOR(who, hipMemcpy(vd, dn, n * 8, hipMemcpyHostToDevice));
   HIPDOOR(who, hipMemcpy(vc, coeffs, n * 8, hipMemcpyHostToDevice)); HIPDOOR(who, hipMemsetAsync(flag, 0, 4, st));
+  if (coeffs2) HIPDOOR(who, hipMemcpy(vc2, coeffs2, n * 8, hipMemcpyHostToDevice));
   u64 *skey; u32 *sperm;
   { const int rs = det_ranks_sorted(c, who, n, vu, vd, L.mem, work, &skey, &sperm); if (rs) return rs; }
   hipLaunchKernelGGL(k_rdm_gather, dim3(nblk(n)), dim3(TPB), 0, st, (const u32 *)sperm, (const u64 *)vu, (const u64 *)vd, (const double *)vc, su, sd, sc, (long long)n);
+  if (coeffs2) hipLaunchKernelGGL(k_rdm_gather, dim3(nblk(n)), dim3(TPB), 0, st, (const u32 *)sperm, (const u64 *)vu, (const u64 *)vd, (const double *)vc2, su, sd, sc2, (long long)n);
   hipLaunchKernelGGL(k_rdm_repeats, dim3(nblk(n)), dim3(TPB), 0, st, (const u64 *)skey, (long long)n, flag);
   int rep = 0;
   HIPDOOR(who, hipGetLastError()); HIPDOOR(who, hipMemcpyAsync(&rep, flag, 4, hipMemcpyDeviceToHost, st)); HIPDOOR(who, hipStreamSynchronize(st));
   if (rep) return fail(SQMC_ERR_BAD_ARG, w + ": a determinant appears twice in the list");
-  L.n = n; L.su = su; L.sd = sd; L.sc = sc; L.skey = skey;
+  L.n = n; L.su = su; L.sd = sd; L.sc = sc; L.sc2 = sc2; L.skey = skey;
   return SQMC_OK;
 }
 // tools/rdm_time.py: HIP events around the kernels of a 1-RDM call (SQMC_RDM_TIME set when the library first runs one)

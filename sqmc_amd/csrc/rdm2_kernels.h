@@ -28,6 +28,8 @@
 //   k_rdm2_expand   into the zeroed dense block: (a, b) and (b, a), and for aa / bb the four signed images of p < q, r < s; an image
 //                   of sign -1 is 0.0 - g, so that nothing is ever -0.0.  G[p,q,r,s] == G[r,s,p,q] and the antisymmetries hold exactly.
 
+#include "rdm2_index.h"      // rdm2_entry, rdm2_put: shared with tdm_kernels.h
+
 __device__ __forceinline__ int rdm2_nth_bit(u64 s, int k) { for (int q = 0; q < k; q++) s &= s - 1; return ctz64(s); }
 
 // record t = determinant t / R, local pair t % R.  sortkey: the word (oneword) or the key of K; idx: the record's own index
@@ -77,13 +79,6 @@ __global__ void __launch_bounds__(TPB) k_rdm2_colstart(const u32 *__restrict__ s
   while (lo < hi) { const long long mid = (lo + hi) >> 1; if (sP[mid] < (u32)p) lo = mid + 1; else hi = mid; }
   start[p] = (u32)lo;
 }
-// flat index e = j (j + 1) / 2 + i, i <= j
-__device__ __forceinline__ void rdm2_entry(long long e, long long *i, long long *j) {
-  long long q = (long long)((sqrt(8.0 * (double)e + 1.0) - 1.0) * 0.5);
-  while (q > 0 && q * (q + 1) / 2 > e) q--;
-  while ((q + 1) * (q + 2) / 2 <= e) q++;
-  *j = q; *i = e - q * (q + 1) / 2;
-}
 // G = 256: a block per entry; G = 64: a wavefront per entry, four to a block.  Entries [e0, e1)
 template <int G>
 __global__ void __launch_bounds__(256) k_rdm2_gram(const u64 *__restrict__ sK, const double *__restrict__ sV, const u32 *__restrict__ start, const u32 *__restrict__ col,
@@ -111,9 +106,6 @@ __global__ void __launch_bounds__(256) k_rdm2_gram(const u64 *__restrict__ sK, c
     __syncthreads();
     if (threadIdx.x == 0 && e < e1) gram[e] = (red[0] + red[1]) + (red[2] + red[3]);
   } else if (lane == 0 && e < e1) gram[e] = acc;
-}
-__device__ __forceinline__ void rdm2_put(double *__restrict__ out, int norb, int p, int q, int r, int s, double g) {
-  out[(size_t)p + (size_t)norb * ((size_t)q + (size_t)norb * ((size_t)r + (size_t)norb * (size_t)s))] = g;
 }
 // one thread per entry of the Gram matrix; out: norb^4 doubles, zeroed
 __global__ void __launch_bounds__(TPB) k_rdm2_expand(const double *__restrict__ gram, const u32 *__restrict__ col, long long nent, int kind, int norb, double *__restrict__ out) {

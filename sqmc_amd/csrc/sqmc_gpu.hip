@@ -41,6 +41,7 @@
 #include "host_sort.h"
 #include "rdm2_plan.h"
 #include "rdm2_launch.h"
+#include "tdm_launch.h"
 #include "orbopt_plan.h"
 #include "orbopt_launch.h"
 
@@ -1936,6 +1937,7 @@ int sqmc_gpu_debug_last_head(sqmc_gpu_ctx *c, int32_t info[6]) {
 #include "abi_doors.inc"
 #include "abi_rdm.inc"
 #include "abi_rdm2.inc"
+#include "abi_tdm.inc"
 #include "abi_greens.inc"
 #include "abi_rotate.inc"
 #include "abi_orbopt.inc"

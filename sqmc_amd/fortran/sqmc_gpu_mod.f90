@@ -24,7 +24,7 @@ module sqmc_gpu_mod
   public :: sqmc_gpu_hci_pt2_stochastic_prepare, sqmc_gpu_hci_pt2_stochastic_sample, sqmc_gpu_hci_pt2_stochastic_stats, sqmc_gpu_hci_pt2_stochastic_free
   public :: sqmc_gpu_set_spawn_diagnostics, sqmc_gpu_reset_spawn_diagnostics, sqmc_gpu_get_spawn_diagnostics
   public :: sqmc_gpu_set_hubbardk_space_sym, sqmc_gpu_hubbardk_sym_images, sqmc_gpu_debug_bucket_boundaries
-  public :: sqmc_gpu_hci_1rdm, sqmc_gpu_hci_1rdm_pt, sqmc_gpu_hci_2rdm, sqmc_gpu_rotate_integrals, sqmc_gpu_orbital_gradient, sqmc_gpu_hci_greens_function
+  public :: sqmc_gpu_hci_1rdm, sqmc_gpu_hci_1rdm_pt, sqmc_gpu_hci_2rdm, sqmc_gpu_hci_1tdm, sqmc_gpu_hci_2tdm, sqmc_gpu_rotate_integrals, sqmc_gpu_orbital_gradient, sqmc_gpu_hci_greens_function
   public :: sqmc_gpu_spmv_plan_submatrix, sqmc_shell_sort_magnitude
   public :: sqmc_gpu_one_index_transform, sqmc_gpu_orbopt_prepare, sqmc_gpu_orbopt_gradient, sqmc_gpu_orbopt_hessian_vector, sqmc_gpu_orbopt_free
   public :: sqmc_gpu_check
@@ -208,6 +208,17 @@ module sqmc_gpu_mod
     integer(c_int) function sqmc_gpu_hci_2rdm(ctx, n_var, var_up, var_dn, coeffs, blocks, rdm_aa, rdm_bb, rdm_ab) bind(C, name='sqmc_gpu_hci_2rdm')
       import; type(c_ptr), value :: ctx; integer(c_int64_t), value :: n_var; integer(c_int64_t), intent(in) :: var_up(*), var_dn(*)
       real(c_double), intent(in) :: coeffs(*); integer(c_int32_t), value :: blocks; type(c_ptr), value :: rdm_aa, rdm_bb, rdm_ab
+    end function
+    ! the one-body transition density matrix tdm(norb, norb) of two vectors over one list, tdm(p, r) = <bra| a+_r a_p |ket> spin-summed;
+    ! orbital_symmetries as in sqmc_gpu_hci_1rdm
+    integer(c_int) function sqmc_gpu_hci_1tdm(ctx, n_var, var_up, var_dn, bra, ket, orbital_symmetries, tdm) bind(C, name='sqmc_gpu_hci_1tdm')
+      import; type(c_ptr), value :: ctx; integer(c_int64_t), value :: n_var; integer(c_int64_t), intent(in) :: var_up(*), var_dn(*)
+      real(c_double), intent(in) :: bra(*), ket(*); type(c_ptr), value :: orbital_symmetries; real(c_double), intent(out) :: tdm(*)
+    end function
+    ! the two-body transition density matrix in the spin blocks of sqmc_gpu_hci_2rdm: (p, q, r, s) = <bra| a+_p a+_q a_s a_r |ket>
+    integer(c_int) function sqmc_gpu_hci_2tdm(ctx, n_var, var_up, var_dn, bra, ket, blocks, tdm_aa, tdm_bb, tdm_ab) bind(C, name='sqmc_gpu_hci_2tdm')
+      import; type(c_ptr), value :: ctx; integer(c_int64_t), value :: n_var; integer(c_int64_t), intent(in) :: var_up(*), var_dn(*)
+      real(c_double), intent(in) :: bra(*), ket(*); integer(c_int32_t), value :: blocks; type(c_ptr), value :: tdm_aa, tdm_bb, tdm_ab
     end function
     ! the integral rotation of generate_natorb_integrals (hci.f90:3683-3791): rot(norb, norb) with rot(p, k) = component on the
     ! context's orbital k of new orbital p (column-major; the C side reads rot[k norb + p], 0-based); integrals_out(0:n_integrals)

@@ -1849,7 +1849,9 @@ def dense_integrals(host):
 
 def rdm_energy(host, one_rdm, two_rdm_sf):
     """E = sum_pr h_pr D_pr + 1/2 sum_pqrs (pr|qs) G[p,q,r,s] + E_core sum c^2, D the spin-summed one-body matrix of GpuChem.one_rdm,
-    G the spin-free two-body matrix; sum c^2 = trace(D) / nelec (nothing is renormalised)"""
+    G the spin-free two-body matrix; sum c^2 = trace(D) / nelec (nothing is renormalised).  Handed the transition matrices of
+    hci_transition_rdms (GpuChem.one_tdm, spin_free_two_rdm of GpuChem.two_tdm) it is <bra|H|ket>: h is symmetric, the two-body sum
+    pairs (pr|qs) with T[p,q,r,s] as it stands, and trace(D) / nelec is then the overlap <bra|ket>"""
     h, eri, const = dense_integrals(host)
     one = np.asarray(one_rdm, float)
     n2 = float(np.trace(one)) / (host.nup + host.ndn)
@@ -1857,7 +1859,8 @@ def rdm_energy(host, one_rdm, two_rdm_sf):
 
 
 def s_squared(host, d_ab, norm2=1.0):
-    """<S^2> = (Sz^2 + Sz + n_dn) sum c^2 - sum_pq G_ab[q,p,p,q], Sz = (nup - ndn) / 2"""
+    """<S^2> = (Sz^2 + Sz + n_dn) sum c^2 - sum_pq G_ab[q,p,p,q], Sz = (nup - ndn) / 2.  Handed the ab block of GpuChem.two_tdm and
+    norm2 = the overlap <bra|ket> (transition_overlap) it is <bra|S^2|ket>"""
     sz = 0.5 * (host.nup - host.ndn)
     return (sz * sz + sz + host.ndn) * float(norm2) - float(np.einsum("qppq->", np.asarray(d_ab, float)))
 
@@ -1889,6 +1892,134 @@ def two_rdm_host(up, dn, coeffs, norb, blocks="all"):
             J = states[int(j)]
             gone, come = bits(J & ~I), bits(I & ~J)
             w = c[i] * c[j]
+            for extra in combinations(bits(I & J), 2 - len(gone)):
+                A, B = gone + list(extra), come + list(extra)
+                for R, S in ((A[0], A[1]), (A[1], A[0])):
+                    s1 = _occ_sign(J, R); K1 = J ^ (1 << R)
+                    s2 = _occ_sign(K1, S); K2 = K1 ^ (1 << S)
+                    for P, Q in ((B[0], B[1]), (B[1], B[0])):
+                        kind = (P >= norb, Q >= norb, R >= norb, S >= norb)
+                        b = "aa" if not any(kind) else "bb" if all(kind) else "ab" if kind == (False, True, False, True) else None
+                        if b not in out:
+                            continue
+                        s3 = _occ_sign(K2, Q); K3 = K2 | (1 << Q)
+                        out[b][P % norb, Q % norb, R % norb, S % norb] += s1 * s2 * s3 * _occ_sign(K3, P) * w
+    return out
+
+
+# ------------------------------------------------------------------------- transition density matrices of two vectors
+def transition_context(host):
+    """a context of host with time_sym off: what the determinant-basis doors (one_tdm, two_tdm, one_rdm, two_rdm) accept.  The caller closes it"""
+    import copy
+    plain = host
+    if bool(getattr(host, "time_sym", False)):
+        plain = copy.copy(host)
+        plain.time_sym = False
+    return plain.gpu()
+
+
+def hci_transition_rdms(host, up, dn, wts, i, j, blocks="all", g=None):
+    """The one- and two-body transition density matrices between states i (bra) and j (ket) of wts[n, n_states] (0-based columns):
+    (GpuChem.one_tdm's [p, r] array, GpuChem.two_tdm's dict of the blocks asked for).  A time-symmetrised wavefunction is expanded
+    in determinants first; time_symmetrized_to_dets orders its list by up and dn alone, so both expansions share it, and the
+    context is one with time_sym off.  Nothing is renormalised and no symmetry filter is applied.  g: an open context with time_sym
+    off to use (transition_context(host)), for a caller that forms several pairs; None: one is opened and closed here."""
+    w = np.asarray(wts, float)
+    w = w.reshape(len(w), -1)
+    if not (0 <= i < w.shape[1] and 0 <= j < w.shape[1]):
+        raise ValueError("hci_transition_rdms: states %d, %d of %d" % (i, j, w.shape[1]))
+    if bool(getattr(host, "time_sym", False)):
+        z = getattr(host, "z", 1)
+        du, dd, bra = time_symmetrized_to_dets(up, dn, w[:, i], z)
+        ku, kd, ket = time_symmetrized_to_dets(up, dn, w[:, j], z)
+        assert np.array_equal(du, ku) and np.array_equal(dd, kd)
+    else:
+        du, dd, bra, ket = up, dn, w[:, i], w[:, j]
+    own = g is None
+    if own:
+        g = transition_context(host)
+    try:
+        return g.one_tdm(du, dd, bra, ket), g.two_tdm(du, dd, bra, ket, blocks)
+    finally:
+        if own:
+            g.close()
+
+
+def union_expansion(upA, dnA, cA, upB, dnB, cB):
+    """Two wavefunctions on lists of their own (two eps_var, two truncations) on one: (up, dn, a, b), the union of the two lists in
+    sort_dets order and the two coefficient vectors over it, 0.0 where a wavefunction does not hold a determinant"""
+    ua, da, ub, db = (np.asarray(x, np.uint64) for x in (upA, dnA, upB, dnB))
+    ca, cb = np.asarray(cA, float), np.asarray(cB, float)
+    if not (len(ua) == len(da) == len(ca) and len(ub) == len(db) == len(cb)):
+        raise ValueError("union_expansion: a list and its coefficients differ in length")
+    where = {}
+    for k, det in enumerate(zip(ua.tolist(), da.tolist())):
+        if det in where:
+            raise ValueError("union_expansion: a determinant appears twice in the first list")
+        where[det] = (k, None)
+    seen = set()
+    for k, det in enumerate(zip(ub.tolist(), db.tolist())):
+        if det in seen:
+            raise ValueError("union_expansion: a determinant appears twice in the second list")
+        seen.add(det)
+        where[det] = (where[det][0] if det in where else None, k)
+    dets = list(where)
+    up, dn = np.array([d[0] for d in dets], np.uint64), np.array([d[1] for d in dets], np.uint64)
+    a = np.array([0.0 if where[d][0] is None else ca[where[d][0]] for d in dets])
+    b = np.array([0.0 if where[d][1] is None else cb[where[d][1]] for d in dets])
+    order = sort_dets(up, dn)
+    return up[order], dn[order], a[order], b[order]
+
+
+def transition_overlap(host, one):
+    """<bra|ket> = trace(one) / nelec of a one-body transition matrix (every determinant holds nelec electrons)"""
+    return float(np.trace(np.asarray(one, float))) / (host.nup + host.ndn)
+
+
+def natural_transition_orbitals(one):
+    """The singular value decomposition of the spin-summed one-body transition matrix T[p, r] = <bra| a+_r a_p |ket>:
+    (singular values in decreasing order, hole[norb, k], particle[norb, k]) with T = hole diag(values) particle^T; column k of hole
+    is the orbital the electron leaves (index p), column k of particle the one it enters (index r)"""
+    t = np.asarray(one, float)
+    if t.ndim != 2 or t.shape[0] != t.shape[1]:
+        raise ValueError("natural_transition_orbitals: one must be (norb, norb)")
+    u, sv, vt = np.linalg.svd(t)
+    return sv, u, vt.T
+
+
+def ci_orbital_coupling(g, up, dn, c, v):
+    """The orbital-CI block of the coupled response: the derivative of the orbital gradient along a trial CI vector v at coefficients
+    c, an antisymmetric (norb, norb) array.  The energy is quadratic in c, so this is the orbital gradient evaluated on the
+    symmetrised transition matrices D_s = T1 + T1^T, G_s = sf(T2) + sf(T2).transpose(2, 3, 0, 1) with T = T(c, v), and equals
+    [gradient(c + v) - gradient(c - v)] / 2 exactly in exact arithmetic.  Chem contexts only (GpuChem.orbital_gradient)."""
+    t1 = g.one_tdm(up, dn, c, v)
+    sf = spin_free_two_rdm(g.two_tdm(up, dn, c, v))
+    return g.orbital_gradient(t1 + t1.T, sf + sf.transpose(2, 3, 0, 1), outputs="gradient")["gradient"]
+
+
+def two_tdm_host(up, dn, bra, ket, norb, blocks="all"):
+    """GpuChem.two_tdm's blocks by a plain evaluation over all pairs of the list, as two_rdm_host: the timing yardstick of
+    tools/tdm_time.py, quadratic in the list."""
+    from itertools import combinations
+    names = ("aa", "bb", "ab") if blocks == "all" else (blocks,) if isinstance(blocks, str) else tuple(blocks)
+    up, dn, cb, ck = np.asarray(up, np.uint64), np.asarray(dn, np.uint64), np.asarray(bra, float), np.asarray(ket, float)
+    out = {b: np.zeros((norb,) * 4, order="F") for b in names}
+    states = [int(a) | (int(b) << norb) for a, b in zip(up, dn)]
+    pop = np.array([bin(x).count("1") for x in range(65536)], np.uint8)
+
+    def popcount(x):
+        return sum(pop[(x >> np.uint64(16 * k)) & np.uint64(0xFFFF)].astype(np.int32) for k in range(4))
+
+    def bits(x):
+        return [k for k in range(2 * norb) if x >> k & 1]
+
+    for i in range(len(cb)):
+        near = np.nonzero(popcount(up ^ up[i]) + popcount(dn ^ dn[i]) <= 4)[0]
+        I = states[i]
+        for j in near:
+            J = states[int(j)]
+            gone, come = bits(J & ~I), bits(I & ~J)
+            w = cb[i] * ck[j]
             for extra in combinations(bits(I & J), 2 - len(gone)):
                 A, B = gone + list(extra), come + list(extra)
                 for R, S in ((A[0], A[1]), (A[1], A[0])):

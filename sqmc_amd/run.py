@@ -308,6 +308,43 @@ def run_two_rdm(h, up, dn, wts, energy, p, path):
     return rows
 
 
+def run_transition_rdm(h, up, dn, wts, p, path):
+    """--transition-rdm PATH: the one- and two-body transition density matrices of every pair of states i < j of the variational
+    wavefunction (host.hci_transition_rdms, bra i and ket j), per pair the overlap, <i|H|j> and <i|S^2|j> from the matrices and the
+    three largest singular values of the spin-summed one-body matrix in print, and all matrices in one new .npz (one_1_2, aa_1_2,
+    bb_1_2, ab_1_2, ...: arrays [p, r] and [p, q, r, s])"""
+    from . import host as H
+    if os.path.exists(path):                         # before any work is done, as --rotate-integrals
+        raise FileExistsError("sqmc_amd: %s exists; the transition density matrices are written to a new file only" % path)
+    saved, rows = {}, []
+    p("\nComputing transition density matrices between the states of the variational wavefunction")
+    g = H.transition_context(h)                      # one context for every pair of states
+    pairs = []
+    try:
+        for i in range(wts.shape[1]):
+            for j in range(i + 1, wts.shape[1]):
+                pairs.append((i, j) + H.hci_transition_rdms(h, up, dn, wts, i, j, g=g))
+    finally:
+        g.close()
+    for i, j, one, d in pairs:
+        ovl = H.transition_overlap(h, one)
+        hij, sij = H.rdm_energy(h, one, H.spin_free_two_rdm(d)), H.s_squared(h, d["ab"], ovl)
+        sv = H.natural_transition_orbitals(one)[0]
+        p("\nTransition density matrices of states%4d and%4d:" % (i + 1, j + 1))
+        p(" Overlap =%10.2E" % ovl)
+        p(" <i|H|j> from the density matrices =%10.2E" % hij)
+        p(" <i|S^2|j> =%10.2E" % sij)
+        p(" Largest singular values of the one-body matrix =" + "".join("%14.9f" % x for x in sv[:3]))
+        saved["one_%d_%d" % (i + 1, j + 1)] = one
+        for b in d:
+            saved["%s_%d_%d" % (b, i + 1, j + 1)] = d[b]
+        rows.append(dict(states=(i + 1, j + 1), overlap=ovl, h=hij, s_squared=sij, singular_values=[float(x) for x in sv[:3]]))
+    with open(path, "xb") as f:
+        np.savez(f, **saved)
+    p("\nTransition density matrices written to " + path)
+    return rows
+
+
 def run_optimize_orbitals(h, up, dn, wts, energy, p, path, solver="diagonal"):
     """--optimize-orbitals [PATH]: one orbital-optimisation step on the variational wavefunction (host.optimize_orbitals_step; several
     states: their averaged matrices), its figures in print, and the rotated integrals written to PATH, a new file in the format of
@@ -338,7 +375,7 @@ def run_optimize_orbitals(h, up, dn, wts, energy, p, path, solver="diagonal"):
 
 
 def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False, pt_diag_update=0, one_rdm_path=None, natorb_fcidump=None, greens_signed=False,
-            extrap_rebuild=False, two_rdm_path=None, optimize_orbitals=None, orbopt_solver="diagonal"):
+            extrap_rebuild=False, two_rdm_path=None, optimize_orbitals=None, orbopt_solver="diagonal", transition_rdm_path=None):
     """pt_on_device: the samples of the semistochastic PT are evaluated by the library (host.hci_pt2_stochastic on_device);
     pt_diag_update: 0 / 1 / 2, how the PT stage forms H_aa (host.hci_pt2); one_rdm_path: with &natorb get_natorbs = t, also save the
     1-RDM there as .npy; natorb_fcidump: with &natorb get_natorbs = t, rotate the integrals into the natural orbitals and write them
@@ -350,7 +387,15 @@ def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False, pt_diag
     then holds two_rdm, its per-state records.  Without it the output is what it is without this argument.  optimize_orbitals: after
     the variational stage (and run_two_rdm), run_optimize_orbitals writing to this new file (True: FCIDUMP_opt_eps_var=<smallest
     eps_var>); the result then holds optimize_orbitals.  Without it the output is what it is without this argument.  orbopt_solver:
-    "diagonal" (the step as it always was) or "newton" (run_optimize_orbitals); only with optimize_orbitals."""
+    "diagonal" (the step as it always was) or "newton" (run_optimize_orbitals); only with optimize_orbitals.  transition_rdm_path:
+    after the variational stage (and run_two_rdm), run_transition_rdm on every pair of states; the result then holds
+    transition_rdm, its per-pair records.  Without it the output is what it is without this argument."""
+    if transition_rdm_path and (deck["hamiltonian_type"] == "heg" or deck.get("get_natorbs") or deck.get("n_energy_batch", 0) > 0):
+        raise SystemExit("--transition-rdm runs between the variational and the PT stage of a chem deck: not with heg, &natorb get_natorbs or n_energy_batch > 0, which end elsewhere")
+    if transition_rdm_path and deck["n_states"] < 2:
+        raise SystemExit("--transition-rdm needs two states at least: n_states = %d" % deck["n_states"])
+    if transition_rdm_path and deck["nelec"] < 2:
+        raise SystemExit("--transition-rdm needs at least two electrons")
     if orbopt_solver not in ("diagonal", "newton"):
         raise SystemExit("--orbopt-solver: diagonal or newton")
     if orbopt_solver != "diagonal" and not optimize_orbitals:
@@ -414,6 +459,10 @@ def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False, pt_diag
     if two_rdm_path:
         two_rdm = run_two_rdm(h, up, dn, np.asarray(wts, float).reshape(len(up), -1), energy, p, two_rdm_path)
         t0, t1 = t0 + (time.perf_counter() - t1), time.perf_counter()      # keep the stage out of both times of the last line
+    transition = None
+    if transition_rdm_path:
+        transition = run_transition_rdm(h, up, dn, np.asarray(wts, float).reshape(len(up), -1)[:, :n_states], p, transition_rdm_path)
+        t0, t1 = t0 + (time.perf_counter() - t1), time.perf_counter()      # keep the stage out of both times of the last line
     optorb = None
     if optimize_orbitals:
         if optimize_orbitals is True:
@@ -458,6 +507,8 @@ def run_hci(deck, fcidump="FCIDUMP", out=sys.stdout, pt_on_device=False, pt_diag
         res["greens"] = greens
     if two_rdm is not None:
         res["two_rdm"] = two_rdm
+    if transition is not None:
+        res["transition_rdm"] = transition
     if optorb is not None:
         res["optimize_orbitals"] = optorb
     return res
@@ -501,6 +552,10 @@ def main(argv=None):
     ap.add_argument("--orbopt-solver", choices=("diagonal", "newton"), default="diagonal", help="with --optimize-orbitals: the diagonal-Newton step (default) or "
                     "a line-search Newton-CG step on the device's orbital Hessian-vector products; prints the number of products, why the solver stopped and "
                     "the predicted beside the actual change")
+    ap.add_argument("--transition-rdm", default=None, metavar="PATH", help="chem HCI decks with n_states >= 2: after the variational stage compute the one- and "
+                    "two-body transition density matrices of every pair of states on the device, print the overlap, <i|H|j> and <i|S^2|j> they give and the "
+                    "largest singular values of the one-body matrix, and save them to PATH, a new .npz; refused with n_states = 1, heg decks, &natorb "
+                    "get_natorbs and n_energy_batch > 0")
     a = ap.parse_args(argv)
     text = open(a.input).read() if a.input else sys.stdin.read()
     lines = [l for l in text.splitlines() if l.strip() and not l.lstrip().startswith("!")]
@@ -511,7 +566,8 @@ def main(argv=None):
                         dtm_elems_in=a.dtm_elems_in, dtm_elems_out=a.dtm_elems_out, spawn_histograms=a.spawn_histograms)
     deck = parse_hci_deck(text)
     return run_hci(deck, a.fcidump, pt_on_device=a.pt_on_device, pt_diag_update=a.pt_diag_update, one_rdm_path=a.one_rdm, natorb_fcidump=a.rotate_integrals,
-                   greens_signed=a.greens_signed, extrap_rebuild=a.extrap_rebuild, two_rdm_path=a.two_rdm, optimize_orbitals=a.optimize_orbitals, orbopt_solver=a.orbopt_solver)
+                   greens_signed=a.greens_signed, extrap_rebuild=a.extrap_rebuild, two_rdm_path=a.two_rdm, optimize_orbitals=a.optimize_orbitals, orbopt_solver=a.orbopt_solver,
+                   transition_rdm_path=a.transition_rdm)
 
 
 if __name__ == "__main__":

@@ -2,7 +2,7 @@
 # Registers, spills, LDS and occupancy of every kernel of libsqmc_gpu, from the compiler's own remarks (no GPU needed).
 # usage: tools/kernel_resources.sh [extra hipcc flags] > profiles/rNN_kernel_resources.txt
 cd "$(dirname "$0")/.."
-for unit in sqmc_amd/csrc/sqmc_gpu.hip sqmc_amd/csrc/rdm2_device.hip sqmc_amd/csrc/orbopt_device.hip; do
+for unit in sqmc_amd/csrc/sqmc_gpu.hip sqmc_amd/csrc/rdm2_device.hip sqmc_amd/csrc/orbopt_device.hip sqmc_amd/csrc/tdm_device.hip; do
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-value -Iinclude "$@" \
   -Rpass-analysis=kernel-resource-usage -c $unit -o /dev/null 2>&1
 done | python3 -c '
